@@ -2,7 +2,12 @@
 """bench.py -- BASELINE.json's metric on MI355X: stereo PCM samples/s through the
 IIR + 50 ms RMS + histogram path, with the dB delta against the CPU oracle.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` then also writes what the last
+timed step handed its caller (per-track results, histograms, the album result) as DIR/<name>.npy.  Everything else the line
+can carry -- `one_shot`, `configs1`, `mp3_end_to_end`, `parity`, `cpu_baseline` -- is measured with `--full` only (null
+without it); the `--no-*` switches and `--cpu-seconds 0` drop single legs of a `--full` run.
 
 A "step" is one pass of the hot path over one batch of synthetic PCM that is already resident
 in HBM (generated there by the library's rg_synth kernel; include/rg_synth.h):
@@ -19,7 +24,8 @@ in HBM (generated there by the library's rg_synth kernel; include/rg_synth.h):
            album fixed instead and shards it by cumulative frames (configs[3]'s 8000-track album on N GPUs:
            `--scaling strong --total-tracks 8000`); both curves can come out of one 8-GPU lease.  One rank per GPU,
            launched by torch.distributed.run.  Every N > 1 line carries `exchange` (ranks of the library's communicator,
-           transport, ncclGetVersion), `parity` (rank 0's first tracks against the oracle, bin for bin) and `cpu_baseline`.
+           transport, ncclGetVersion) and, with `--full`, `parity` (rank 0's first tracks against the oracle, bin for bin) and
+           `cpu_baseline`.
 
 Timing: an untimed pre-roll (0.25 s worth of steps, so that clock and power have settled), W warm-up
 steps, then exactly K steps between barrier + torch.cuda.synchronize() pairs; the time is the MAX
@@ -53,6 +59,8 @@ ALGO_FLOP_PER_FRAME = 108          # 2 x (21 + 5 + 1) FMA
 HBM_PEAK_GBPS = 8000.0             # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 FP64_PEAK_TFLOPS = 78.6            # MI355X FP64 vector: 256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz
 PROFILE_ROUND = "r06"
+DUMP_BUDGET_BYTES = 64 << 20       # --dump-outputs: all arrays together
+DUMP_SAMPLE_SEED = 0x5EED          # --dump-outputs: which tracks' histograms when not all of them fit
 
 
 class _DevArray:
@@ -73,6 +81,33 @@ def _usable_cores() -> int:
     except (OSError, ValueError):
         pass
     return n
+
+
+def dump_outputs(out_dir: str, track_index, res, hists=None, album=None) -> None:
+    """--dump-outputs: what the timed path handed its caller after the last timed step, as DIR/<name>.npy.
+    Per-track records of every track (track_<field>.npy, float64, in the order of track_index.npy: the tracks' global
+    indices, whose seed is 0x5EED0000 + index), the 12 000-bin histograms as float32 (counts, exact below 2^24) -- of every
+    track if they fit the budget, else of a fixed seeded sample of them (histogram_track_index.npy says which) -- and the
+    album record (album_<field>.npy, one element each) when the step was an album step."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {"track_index": np.asarray(track_index, dtype=np.float64)}
+    for f in ("loudness_db", "gain_db", "peak", "sample_rate", "windows", "flags"):
+        arrays[f"track_{f}"] = np.array([getattr(r, f) for r in res], dtype=np.float64)
+    if album is not None:
+        for f in ("album_loudness_db", "album_gain_db", "album_peak", "album_gain_steps", "windows"):
+            arrays[f if f.startswith("album_") else f"album_{f}"] = np.array([getattr(album, f)], dtype=np.float64)
+    if hists is not None and len(res):
+        room = DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values()) - 8 * len(res)
+        rows = min(len(res), max(0, room // (4 * hists.shape[1])))
+        pick = (np.arange(len(res)) if rows == len(res)
+                else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(res), size=rows, replace=False)))
+        arrays["histogram_track_index"] = np.asarray(track_index, dtype=np.float64)[pick]
+        arrays["histograms"] = np.asarray(hists[pick], dtype=np.float32)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
 
 
 def workload_tag(ntr: int, frames: int, album: bool) -> str:
@@ -426,10 +461,11 @@ def node_main(args) -> int:
             dt = time.perf_counter() - t0
             ks, kl, ksp = an.timing_read(reset=True)
             an.timing_enable(False)
-            res, hists = an.collect(ntr, want_hist=True) if i == 0 else (an.collect(ntr), None)
+            res, hists = an.collect(ntr, want_hist=True) if i == 0 or args.dump_outputs else (an.collect(ntr), None)
             alb = an.album_finish()
             npar = min(args.parity_tracks, ntr)
             out[i] = {"dt": dt, "frames": frames * ntr, "k": (ks, kl, ksp), "album": alb, "first": res[0] if res else None,
+                      "mine": mine, "all_res": res, "all_hists": hists if args.dump_outputs else None,
                       "flagged": sum(1 for r in res if r.flags & 2), "seeds": [0x5EED0000 + g for g in mine[:npar]],
                       "res": res[:npar], "hists": hists[:npar].copy() if hists is not None else None,
                       "exchange": exchange_block(an, "rccl (library communicators of this process, ncclCommInitAll)")}
@@ -450,8 +486,12 @@ def node_main(args) -> int:
     tag = workload_tag(args.tracks_per_rank, frames, True)
     roof = roofline_block(out[0]["frames"], ks, kl, ksp, tag)
     alb0 = out[0]["album"]
+    if args.dump_outputs:  # every device's tracks, in album order
+        order = sorted(((g, o["all_res"][t], o["all_hists"][t]) for o in out for t, g in enumerate(o["mine"])), key=lambda e: e[0])
+        dump_outputs(args.dump_outputs, [e[0] for e in order], [e[1] for e in order],
+                     np.stack([e[2] for e in order]) if order else None, alb0)
     parity = cpu = None
-    if args.cpu_seconds > 0 and out[0]["seeds"]:
+    if args.full and args.cpu_seconds > 0 and out[0]["seeds"]:
         # device 0's first tracks of the album (global indices 0, n_dev, 2 n_dev, ...) against the oracle, bin for bin
         from oracle import pyoracle as po
 
@@ -524,6 +564,12 @@ def main() -> int:
                     help="ONE process for all --gpus devices (include/mp3rgain_amd_node.h: one context and one host thread per GPU, "
                          "the library's in-process RCCL communicators for the album exchange) instead of one rank per GPU; "
                          "also what `--gpus N` does when it is not launched through torch.distributed.run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: one_shot, configs1, mp3_end_to_end, parity, "
+                         "cpu_baseline (without it they are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (per-track results, histograms, album result) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
 
     import numpy as np
@@ -699,11 +745,13 @@ def main() -> int:
     alb = an.album_finish() if album else None
     n_imprecise = sum(1 for r in res if r.flags & 2)
     n_nonfinite = sum(1 for r in res if r.flags & 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mine, res, hists, alb)
 
     # ---- one batch in flight: the synchronous entry point (rg_analyze_pcm_batch on the resident arena) -- the shape the
     # reference's blocking API has.  Nothing overlaps here: the dominant kernel's HIP-event duration IS one launch alone.
     one_shot = None
-    if world == 1 and not album and ntr > 0 and not args.no_one_shot:
+    if args.full and world == 1 and not album and ntr > 0 and not args.no_one_shot:
         for _ in range(3):
             an.analyze_device(descs, ntr, pcm.data_ptr(), pcm_bytes)
         an.timing_enable(True)
@@ -751,7 +799,7 @@ def main() -> int:
 
     # ---- secondary workload on one GPU: configs[1], one 10-minute track (fits the Infinity Cache) ----------
     configs1 = None
-    if world == 1 and not args.no_configs1 and not album and not args.mixed:
+    if args.full and world == 1 and not args.no_configs1 and not album and not args.mixed:
         pcm1, descs1, bytes1 = make_batch([(0x5EED0000, RATE, 2, FRAMES_10MIN)])
 
         def step1():
@@ -774,7 +822,7 @@ def main() -> int:
     # ---- informational leg on one GPU: from compressed MP3 files to album gain (north_star's "MP3 frame decode to
     # PCM" in front of the measured path).  Never `value`: it includes file reads, the host's frame walk and PCIe. ----
     mp3_leg = None
-    if world == 1 and not args.no_mp3 and not album and not args.mixed:
+    if args.full and world == 1 and not args.no_mp3 and not album and not args.mixed:
         try:
             mp3_leg = mp3_end_to_end(an, args.mp3_files)
         except Exception as ex:  # noqa: BLE001
@@ -784,7 +832,7 @@ def main() -> int:
     if rank == 0:
         cpu = None
         parity = None
-        if args.cpu_seconds > 0 and ntr > 0:
+        if args.full and args.cpu_seconds > 0 and ntr > 0:
             from oracle import pyoracle as po
 
             # ---- parity: full histograms of the first tracks of this rank's batch against the oracle ----

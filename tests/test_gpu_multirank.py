@@ -165,7 +165,7 @@ def test_bench_rank_mode_rehearsal(standin, oracle, world):
     tracks_per_rank, minutes = 3, 0.1
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), "bench.py", "--gpus", str(world), "--steps", "4", "--warmup", "2", "--tracks-per-rank",
-           str(tracks_per_rank), "--minutes", str(minutes), "--cpu-seconds", "0.2", "--pre-roll", "0.001", "--parity-tracks", "2"]
+           str(tracks_per_rank), "--minutes", str(minutes), "--cpu-seconds", "0.2", "--pre-roll", "0.001", "--parity-tracks", "2", "--full"]
     p = subprocess.run(cmd, cwd=str(ROOT), env=_bench_env(standin), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith("{") and '"metric"' in ln]
@@ -205,7 +205,7 @@ def test_bench_node_mode_rehearsal(standin, oracle):
     """`bench.py --node --gpus 3` with three contexts on device 0: in-process communicators, one host thread per context."""
     tracks_per_rank, minutes = 2, 0.1
     cmd = [sys.executable, "bench.py", "--node", "--gpus", "3", "--steps", "4", "--warmup", "2", "--tracks-per-rank", str(tracks_per_rank),
-           "--minutes", str(minutes), "--pre-roll", "0.001", "--cpu-seconds", "0.2", "--parity-tracks", "2"]
+           "--minutes", str(minutes), "--pre-roll", "0.001", "--cpu-seconds", "0.2", "--parity-tracks", "2", "--full"]
     p = subprocess.run(cmd, cwd=str(ROOT), env=_bench_env(standin), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:]
     o = _json_line(p.stdout)

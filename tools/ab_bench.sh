@@ -4,7 +4,7 @@
 for round in 1 2; do
   for lib in "$@"; do
     if [ "$lib" = default ]; then unset MP3RGAIN_AMD_LIB; else export MP3RGAIN_AMD_LIB=build_ab/lib$lib.so; fi
-    python bench.py --no-mp3 --cpu-seconds 0 ${AB_ARGS} 2>/dev/null | python -c "
+    python bench.py --full --no-mp3 --cpu-seconds 0 ${AB_ARGS} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 o=d.get('one_shot') or {}; c=d.get('configs1') or {}

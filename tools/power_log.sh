@@ -8,7 +8,7 @@ cd $R
 ( while true; do echo "t=$(date +%s.%N) $(rocm-smi -d 0 --showpower --showclocks --showtemp --csv 2>/dev/null | tail -n +2 | tr '\n' ' ')"; sleep 0.2; done ) > $OUTF.raw &
 SPID=$!
 sleep 1
-python bench.py --cpu-seconds 0 --no-configs1 "$@" > $OUTF.bench.json 2> $OUTF.err
+python bench.py --full --cpu-seconds 0 --no-configs1 "$@" > $OUTF.bench.json 2> $OUTF.err
 sleep 1
 kill $SPID
 rocm-smi -d 0 --showpower --showclocks --showmaxpower --csv > $OUTF.header 2>/dev/null
