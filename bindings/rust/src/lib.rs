@@ -11,7 +11,7 @@
 //!   (`:929-941`), `analyze_album[_with_index]` (`:1033-1074`), `find_peak_amplitude` (`:1140`), `is_available`
 //!   (`:1119`), the result structs (`:57-95`, `:1125-1132`) -- implemented over the library: a maintainer replaces
 //!   `mod replaygain;` by `pub use mp3rgain_amd::replaygain;` and the callers in `src/main.rs` / `src/lib.rs` compile
-//!   unchanged.  MPEG Layer III is decoded by the library (on the GPU); an M4A/AAC file needs
+//!   unchanged.  MPEG Layer III and native FLAC are decoded by the library (on the GPU), WAV is read directly; an M4A/AAC file needs
 //!   [`replaygain::set_decoder_command`].
 //!
 //! The seam *after* the decoder (the host keeps symphonia and hands decoded PCM over) is

@@ -194,7 +194,10 @@ int rg_set_kernel(rg_ctx *ctx, int variant);
  * INTEGRATION.md -- and the library never calls getenv after rg_create): key 10 = album parts: 1 =
  * never, 2 = on, 3 = on for copy-bound chunks only (not for chunks the device had to wait for the host's loaders for); key 11 = the copy-bound rule of the parts, compressed bytes per granule-channel from which a chunk
  * becomes a part, PLUS ONE (1 = every chunk); key 12 = bytes of a pinned staging block (>= 4096); key 13 = estimated PCM
- * bytes per group of files of rg_analyze_tracks / rg_analyze_album.
+ * bytes per group of files of rg_analyze_tracks / rg_analyze_album,
+ * key 14 = how FLAC files of the file-level entry points are decoded (mp3rgain_amd_flac.h; identical PCM, bit for bit):
+ * 1 (default) = the host walks the frames, the GPU checks, lays out and decodes them straight into the analysis arena;
+ * 0 = the host decoder.
  * (Key 9 of ABI 4 -- windows 2..m in a kernel of their own -- is gone with that kernel: it spilled and was never faster.) */
 int rg_set_tuning(rg_ctx *ctx, int key, int64_t value);
 /* diagnostic (host only): variant 2's design for one rate and segment length.  T_out: [L][12],

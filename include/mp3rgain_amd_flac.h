@@ -1,0 +1,91 @@
+/* mp3rgain_amd_flac.h -- C ABI of the FLAC decode row: a native FLAC stream (optionally behind an ID3v2 tag) -> planar
+ * integer PCM, on the host (rg_flac_decode_s32) and on the device (rg_flac_decode_device, and the file-level entry points
+ * of mp3rgain_amd.h, tuning key 14).
+ *
+ * Scope: every subframe type (CONSTANT, VERBATIM, FIXED 0-4, LPC 1-32 with up to 15-bit coefficients), wasted bits,
+ * Rice / Rice2 partitions of order 0-15 with escape codes, independent (1-8 channels), left/side, right/side and mid/side
+ * channel assignments, every block-size and sample-rate header code, 4-24 bits per sample.  A stream of 25-32 bits per
+ * sample is reported as RG_FLAC_ERR_UNSUPPORTED (the file route hands it to the decoder command).
+ *
+ * Frames.  The stream is walked by a byte-aligned forward scan (rg_flac_index_frames): a frame header is accepted when its
+ * sync code, reserved bits, fields, CRC-8 and frame / sample number all hold (the number continues the previous accepted
+ * frame's: strictly after it, at most 64 frames -- or 64 x 65536 samples -- later).  A frame reaches to the next accepted
+ * header or to the end of the data (the last frame ends at the last point its CRC-16 holds, so a trailing tag is not part
+ * of it).  A frame whose CRC-16 does not match, that does not parse, or whose samples do not fit their width is dropped and
+ * contributes no samples: the rule the MPEG decoder follows (DecodeError -> continue, src/replaygain.rs:896-899).  The
+ * reference decodes FLAC with symphonia, whose source is not in the reference tree; its handling of damaged FLAC could not
+ * be compared, and this rule is the project's own.
+ *
+ * Host code (apart from rg_flac_decode_device), plain C types, no exceptions or aborts across the ABI.
+ */
+#ifndef MP3RGAIN_AMD_FLAC_H
+#define MP3RGAIN_AMD_FLAC_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef enum rg_flac_status {
+    RG_FLAC_OK = 0,
+    RG_FLAC_ERR_ARG = -1,
+    RG_FLAC_ERR_NOT_FLAC = -2,    /* no "fLaC" marker or no valid STREAMINFO                                   */
+    RG_FLAC_ERR_CAPACITY = -3,    /* output too small (what is needed is in the info)                          */
+    RG_FLAC_ERR_UNSUPPORTED = -4  /* a FLAC stream this decoder does not take (25-32 bits per sample)          */
+} rg_flac_status;
+
+typedef struct rg_flac_info {
+    uint32_t sample_rate;      /* STREAMINFO                                                                   */
+    uint32_t channels;
+    uint32_t bits_per_sample;
+    uint32_t min_block_size;
+    uint32_t max_block_size;
+    uint32_t id3v2_bytes;      /* tag skipped in front of "fLaC"                                               */
+    uint64_t total_samples;    /* STREAMINFO, per channel; 0 = unknown                                         */
+    uint64_t metadata_bytes;   /* offset of the first byte after the metadata blocks (ID3v2 tag included)      */
+    uint64_t frames;           /* PCM frames per channel: index = if every frame decodes, decode = produced     */
+    uint32_t audio_frames;     /* FLAC frames: indexed / decoded                                               */
+    uint32_t dropped_frames;   /* indexed frames that did not decode (CRC-16, parse, range)                    */
+} rg_flac_info;
+
+typedef struct rg_flac_frame {
+    uint64_t offset;           /* byte offset of the frame header in the data                                 */
+    uint64_t first_sample;     /* from the header: frame number x max block size, or the sample number         */
+    uint32_t length;           /* bytes, CRC-16 included                                                       */
+    uint32_t block_size;
+    uint8_t channel_assignment;/* 0-7: channels - 1 independent; 8 left/side, 9 right/side, 10 mid/side        */
+    uint8_t header_length;     /* bytes of the frame header, CRC-8 included                                    */
+    uint16_t reserved;
+    uint32_t reserved2;
+} rg_flac_frame;               /* 32 bytes */
+
+/* 1 if `data` is a native FLAC stream (after an optional ID3v2 tag). */
+int rg_flac_is_flac(const void *data, size_t len);
+
+/* Metadata only: STREAMINFO, the ID3v2 and metadata sizes (frames / audio_frames / dropped_frames are 0). */
+int rg_flac_scan(const void *data, size_t len, rg_flac_info *out);
+
+/* The frame walk.  Writes up to `capacity` entries; *n_frames = frames found (RG_FLAC_ERR_CAPACITY if more than
+ * `capacity`).  out->frames = the sum of their block sizes. */
+int rg_flac_index_frames(const void *data, size_t len, rg_flac_frame *frames, size_t capacity, size_t *n_frames, rg_flac_info *out);
+
+/* Decode a whole stream into `channels` planes of `capacity` int32 samples each, right-justified.  On RG_FLAC_OK
+ * out->frames is the number of samples written per channel and out->dropped_frames the frames dropped. */
+int rg_flac_decode_s32(const void *data, size_t len, int32_t *const *planes, uint64_t capacity, rg_flac_info *out);
+
+/* The index and the decoder agree on the frame count and the PCM length: 0 = yes, 1 = no, < 0 = not decodable. */
+int rg_flac_index_selfcheck(const void *data, size_t len);
+
+/* Text of the calling thread's last error ("" if none). */
+const char *rg_flac_last_error(void);
+
+/* Test seam of the device decoder: the stream through the file route's device kernels (frame check, layout, decode),
+ * PCM back to `planes` as rg_flac_decode_s32 returns it (bit for bit, tests/test_gpu_flac.py).  `ctx` is an rg_ctx. */
+int rg_flac_decode_device(void *ctx, const void *data, size_t len, int32_t *const *planes, uint64_t capacity, rg_flac_info *out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MP3RGAIN_AMD_FLAC_H */

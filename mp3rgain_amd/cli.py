@@ -223,6 +223,20 @@ def _is_riff_wave(file) -> bool:
     return len(head) == 12 and head[:4] == b"RIFF" and head[8:] == b"WAVE"
 
 
+def _is_flac(file) -> bool:
+    """A native FLAC stream by its bytes ("fLaC", also behind an ID3v2 tag), as _is_riff_wave recognises WAV."""
+    try:
+        with open(file, "rb") as f:
+            head = f.read(10)
+            skip = 0
+            if len(head) == 10 and head[:3] == b"ID3" and not any(b & 0x80 for b in head[6:10]):
+                skip = 10 + ((head[6] << 21) | (head[7] << 14) | (head[8] << 7) | head[9]) + (10 if head[5] & 0x10 else 0)
+            f.seek(skip)
+            return f.read(4) == b"fLaC"
+    except OSError:
+        return False
+
+
 def _file_result(file: Path, **kw) -> dict:
     d = {"file": str(file)}
     for k in _FILE_KEYS[1:]:
@@ -839,6 +853,12 @@ class Cli:
             if self.talk:
                 self.e(f"  x {name} - {msg}")
             return _file_result(file, status="error", error=msg)
+        if _is_flac(file):
+            # FLAC has no global_gain fields either; ReplayGain tags (Vorbis comments) are not written yet
+            msg = "FLAC input is analysed only: lossless gain applies to MPEG Layer III frames"
+            if self.talk:
+                self.e(f"  x {name} - {msg}")
+            return _file_result(file, status="error", error=msg)
         fn = mp3gain.apply_gain_with_undo_wrap if o.wrap_gain else mp3gain.apply_gain_with_undo
         try:
             frames = self._with_temp_file(file, lambda f: fn(f, actual))
@@ -934,7 +954,7 @@ def expand_files_recursive(paths: List[Path]) -> List[Path]:  # src/main.rs:436-
             p = Path(entry.path)
             if entry.is_dir():
                 walk(p)
-            elif p.suffix.lower() in (".mp3", ".m4a", ".aac", ".mp4"):
+            elif p.suffix.lower() in (".mp3", ".m4a", ".aac", ".mp4", ".flac"):
                 out.append(p)
 
     for p in paths:

@@ -315,6 +315,9 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_peak_bits.release();
     c->d_arena.release();
     c->d_wav.release();
+    c->d_flac_blob.release();
+    c->d_flac_work.release();
+    c->h_flac_stage.release();
     if (c->file_pool && c->file_pool_free) c->file_pool_free(c->file_pool);
     c->file_pool = nullptr;
     c->d_mp3_tab.release();
@@ -401,6 +404,10 @@ extern "C" int rg_set_tuning(rg_ctx *c, int key, int64_t value) {
             c->tune_stage_bytes = (size_t)value;
             return RG_OK;
         case RG_TUNE_GROUP_BYTES: c->tune_group_bytes = (size_t)value; return RG_OK;
+        case RG_TUNE_GPU_FLAC_DECODE:
+            if (value > 1) return rg_set_err(c, RG_ERR_INVALID_ARG, "tuning key 14 takes 0 (host decoder) or 1 (device decoder, default)");
+            c->gpu_flac_decode = (int)value;
+            return RG_OK;
         case RG_TUNE_PIPELINE_SLOTS: {
             if (sync_all(c) != RG_OK) return RG_ERR_DEVICE;
             c->n_slots = value == 0 ? RG_DEFAULT_SLOTS : (value > RG_MAX_SLOTS ? RG_MAX_SLOTS : (int)value);

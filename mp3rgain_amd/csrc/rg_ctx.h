@@ -64,7 +64,7 @@ struct RgTmDeviceTables {
 
 enum { RG_TUNE_TM_SEGMENT = 1, RG_TUNE_TM_TARGET_LANES = 2, RG_TUNE_PIPELINE_SLOTS = 3, RG_TUNE_TM_WINDOWS = 4, RG_TUNE_INGEST_CHUNK_KIB = 5,
        RG_TUNE_GPU_MP3_DECODE = 6, RG_TUNE_LOADER_THREADS = 7, RG_TUNE_ALBUM_PARTS = 10, RG_TUNE_PARTS_MIN_BPU = 11,
-       RG_TUNE_STAGE_BYTES = 12, RG_TUNE_GROUP_BYTES = 13 };
+       RG_TUNE_STAGE_BYTES = 12, RG_TUNE_GROUP_BYTES = 13, RG_TUNE_GPU_FLAC_DECODE = 14 };
 
 #define RG_MAX_SLOTS 8
 #define RG_SLOT_STREAMS 4   // HIP streams the slots are spread over (the runtime has 4 hardware queues by default)
@@ -183,6 +183,10 @@ struct rg_ctx {
     int gpu_mp3_decode = 3;                  // tuning key 6: 0 = host decoder, 1 = stages B-E of MP3 decoding run on the device,
                                              // 2 = scalefactors + Huffman too, 3 (default) = side-information parsing too: the host
                                              // only finds the frames and strips their headers (loader pipeline, rg_files.hip)
+    int gpu_flac_decode = 1;                 // tuning key 14: 0 = host FLAC decoder, 1 (default) = the device decoder (rg_flacdev.hip)
+    DevBuf<unsigned char> d_flac_blob;       // rg_flacdev.hip: the staged FLAC streams, their frame index and stream table
+    DevBuf<unsigned char> d_flac_work;       // per frame: good / dropped flags and output offsets; per stream: results
+    PinnedBuf<unsigned char> h_flac_stage;   // pinned staging of d_flac_blob, and the results coming back
     int32_t file_track_index = -1;           // Some(idx) of the file-level call in progress (src/replaygain.rs:838-851); -1 = None
     unsigned loader_threads = 0;             // tuning key 7: host threads of the file loaders; 0 = every core this process may use
     // Routing knobs of the file layer.  The environment is read ONCE, at rg_create (rg_capi.hip: read_env_defaults; getenv is

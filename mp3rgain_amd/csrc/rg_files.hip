@@ -38,6 +38,7 @@
 #include "../../include/mp3rgain_amd_mp4.h"
 #include "../../include/mp3rgain_amd_demux.h"
 #include "rg_ctx.h"
+#include "rg_flac.h"
 #include "rg_mp3dev.h"
 #include "rg_mp3dev_host.h"
 #include "rg_mp3_frame.h"
@@ -231,9 +232,16 @@ struct LoadedAudio {
     uint64_t arena_off = 0;
     uint64_t walked_frames = 0;  // PCM frames if every walked frame decodes: what the arena is laid out for
     uint32_t result_index = 0;
+    // a native FLAC stream (file_bytes): its frame index for the device route (tuning key 14 = 1), or the host decoder's PCM
+    // already in the arena's format (key 14 = 0); `frames` is then the decoded length, else what the index walked
+    bool flac = false;
+    std::vector<rg_flac_frame> flac_frames;
+    std::vector<uint8_t> flac_pcm;
+    uint32_t flac_bps = 0;
     // ready for the next file; the vectors keep their capacity
     void reset() {
         wav.clear(); planar.clear(); is.clear(); units.clear(); main_stream.clear(); recs.clear(); file_bytes.clear();
+        flac_frames.clear(); flac_pcm.clear(); flac = false; flac_bps = 0;
         sample_rate = channels = 0; frames = 0; n_units = 0; lsf = 0;
         decoded = split = is_mp4 = staged = false;
         arena_off = 0; walked_frames = 0; result_index = 0; n_audio_tracks = 1;
@@ -254,6 +262,66 @@ std::vector<LoadedAudio> &file_pool(rg_ctx *c, size_t n) {
 
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
+
+// The arena format of FLAC PCM, the WAV route's convention: up to 16 bits S16 planar (<< 16 - bps), 17-24 bits S32 planar
+// (<< 32 - bps).  Both are exact powers of two, so the analysis sees the same normalised samples either way.
+uint32_t flac_elem_bytes(uint32_t bps) { return bps <= 16 ? 2u : 4u; }
+uint32_t flac_shift(uint32_t bps) { return bps <= 16 ? 16u - bps : 32u - bps; }
+uint16_t flac_format(uint32_t bps) { return bps <= 16 ? RG_FMT_S16_PLANAR : RG_FMT_S32_PLANAR; }
+
+constexpr int kFlacNotHere = 1;  // load_flac: a FLAC stream this library does not decode (the decoder command's to try)
+
+// A native FLAC stream in `out->file_bytes`: the frame walk, and with route 0 the host decoder's PCM in the arena's format.
+int load_flac(int route, const char *path, LoadedAudio *out, std::string *err) {
+    rg_flac_info si;
+    const int rc = rg_flac_index_vec(out->file_bytes.data(), out->file_bytes.size(), &out->flac_frames, &si);
+    if (rc == RG_FLAC_ERR_UNSUPPORTED) {
+        *err = std::string("Failed to create decoder: ") + path + " (FLAC of " + std::to_string(si.bits_per_sample) +
+               " bits per sample; this library decodes 4-24: set a decoder command, rg_set_decoder_command)";
+        return kFlacNotHere;
+    }
+    if (rc != RG_FLAC_OK) {
+        *err = std::string("Failed to probe format: ") + path + " (" + rg_flac_last_error() + ")";
+        return RG_ERR_FORMAT;
+    }
+    out->flac = true;
+    out->sample_rate = si.sample_rate;
+    out->channels = si.channels;
+    out->flac_bps = si.bits_per_sample;
+    out->frames = si.frames;
+    if (route != 0) return RG_OK;
+    // the host decoder
+    std::vector<int32_t> pcm((size_t)si.frames * si.channels + 1);
+    int32_t *planes[8];
+    for (uint32_t ch = 0; ch < si.channels; ++ch) planes[ch] = pcm.data() + (size_t)ch * si.frames;
+    rg_flac_info di;
+    if (rg_flac_decode_vec(out->file_bytes.data(), out->file_bytes.size(), out->flac_frames, si, planes, si.frames, &di, nullptr) != RG_FLAC_OK) {
+        *err = std::string("Failed to decode: ") + path;
+        return RG_ERR_FORMAT;
+    }
+    const uint32_t eb = flac_elem_bytes(si.bits_per_sample), sh = flac_shift(si.bits_per_sample);
+    out->frames = di.frames;
+    out->flac_pcm.resize((size_t)di.frames * si.channels * eb);
+    for (uint32_t ch = 0; ch < si.channels; ++ch) {
+        const int32_t *src = planes[ch];
+        if (eb == 2) {
+            int16_t *dst = reinterpret_cast<int16_t *>(out->flac_pcm.data()) + (size_t)ch * di.frames;
+            for (uint64_t i = 0; i < di.frames; ++i) dst[i] = (int16_t)((uint32_t)src[i] << sh);
+        } else {
+            int32_t *dst = reinterpret_cast<int32_t *>(out->flac_pcm.data()) + (size_t)ch * di.frames;
+            for (uint64_t i = 0; i < di.frames; ++i) dst[i] = (int32_t)((uint32_t)src[i] << sh);
+        }
+    }
+    out->flac_frames.clear();
+    return RG_OK;
+}
+
+// FLAC in an Ogg container ("OggS" page whose first packet starts 0x7F "FLAC"): not decoded here
+bool is_ogg_flac(const uint8_t *d, size_t len) {
+    if (len < 27 || memcmp(d, "OggS", 4) != 0) return false;
+    const size_t body = 27 + (size_t)d[26];
+    return len >= body + 5 && d[body] == 0x7F && memcmp(d + body + 1, "FLAC", 4) == 0;
+}
 
 // Grow the arena to `need` bytes without losing its first `keep` bytes (PCM that chunks decoded earlier in the call).
 // The device is idle when this returns from a growth.
@@ -342,6 +410,14 @@ int stage_loaded(rg_ctx *c, const std::vector<LoadedAudio> &in, size_t n, std::v
             continue;
         }
         d.offset_bytes = dst_total;
+        if (in[i].flac) {  // laid out for every walked frame (device route) or the host decoder's length; frames fixed below
+            d.frames = in[i].frames;
+            d.sample_rate = in[i].sample_rate;
+            d.channels = (uint16_t)in[i].channels;
+            d.format = flac_format(in[i].flac_bps);
+            dst_total = align16(dst_total + (size_t)in[i].frames * in[i].channels * flac_elem_bytes(in[i].flac_bps));
+            continue;
+        }
         if (in[i].decoded || in[i].split) {
             d.frames = in[i].frames;
             d.sample_rate = in[i].sample_rate;
@@ -375,9 +451,31 @@ int stage_loaded(rg_ctx *c, const std::vector<LoadedAudio> &in, size_t n, std::v
     if (rc != RG_OK) return rc;
     hipStream_t fs = c->user_attached ? c->user_stream : c->slot().stream;
     std::vector<RgMp3SplitItem> split;
+    std::vector<RgFlacDevStream> flac;
+    std::vector<size_t> flac_of;
     for (size_t i = 0; i < n; ++i) {
         unsigned char *dst = c->d_arena.p + (*descs)[i].offset_bytes;
         if (in[i].staged) continue;
+        if (in[i].flac) {
+            if (in[i].flac_frames.empty()) {  // the host decoder's PCM (or an empty stream)
+                if (!in[i].flac_pcm.empty()) RG_HIP(c, hipMemcpyAsync(dst, in[i].flac_pcm.data(), in[i].flac_pcm.size(), hipMemcpyHostToDevice, fs));
+                if (in[i].flac_pcm.empty()) (*descs)[i].frames = 0;
+                continue;
+            }
+            RgFlacDevStream st{};
+            st.bytes = in[i].file_bytes.data();
+            st.len = in[i].file_bytes.size();
+            st.frames = in[i].flac_frames.data();
+            st.n_frames = (uint32_t)in[i].flac_frames.size();
+            st.channels = in[i].channels;
+            st.bps = in[i].flac_bps;
+            st.elem_bytes = flac_elem_bytes(in[i].flac_bps);
+            st.shift = flac_shift(in[i].flac_bps);
+            st.dst = dst;
+            flac.push_back(st);
+            flac_of.push_back(i);
+            continue;
+        }
         if (in[i].split) {
             RgMp3SplitItem it{};
             it.is = in[i].is.data();
@@ -409,6 +507,11 @@ int stage_loaded(rg_ctx *c, const std::vector<LoadedAudio> &in, size_t n, std::v
     if (!split.empty()) {  // the device half of the MP3 decoder writes PCM straight into the arena
         rc = rg_mp3dev_decode(c, split.data(), split.size(), fs);
         if (rc != RG_OK) return rc;
+    }
+    if (!flac.empty()) {  // the device FLAC decoder writes PCM straight into the arena; the decoded lengths come back
+        rc = rg_flacdev_decode(c, flac.data(), flac.size(), fs);
+        if (rc != RG_OK) return rc;
+        for (size_t k = 0; k < flac.size(); ++k) (*descs)[flac_of[k]].frames = flac[k].samples;
     }
     // the host buffers are the caller's locals: the copies must have left them before this returns
     RG_HIP(c, hipStreamSynchronize(fs));
@@ -463,12 +566,15 @@ std::string shell_quote(const char *s) {
 
 // Load one file (no device work; safe to call from several threads at once as long as `err` is per call).
 // RIFF/WAVE: the bytes; MPEG Layer III: decoded planar f32; anything else: the decoder command's stdout.
-int load_audio_for_impl(const std::string &decoder_cmd, int gpu_decode, const char *path, LoadedAudio *out, std::string *err, int32_t track_index);
+// A native FLAC stream (also behind an ID3v2 tag): its frame index, or PCM from the host decoder (flac_route = tuning key 14).
+int load_audio_for_impl(const std::string &decoder_cmd, int gpu_decode, const char *path, LoadedAudio *out, std::string *err, int32_t track_index,
+                        int flac_route);
 // The loaders run on host threads of the library's own: an allocation failure there must come back as a status, not end
 // the process in std::terminate.
-int load_audio_for(const std::string &decoder_cmd, int gpu_decode, const char *path, LoadedAudio *out, std::string *err, int32_t track_index) {
+int load_audio_for(const std::string &decoder_cmd, int gpu_decode, const char *path, LoadedAudio *out, std::string *err, int32_t track_index,
+                   int flac_route) {
     try {
-        return load_audio_for_impl(decoder_cmd, gpu_decode, path, out, err, track_index);
+        return load_audio_for_impl(decoder_cmd, gpu_decode, path, out, err, track_index, flac_route);
     } catch (const std::bad_alloc &) {
         *err = std::string("Out of memory while loading: ") + (path ? path : "");
         return RG_ERR_NOMEM;
@@ -477,7 +583,8 @@ int load_audio_for(const std::string &decoder_cmd, int gpu_decode, const char *p
         return RG_ERR_FORMAT;
     }
 }
-int load_audio_for_impl(const std::string &decoder_cmd, int gpu_decode, const char *path, LoadedAudio *out, std::string *err, int32_t track_index) {
+int load_audio_for_impl(const std::string &decoder_cmd, int gpu_decode, const char *path, LoadedAudio *out, std::string *err, int32_t track_index,
+                        int flac_route) {
     char msg[1024];
     auto fail = [&](int code, const char *fmt, const char *a, int b = 0) {
         snprintf(msg, sizeof msg, fmt, a, b);
@@ -496,7 +603,20 @@ int load_audio_for_impl(const std::string &decoder_cmd, int gpu_decode, const ch
         out->wav.swap(bytes);
         return RG_OK;
     }
-    const bool mp4 = bytes.size() >= 8 && memcmp(bytes.data() + 4, "ftyp", 4) == 0;
+    // FLAC before the MPEG probe: a FLAC payload can hold byte runs the Layer III scanner would take for frames
+    bool to_command = false;
+    if (rg_flac_is_flac(bytes.data(), bytes.size())) {
+        const int rc = load_flac(flac_route, path, out, err);
+        if (rc != kFlacNotHere) return rc;
+        out->flac = false;
+        if (decoder_cmd.empty()) return RG_ERR_FORMAT;
+        to_command = true;
+    } else if (is_ogg_flac(bytes.data(), bytes.size())) {
+        if (decoder_cmd.empty())
+            return fail(RG_ERR_FORMAT, "Failed to create decoder: %s (FLAC in Ogg is not decoded by this library: set a decoder command, rg_set_decoder_command)", path);
+        to_command = true;
+    }
+    const bool mp4 = !to_command && bytes.size() >= 8 && memcmp(bytes.data() + 4, "ftyp", 4) == 0;
     out->is_mp4 = rg_mp4_is_mp4_data(bytes.data(), bytes.size()) != 0;  // detect_file_type, src/replaygain.rs:777-783
     int mp4_track = 0;
     bool mp4_mpeg_audio = false;  // the selected track of an MP4 file is MPEG audio: `bytes` now holds its elementary stream
@@ -542,7 +662,7 @@ int load_audio_for_impl(const std::string &decoder_cmd, int gpu_decode, const ch
             }
         }
     }
-    if (!mp4 || mp4_mpeg_audio) {
+    if (!to_command && (!mp4 || mp4_mpeg_audio)) {
         // the probe (src/replaygain.rs:815-822) and the packet loop (:881-904) for an MPEG audio stream
         rg_mp3_stream_info si;
         if (rg_mp3_scan(bytes.data(), bytes.size(), &si) == RG_MP3DEC_OK && si.audio_frames > 0) {
@@ -761,7 +881,7 @@ int file_outcome(const LoadedAudio &la, int load_rc, const std::string &load_err
         return RG_ERR_INVALID_ARG;
     }
     uint32_t rate = la.sample_rate;
-    if (!la.decoded && !la.split && !la.staged) {
+    if (!la.decoded && !la.split && !la.staged && !la.flac) {
         rg_wav_info wi;
         rate = rg_wav_parse(la.wav.data(), la.wav.size(), &wi) == RG_OK ? wi.sample_rate : 0;
         if (rate == 0) {
@@ -828,6 +948,7 @@ int load_many_pipelined(rg_ctx *c, const char *const *paths, size_t n, std::vect
     std::atomic<uint64_t> t_read{0}, t_compact{0}, t_wait{0}, t_copy{0};  // trace: microseconds summed over the loader threads
     const std::string cmd = c->decoder_cmd;
     const int32_t track_index = c->file_track_index;
+    const int flac_route = c->gpu_flac_decode;
     const int device = c->device;
     std::atomic<size_t> next_file{0};
 
@@ -863,13 +984,24 @@ int load_many_pipelined(rg_ctx *c, const char *const *paths, size_t n, std::vect
             la.wav.assign(sc.p, sc.p + len);
             return;
         }
+        if (rg_flac_is_flac(sc.p, len)) {  // (before the MPEG probe, as in load_audio_for)
+            la.file_bytes.assign(sc.p, sc.p + len);
+            const int frc = load_flac(flac_route, path, &la, &err);
+            if (frc != kFlacNotHere) {
+                (*rcs)[i] = frc;
+                return;
+            }
+            la.flac = false;
+            (*rcs)[i] = cmd.empty() ? RG_ERR_FORMAT : load_audio_for(cmd, 2, path, &la, &err, track_index, flac_route);
+            return;
+        }
         const bool mp4 = len >= 8 && memcmp(sc.p + 4, "ftyp", 4) == 0;
         la.is_mp4 = rg_mp4_is_mp4_data(sc.p, len) != 0;
         rg_mp3_stream_info si;
         uint64_t main_len = 0;
         const double tl1 = trace ? now() : 0.0;
         if (mp4 || rg_mp3_compact_stream(sc.p, len, &sc.slots, &sc.tiles, &main_len, &si) != RG_MP3DEC_OK || si.audio_frames == 0) {
-            (*rcs)[i] = load_audio_for(cmd, 2, path, &la, &err, track_index);  // the decoder command, or the reference's probe error
+            (*rcs)[i] = load_audio_for(cmd, 2, path, &la, &err, track_index, flac_route);  // the decoder command, or the reference's probe error
             return;
         }
         la.sample_rate = si.sample_rate;
@@ -1207,8 +1339,10 @@ int load_many(rg_ctx *c, const char *const *paths, size_t n, std::vector<LoadedA
         const std::string cmd = c->decoder_cmd;
         const int32_t track_index = c->file_track_index;
         const int gpu_decode = c->gpu_mp3_decode;
+        const int flac_route = c->gpu_flac_decode;
         auto work = [&]() {
-            for (size_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) rcs[i] = load_audio_for(cmd, gpu_decode, paths[i], &(*out)[i], &errs[i], track_index);  // (*out) holds >= n entries
+            for (size_t i = next.fetch_add(1); i < n; i = next.fetch_add(1))
+                rcs[i] = load_audio_for(cmd, gpu_decode, paths[i], &(*out)[i], &errs[i], track_index, flac_route);  // (*out) holds >= n entries
         };
         if (workers <= 1) {
             work();
@@ -1736,5 +1870,42 @@ extern "C" int rg_mp3_decode_device(rg_ctx *c, const void *data, size_t len, flo
         RG_HIP(c, hipMemcpy(ch0, it.d_ch0, (size_t)out->frames * sizeof(float), hipMemcpyDeviceToHost));
         if (out->channels == 2) RG_HIP(c, hipMemcpy(ch1, it.d_ch1, (size_t)out->frames * sizeof(float), hipMemcpyDeviceToHost));
     }
+    return RG_OK;
+}
+
+// Decode one FLAC stream through the device route's kernels and bring the PCM back, right-justified int32: the parity hook
+// of tests/test_gpu_flac.py.  Same outputs as rg_flac_decode_s32.
+extern "C" int rg_flac_decode_device(void *ctx, const void *data, size_t len, int32_t *const *planes, uint64_t capacity, rg_flac_info *out) {
+    rg_ctx *c = static_cast<rg_ctx *>(ctx);
+    if (!c || !data || !out || !planes) return RG_ERR_INVALID_ARG;
+    std::vector<rg_flac_frame> frames;
+    rg_flac_info si;
+    if (rg_flac_index_vec((const uint8_t *)data, len, &frames, &si) != RG_FLAC_OK) return rg_set_err(c, RG_ERR_FORMAT, "%s", rg_flac_last_error());
+    int rc = rg_bind_device(c);
+    if (rc != RG_OK) return rc;
+    for (int s = 0; s < c->n_slots; ++s) RG_HIP(c, hipStreamSynchronize(c->slots[s].stream));
+    const size_t bytes = (size_t)si.frames * si.channels * sizeof(int32_t);
+    RG_HIP(c, c->d_arena.reserve(bytes ? bytes : 16));
+    RgFlacDevStream st{};
+    st.bytes = (const uint8_t *)data;
+    st.len = len;
+    st.frames = frames.data();
+    st.n_frames = (uint32_t)frames.size();
+    st.channels = si.channels;
+    st.bps = si.bits_per_sample;
+    st.elem_bytes = 4;
+    st.shift = 0;
+    st.dst = c->d_arena.p;
+    hipStream_t fs = c->slots[0].stream;
+    rc = rg_flacdev_decode(c, &st, 1, fs);
+    if (rc != RG_OK) return rc;
+    *out = si;
+    out->frames = st.samples;
+    out->audio_frames = st.decoded_frames;
+    out->dropped_frames = st.dropped_frames;
+    if (st.samples > capacity) return rg_set_err(c, RG_ERR_INVALID_ARG, "capacity %llu < %llu frames", (unsigned long long)capacity, (unsigned long long)st.samples);
+    for (uint32_t ch = 0; ch < si.channels && st.samples; ++ch)
+        RG_HIP(c, hipMemcpy(planes[ch], c->d_arena.p + (size_t)ch * st.samples * sizeof(int32_t), (size_t)st.samples * sizeof(int32_t), hipMemcpyDeviceToHost));
+    c->user_dirty = true;
     return RG_OK;
 }

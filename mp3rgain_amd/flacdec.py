@@ -1,0 +1,125 @@
+"""ctypes binding of include/mp3rgain_amd_flac.h: a native FLAC stream -> planar int32 PCM (host decoder).
+
+Host code, no GPU needed.  Only loads the in-tree shared library -- there is no Python decoder behind it."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Tuple
+
+import numpy as np
+
+from . import _capi
+
+OK, ERR_ARG, ERR_NOT_FLAC, ERR_CAPACITY, ERR_UNSUPPORTED = 0, -1, -2, -3, -4
+
+
+class FlacInfo(C.Structure):
+    _fields_ = [
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("bits_per_sample", C.c_uint32),
+        ("min_block_size", C.c_uint32),
+        ("max_block_size", C.c_uint32),
+        ("id3v2_bytes", C.c_uint32),
+        ("total_samples", C.c_uint64),
+        ("metadata_bytes", C.c_uint64),
+        ("frames", C.c_uint64),
+        ("audio_frames", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class FlacFrame(C.Structure):
+    _fields_ = [
+        ("offset", C.c_uint64),
+        ("first_sample", C.c_uint64),
+        ("length", C.c_uint32),
+        ("block_size", C.c_uint32),
+        ("channel_assignment", C.c_uint8),
+        ("header_length", C.c_uint8),
+        ("reserved", C.c_uint16),
+        ("reserved2", C.c_uint32),
+    ]
+
+
+SYMBOLS = [
+    ("rg_flac_is_flac", C.c_int, [C.c_void_p, C.c_size_t]),
+    ("rg_flac_scan", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(FlacInfo)]),
+    ("rg_flac_index_frames", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(FlacFrame), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(FlacInfo)]),
+    ("rg_flac_decode_s32", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(FlacInfo)]),
+    ("rg_flac_index_selfcheck", C.c_int, [C.c_void_p, C.c_size_t]),
+    ("rg_flac_last_error", C.c_char_p, []),
+    ("rg_flac_decode_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(FlacInfo)]),
+]
+
+
+class FlacError(RuntimeError):
+    def __init__(self, code: int, msg: str):
+        super().__init__(f"{msg} (status {code})")
+        self.code = code
+
+
+def _lib():
+    L = _capi.load()
+    if not getattr(L, "_flac_bound", False):
+        for name, res, args in SYMBOLS:
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        L._flac_bound = True
+    return L
+
+
+def _buf(data: bytes):
+    return (C.c_char * max(1, len(data))).from_buffer_copy(data if data else b"\0")
+
+
+def is_flac(data: bytes) -> bool:
+    return bool(_lib().rg_flac_is_flac(_buf(data), len(data)))
+
+
+def scan(data: bytes) -> FlacInfo:
+    L = _lib()
+    info = FlacInfo()
+    rc = L.rg_flac_scan(_buf(data), len(data), C.byref(info))
+    if rc != OK:
+        raise FlacError(rc, L.rg_flac_last_error().decode())
+    return info
+
+
+def index(data: bytes) -> Tuple[List[FlacFrame], FlacInfo]:
+    """The frame walk the device route uses: ([rg_flac_frame], info)."""
+    L = _lib()
+    info = FlacInfo()
+    n = C.c_size_t()
+    buf = _buf(data)
+    rc = L.rg_flac_index_frames(buf, len(data), None, 0, C.byref(n), C.byref(info))
+    if rc not in (OK, ERR_CAPACITY):
+        raise FlacError(rc, L.rg_flac_last_error().decode())
+    frames = (FlacFrame * max(1, n.value))()
+    rc = L.rg_flac_index_frames(buf, len(data), frames, n.value, C.byref(n), C.byref(info))
+    if rc != OK:
+        raise FlacError(rc, L.rg_flac_last_error().decode())
+    return list(frames[:n.value]), info
+
+
+def decode(data: bytes) -> Tuple[int, int, np.ndarray, FlacInfo]:
+    """-> (sample rate, bits per sample, int32 [channels][samples], info)."""
+    L = _lib()
+    _, info = index(data)
+    cap = int(info.frames)
+    out = np.zeros((int(info.channels), max(1, cap)), dtype=np.int32)
+    planes = (C.c_void_p * int(info.channels))(*[out[c].ctypes.data for c in range(int(info.channels))])
+    di = FlacInfo()
+    rc = L.rg_flac_decode_s32(_buf(data), len(data), planes, cap, C.byref(di))
+    if rc != OK:
+        raise FlacError(rc, L.rg_flac_last_error().decode())
+    return int(di.sample_rate), int(di.bits_per_sample), out[:, :int(di.frames)], di
+
+
+def selfcheck(data: bytes) -> int:
+    """rg_flac_index_selfcheck: 0 = the index and the decoder agree, 1 = they do not, < 0 = not decodable."""
+    return int(_lib().rg_flac_index_selfcheck(_buf(data), len(data)))

@@ -328,6 +328,20 @@ class Analyzer:
                                                    out[1].ctypes.data if info.channels == 2 else None, cap, C.byref(di)))
         return out[:, :int(di.frames)], di
 
+    def decode_flac_device(self, data: bytes):
+        """A FLAC stream through the device decoder (frame check, layout, decode kernels) -> (int32 [channels][samples],
+        FlacInfo); bit for bit what flacdec.decode returns."""
+        from . import flacdec
+
+        L = flacdec._lib()
+        _, info = flacdec.index(data)
+        cap = int(info.frames)
+        out = np.zeros((int(info.channels), max(1, cap)), dtype=np.int32)
+        planes = (C.c_void_p * int(info.channels))(*[out[c].ctypes.data for c in range(int(info.channels))])
+        di = flacdec.FlacInfo()
+        self._check(L.rg_flac_decode_device(self._ctx, flacdec._buf(data), len(data), planes, cap, C.byref(di)))
+        return out[:, :int(di.frames)], di
+
     def decode_mp3_bench(self, data: bytes, copies: int, reps: int = 5) -> dict:
         """rg_mp3_decode_bench: per-kernel HIP-event times of the device decode chain on `copies` copies of one stream."""
         ms = (C.c_double * 5)()
