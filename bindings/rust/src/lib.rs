@@ -185,6 +185,7 @@ pub mod ffi {
         pub fn rg_tracks_error(ctx: *const RgCtx, i: usize) -> *const c_char;
         pub fn rg_analyze_album(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, track_index: i32, tracks_out: *mut RgTrackResult, album_out: *mut RgAlbumResult) -> c_int;
         pub fn rg_analyze_album_begin(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, track_index: i32, tracks_out: *mut RgTrackResult, failed_index: *mut usize) -> c_int;
+        pub fn rg_analyze_albums(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, album_first: *const usize, n_albums: usize, track_index: i32, tracks_out: *mut RgTrackResult, status_out: *mut i32, albums_out: *mut RgAlbumResult, album_status_out: *mut i32) -> c_int;
         pub fn rg_find_peak_amplitude(ctx: *mut RgCtx, path: *const c_char, out: *mut RgPeakResult) -> c_int;
         pub fn rg_mp3_decode_device(ctx: *mut RgCtx, data: *const c_void, len: usize, ch0: *mut f32, ch1: *mut f32, capacity: u64, info: *mut c_void) -> c_int;
         pub fn rg_mp3_decode_bench(ctx: *mut RgCtx, data: *const c_void, len: usize, copies: u32, reps: u32, ms_out: *mut f64, units_out: *mut u64, compressed_bytes_out: *mut u64, frames_out: *mut u64) -> c_int;
@@ -200,6 +201,7 @@ pub mod ffi {
         pub fn rg_analyze_tracks_node(node: *mut RgNode, paths: *const *const c_char, n: usize, track_index: i32, out: *mut RgTrackResult, status_out: *mut i32) -> c_int;
         pub fn rg_node_tracks_error(node: *const RgNode, i: usize) -> *const c_char;
         pub fn rg_node_last_partition(node: *const RgNode, owner_out: *mut u32, n: usize) -> c_int;
+        pub fn rg_analyze_albums_node(node: *mut RgNode, paths: *const *const c_char, n: usize, album_first: *const usize, n_albums: usize, track_index: i32, tracks_out: *mut RgTrackResult, status_out: *mut i32, albums_out: *mut RgAlbumResult, album_status_out: *mut i32) -> c_int;
         pub fn rg_node_create_backend(backend: *const RgNodeBackend, devices: *const c_int, n: usize) -> *mut RgNode;
     }
 }
@@ -424,6 +426,50 @@ pub mod replaygain {
             album_gain_db: album.album_gain_db,
             album_peak: album.album_peak,
         })
+    }
+
+    /// `analyze_album` for every album of a library in one call (rg_analyze_albums_node): whole albums are dealt to the
+    /// node's GPUs, each album's result or its first failing file's error (`:1055`) comes back in input order.
+    pub fn analyze_albums(albums: &[Vec<&Path>]) -> Vec<Result<AlbumGainResult>> {
+        let files: Vec<&Path> = albums.iter().flat_map(|a| a.iter().copied()).collect();
+        let mut first = vec![0usize];
+        for a in albums {
+            first.push(first.last().unwrap() + a.len());
+        }
+        let all_fail = |e: anyhow::Error| -> Vec<Result<AlbumGainResult>> { albums.iter().map(|_| Err(anyhow!("{}", e))).collect() };
+        let (_owned, ptrs) = match c_paths(&files) {
+            Ok(p) => p,
+            Err(e) => return all_fail(e),
+        };
+        let mut tracks = vec![ffi::RgTrackResult::default(); files.len()];
+        let mut status = vec![0i32; files.len()];
+        let mut out = vec![ffi::RgAlbumResult::default(); albums.len()];
+        let mut album_status = vec![0i32; albums.len()];
+        let n = match node() {
+            Ok(n) => n.lock().unwrap(),
+            Err(e) => return all_fail(e),
+        };
+        let rc = unsafe {
+            ffi::rg_analyze_albums_node(n.raw, ptrs.as_ptr(), ptrs.len(), first.as_ptr(), albums.len(), -1, tracks.as_mut_ptr(),
+                                        status.as_mut_ptr(), out.as_mut_ptr(), album_status.as_mut_ptr())
+        };
+        if rc != ffi::RG_OK {
+            return all_fail(n.error());
+        }
+        (0..albums.len())
+            .map(|a| {
+                if album_status[a] != ffi::RG_OK {
+                    let bad = (first[a]..first[a + 1]).find(|&i| status[i] != ffi::RG_OK).unwrap_or(first[a]);
+                    return Err(anyhow!("{}", unsafe { text(ffi::rg_node_tracks_error(n.raw, bad)) }));
+                }
+                Ok(AlbumGainResult {
+                    tracks: tracks[first[a]..first[a + 1]].iter().map(to_result).collect(),
+                    album_loudness_db: out[a].album_loudness_db,
+                    album_gain_db: out[a].album_gain_db,
+                    album_peak: out[a].album_peak,
+                })
+            })
+            .collect()
     }
 
     /// src/replaygain.rs:1140-1249

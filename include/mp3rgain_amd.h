@@ -322,6 +322,24 @@ const char *rg_tracks_error(const rg_ctx *ctx, size_t i);
  * whose PCM does not fit the device at once is analysed in parts whose histograms and peaks are folded: same result. */
 int rg_analyze_album(rg_ctx *ctx, const char *const *paths, size_t n, int32_t track_index,
                      rg_track_result *tracks_out, rg_album_result *album_out);
+/* Many albums in one call.  Album a is files [album_first[a], album_first[a+1]) of `paths`; album_first has n_albums + 1
+ * entries, album_first[0] = 0, album_first[n_albums] = n, non-decreasing (else RG_ERR_INVALID_ARG; NULL only when
+ * n_albums = n = 0).  Per file: tracks_out[i], status_out[i] (RG_OK or the file's code, text by rg_tracks_error(ctx, i)),
+ * as rg_analyze_tracks gives them, except that a file the analysis cannot lay out (a RIFF/WAVE stream of a sample format it
+ * does not read: 64-bit float, A-law, mu-law) fails alone, RG_ERR_FORMAT "Failed to probe format: <path>" as in
+ * rg_analyze_album.  A file's result is valid whenever its status is RG_OK, even when its album failed.  Per album:
+ * albums_out[a] and album_status_out[a] = RG_OK, or the code of the album's first failing file in input order
+ * (analyze_album_with_index's abort rule, src/replaygain.rs:1055, per album; albums_out[a] is then zero).  A failing file or
+ * album does not stop the others.  Album a's results are bit for bit those of rg_analyze_album(ctx, paths + album_first[a],
+ * album_first[a+1] - album_first[a], track_index, ...), and so is its error (one exception: rg_analyze_album looks at how
+ * every file loaded before it lays any out, so when a file that cannot be laid out comes before another failing file it
+ * reports the later one; here input order holds); an empty album gets what rg_analyze_album gives for n = 0.  The files are loaded, decoded and analysed as rg_analyze_tracks takes them --
+ * groups, loader pipeline, parts -- with every batch's track histograms folded into per-album packs on the device.  The
+ * return value is RG_OK when the call itself worked, even if some albums failed; when the call fails (a device error),
+ * every file and album it had not finished carries its code, and rg_last_error its text. */
+int rg_analyze_albums(rg_ctx *ctx, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                      int32_t track_index, rg_track_result *tracks_out, int32_t *status_out,
+                      rg_album_result *albums_out, int32_t *album_status_out);
 /* The same up to, not including, the album percentile: per-file results are out, the album's [histogram | peak] pack of
  * THESE files is ready on the device.  rg_album_finish completes it; when other GPUs hold the rest of the album,
  * rg_album_exchange (or a host fold of the packs) comes first -- mp3rgain_amd_node.h does exactly that over all GPUs of a

@@ -60,6 +60,14 @@ int rg_analyze_album_node(rg_node *node, const char *const *paths, size_t n, int
 int rg_analyze_tracks_node(rg_node *node, const char *const *paths, size_t n, int32_t track_index,
                            rg_track_result *out, int32_t *status_out);
 const char *rg_node_tracks_error(const rg_node *node, size_t i);
+/* rg_analyze_albums over all devices: whole albums are dealt out by their files' bytes (rg_node_partition), every device
+ * makes one rg_analyze_albums call over its albums, the results go back to input order; no exchange.  Per-file texts:
+ * rg_node_tracks_error; rg_node_last_partition: per file, every file of an album on the same device.  On a caller-supplied
+ * backend each album is one album_begin + album_pack, finished on the host; when album_begin fails, every file of that
+ * album carries the album's code and text. */
+int rg_analyze_albums_node(rg_node *node, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                           int32_t track_index, rg_track_result *tracks_out, int32_t *status_out,
+                           rg_album_result *albums_out, int32_t *album_status_out);
 /* how the last call dealt the files out: owner_out[i] = index of the device that had file i (n = that call's n) */
 int rg_node_last_partition(const rg_node *node, uint32_t *owner_out, size_t n);
 

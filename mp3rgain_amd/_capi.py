@@ -144,6 +144,7 @@ SYMBOLS = [
     ("rg_mp3_decode_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("rg_mp3_decode_bench", _int, [_vp, _vp, _sz, _u32, _u32, _P(_dbl), _P(_u64), _P(_u64), _P(_u64)]),
     ("rg_analyze_album_begin", _int, [_vp, _P(C.c_char_p), _sz, _i32, _P(TrackResult), _P(_sz)]),
+    ("rg_analyze_albums", _int, [_vp, _P(C.c_char_p), _sz, _P(_sz), _sz, _i32, _P(TrackResult), _P(_i32), _P(AlbumResult), _P(_i32)]),
     # include/mp3rgain_amd_node.h
     ("rg_node_create", _vp, [_P(_int), _sz]),
     ("rg_node_create_backend", _vp, [_vp, _P(_int), _sz]),
@@ -157,6 +158,7 @@ SYMBOLS = [
     ("rg_analyze_tracks_node", _int, [_vp, _P(C.c_char_p), _sz, _i32, _P(TrackResult), _P(_i32)]),
     ("rg_node_tracks_error", C.c_char_p, [_vp, _sz]),
     ("rg_node_last_partition", _int, [_vp, _P(_u32), _sz]),
+    ("rg_analyze_albums_node", _int, [_vp, _P(C.c_char_p), _sz, _P(_sz), _sz, _i32, _P(TrackResult), _P(_i32), _P(AlbumResult), _P(_i32)]),
 ]
 
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions

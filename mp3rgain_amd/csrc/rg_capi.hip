@@ -347,6 +347,11 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_ingest[0].release();
     c->d_ingest[1].release();
     c->d_album_packs.release();
+    c->d_albums_packs.release();
+    c->d_albums_map.release();
+    c->h_albums_map.release();
+    c->d_albums_res.release();
+    c->h_albums_res.release();
     if (c->ingest_stream) {
         (void)hipStreamDestroy(c->ingest_stream);
         for (int k = 0; k < 2; ++k) {

@@ -211,6 +211,13 @@ struct rg_ctx {
     DevBuf<unsigned char> d_arena;           // staging for host PCM (synchronous API)
     DevBuf<unsigned char> d_ingest[2];       // streamed host ingest: two sub-batch arenas, one filling while the other is analysed
     DevBuf<uint32_t> d_album_packs;          // streamed album: one [histogram | peak] pack per sub-batch, folded at the end
+    // rg_analyze_albums (rg_files.hip, rg_albums.hip): [carried pack | one live pack per album of the group], the per-batch
+    // track -> pack maps of a group (pinned, then copied), the finished albums' results
+    DevBuf<uint32_t> d_albums_packs;
+    DevBuf<int32_t> d_albums_map;
+    PinnedBuf<int32_t> h_albums_map;
+    DevBuf<rg_album_result> d_albums_res;
+    PinnedBuf<rg_album_result> h_albums_res;
     hipStream_t ingest_stream = nullptr;     // H2D copies of the streamed ingest
     hipEvent_t ingest_copied[2] = {nullptr, nullptr}, ingest_free[2] = {nullptr, nullptr};
     uint64_t tune_ingest_chunk_kib = 0;      // 0 = default (2 GiB)
@@ -251,6 +258,8 @@ int rg_comm_adopt(rg_ctx *c, void *comm, int world);
 int rg_comm_init_all(rg_ctx **ctxs, size_t n);
 unsigned rg_usable_cores();  // rg_files.hip: the affinity mask cut by the cgroup CPU quota
 int rg_validate_batch(rg_ctx *c, const rg_track_desc *tracks, size_t n, size_t pcm_bytes);  // argument checks of an enqueue
+// rg_analyze_albums' album_first: RG_OK, or RG_ERR_INVALID_ARG with the reason in *msg (rg_files.hip; the node checks the same)
+int rg_albums_check(const size_t *album_first, size_t n_albums, size_t n, std::string *msg);
 
 #define RG_HIP(ctx, call)                                                                          \
     do {                                                                                           \

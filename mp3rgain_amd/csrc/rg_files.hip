@@ -37,6 +37,7 @@
 #include "../../include/mp3rgain_amd_dec.h"
 #include "../../include/mp3rgain_amd_mp4.h"
 #include "../../include/mp3rgain_amd_demux.h"
+#include "rg_albums.h"
 #include "rg_ctx.h"
 #include "rg_flac.h"
 #include "rg_mp3dev.h"
@@ -776,8 +777,47 @@ struct Mp3Pipe {
 // an MPEG stream or failed, an unsupported rate, a track the fast kernels flag -- drops the parts and the album is analysed the
 // plain way from the PCM, which is in the arena either way.
 constexpr size_t kMaxParts = 64;
+// rg_analyze_albums: the live pack (rg_albums.h) the track of each file of a group is folded into.  The track -> pack maps of
+// the group's batches go to pinned memory one after the other (nothing there is rewritten before the group's end, when
+// everything has been waited for) and are copied to the device on the batch's stream, in front of the fold.
+struct AlbumFold {
+    std::vector<int32_t> pack_of;  // per file of the group (the numbering of load_many)
+    std::vector<size_t> album_of_pack;  // the albums that have files in the group, in input order: one live pack each
+    uint32_t *d_packs = nullptr;   // live pack 0; the carried pack sits one stride in front
+    size_t n_packs = 0;
+    bool carried = false;          // pack 0 is an album that had files in earlier groups: it starts from the carried pack
+    size_t map_used = 0;
+};
+// the live packs as they were when the group began (zero, or the carried pack): at the group's start, and again when the
+// plain route follows parts that were folded already
+int fold_init(rg_ctx *c, AlbumFold *f) {
+    for (int k = 0; k < RG_SLOT_STREAMS; ++k) RG_HIP(c, hipStreamSynchronize(c->slots[k].stream));
+    hipStream_t s = c->slots[0].stream;
+    RG_HIP(c, hipMemsetAsync(f->d_packs, 0, f->n_packs * (size_t)RG_ALBUMS_PACK_STRIDE * sizeof(uint32_t), s));
+    if (f->carried)
+        RG_HIP(c, hipMemcpyAsync(f->d_packs, f->d_packs - RG_ALBUMS_PACK_STRIDE, (size_t)RG_ALBUMS_PACK_STRIDE * sizeof(uint32_t),
+                                 hipMemcpyDeviceToDevice, s));
+    RG_HIP(c, hipStreamSynchronize(s));
+    return RG_OK;
+}
+// the batch just enqueued (the context's current slot holds its final track histograms and peaks: after the exact repeat),
+// `files` its tracks' files in batch order: fold them into their albums' packs on the batch's stream `s`
+int fold_batch(rg_ctx *c, AlbumFold *f, const size_t *files, size_t k, hipStream_t s) {
+    if (k == 0) return RG_OK;
+    if (f->map_used + k > c->h_albums_map.cap || f->map_used + k > c->d_albums_map.cap)
+        return rg_set_err(c, RG_ERR_STATE, "rg_analyze_albums: more folded tracks than the group has files");
+    int32_t *h = c->h_albums_map.p + f->map_used;
+    for (size_t j = 0; j < k; ++j) h[j] = f->pack_of[files[j]];
+    int32_t *d = c->d_albums_map.p + f->map_used;
+    RG_HIP(c, hipMemcpyAsync(d, h, k * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    RgSlot &S = c->slot();
+    RG_HIP(c, rg_launch_album_fold(S.d_hist.p, S.peak_ptr, d, (uint32_t)k, f->d_packs, s));
+    f->map_used += k;
+    return RG_OK;
+}
 struct PartsRun {
     int album = 1;  // 0: track mode (rg_analyze_tracks) -- the same parts without the packs
+    AlbumFold *fold = nullptr;  // track mode of rg_analyze_albums: every part is folded into its albums' packs
     bool broken = false;
     size_t n_parts = 0;
     std::vector<size_t> file_of;  // position in c->h_part_results -> file of the call
@@ -897,6 +937,15 @@ int file_outcome(const LoadedAudio &la, int load_rc, const std::string &load_err
         return RG_ERR_UNSUPPORTED_RATE;
     }
     return RG_OK;
+}
+
+// Whether stage_loaded can lay out a file that file_outcome passed: a RIFF/WAVE stream of a sample format the de-interleave
+// does not read (64-bit float, A-law, mu-law, ...) parses, but fails the whole batch there ("input k: unsupported WAV sample
+// format"); rg_analyze_album reports such a file as "Failed to probe format: <path>".
+bool stageable(const LoadedAudio &la) {
+    if (la.decoded || la.split || la.staged || la.flac) return true;
+    rg_wav_info wi;
+    return rg_wav_parse(la.wav.data(), la.wav.size(), &wi) == RG_OK && wav_kind(wi) >= 0;
 }
 
 int load_many_pipelined(rg_ctx *c, const char *const *paths, size_t n, std::vector<LoadedAudio> *out, std::vector<int> *rcs,
@@ -1226,6 +1275,10 @@ int load_many_pipelined(rg_ctx *c, const char *const *paths, size_t n, std::vect
                                      (size_t)RG_ALBUM_PACK_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, fs));
         RG_HIP(c, hipMemcpyAsync(c->h_part_results.p + parts->file_of.size(), S.d_results.p, descs.size() * sizeof(rg_track_result),
                                  hipMemcpyDeviceToHost, fs));
+        if (parts->fold) {  // (before the slot's accumulators serve a later part: same stream)
+            const int fr = fold_batch(c, parts->fold, files.data(), files.size(), fs);
+            if (fr != RG_OK) return fr;
+        }
         parts->n_parts++;
         parts->file_of.insert(parts->file_of.end(), files.begin(), files.end());
         return RG_OK;
@@ -1531,8 +1584,9 @@ extern "C" int rg_analyze_album(rg_ctx *c, const char *const *paths, size_t n, i
 }
 
 // one group of rg_analyze_tracks: files [first, first + n) of the call; file_errors is indexed by the call's numbering
+// (fold: rg_analyze_albums -- every batch's tracks are folded into their albums' packs as well)
 static int analyze_tracks_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, int32_t track_index, rg_track_result *out,
-                                int32_t *status_out) {
+                                int32_t *status_out, AlbumFold *fold = nullptr) {
     paths += first;
     out += first;
     status_out += first;
@@ -1542,6 +1596,7 @@ static int analyze_tracks_group(rg_ctx *c, const char *const *paths, size_t firs
     // parts (PartsRun), track mode: every file of the group has to come through the loader pipeline for them to count
     PartsRun parts;
     parts.album = 0;
+    parts.fold = fold;
     const bool use_parts = c->parts_on() && c->n_slots >= 3 && n > 0 && c->gpu_mp3_decode >= 3 && !c->user_attached;
     if (use_parts)
         for (int k = 0; k < RG_SLOT_STREAMS; ++k) RG_HIP(c, hipStreamSynchronize(c->slots[k].stream));
@@ -1564,6 +1619,10 @@ static int analyze_tracks_group(rg_ctx *c, const char *const *paths, size_t firs
             return RG_OK;
         }
     }
+    if (fold && parts.n_parts) {  // parts were folded already: the plain route below starts the packs over
+        rc = fold_init(c, fold);
+        if (rc != RG_OK) return rc;
+    }
     // the batch holds the files that loaded and whose rate the analysis knows; `slot` maps them back
     std::vector<size_t> slot;
     for (size_t i = 0; i < n; ++i) {
@@ -1576,6 +1635,11 @@ static int analyze_tracks_group(rg_ctx *c, const char *const *paths, size_t firs
         if (frc != RG_OK) {
             status_out[i] = frc;
             c->file_errors[first + i] = msg;
+            continue;
+        }
+        if (fold && !stageable(in[i])) {  // rg_analyze_albums: this file fails alone instead of failing every file of the batch
+            status_out[i] = RG_ERR_FORMAT;
+            c->file_errors[first + i] = std::string("Failed to probe format: ") + paths[i];
             continue;
         }
         slot.push_back(i);
@@ -1595,6 +1659,10 @@ static int analyze_tracks_group(rg_ctx *c, const char *const *paths, size_t firs
                 out[slot[k]] = res[k];
                 out[slot[k]].file_type = in[k].is_mp4 ? RG_FILE_AAC : RG_FILE_MP3;
             }
+        if (rc == RG_OK && fold) {
+            const int fr = fold_batch(c, fold, slot.data(), slot.size(), c->slot().stream);
+            if (fr != RG_OK) return fr;
+        }
     }
     if (rc != RG_OK) {  // a failure of the batch itself (a WAV of a kind the library cannot stage, a device error): every file in it carries it
         for (size_t k = 0; k < slot.size(); ++k) {
@@ -1626,6 +1694,152 @@ extern "C" int rg_analyze_tracks(rg_ctx *c, const char *const *paths, size_t n, 
 extern "C" const char *rg_tracks_error(const rg_ctx *c, size_t i) {
     if (!c || i >= c->file_errors.size()) return "";
     return c->file_errors[i].c_str();
+}
+
+int rg_albums_check(const size_t *album_first, size_t n_albums, size_t n, std::string *msg) {
+    char m[160];
+    if (!album_first) {
+        if (n_albums == 0 && n == 0) return RG_OK;
+        *msg = "album_first is NULL";
+        return RG_ERR_INVALID_ARG;
+    }
+    if (album_first[0] != 0) {
+        snprintf(m, sizeof m, "album_first[0] is %zu, not 0", album_first[0]);
+        *msg = m;
+        return RG_ERR_INVALID_ARG;
+    }
+    if (album_first[n_albums] != n) {
+        snprintf(m, sizeof m, "album_first[%zu] is %zu, not the number of files (%zu)", n_albums, album_first[n_albums], n);
+        *msg = m;
+        return RG_ERR_INVALID_ARG;
+    }
+    for (size_t a = 0; a < n_albums; ++a)
+        if (album_first[a + 1] < album_first[a]) {
+            snprintf(m, sizeof m, "album_first decreases from entry %zu to entry %zu", a, a + 1);
+            *msg = m;
+            return RG_ERR_INVALID_ARG;
+        }
+    return RG_OK;
+}
+
+// Many albums in one call: rg_analyze_tracks' groups, loader pipeline and parts over the whole list, so that the pipeline
+// stays full across album boundaries, with every batch's track histograms and peaks folded into their albums' live packs on
+// the device (rg_albums.hip).  Only albums with files in the current group have a live pack.  An album is finished when the
+// group that holds its last file is: its pack is read out with the others finished there (one launch, one copy back per
+// group).  An album that goes on into the next group is carried in the pack in front of the live ones.  Per album the first
+// failing file in input order decides (src/replaygain.rs:1055).  *files_done: the files whose outcome is final (the groups
+// before the one in progress); done[a]: album a's record is final.
+static int analyze_albums_impl(rg_ctx *c, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                               int32_t track_index, rg_track_result *tracks_out, int32_t *status_out, rg_album_result *albums_out,
+                               int32_t *album_status_out, std::vector<char> &done, size_t *files_done) {
+    std::vector<size_t> album_of(n);
+    for (size_t a = 0; a < n_albums; ++a)
+        for (size_t i = album_first[a]; i < album_first[a + 1]; ++i) album_of[i] = a;
+    std::vector<std::pair<size_t, size_t>> groups;
+    file_groups(c, paths, n, &groups);
+    // live packs: the albums that have files in one group (never more than its files), plus the carried pack in front of them
+    size_t max_packs = 1, max_files = 1;
+    for (const auto &g : groups) {
+        size_t albums = 0;
+        for (size_t i = g.first; i < g.first + g.second; ++i) albums += (i == g.first || album_of[i] != album_of[i - 1]) ? 1 : 0;
+        max_packs = std::max(max_packs, albums);
+        max_files = std::max(max_files, g.second);
+    }
+    RG_HIP(c, c->d_albums_packs.reserve((max_packs + 1) * (size_t)RG_ALBUMS_PACK_STRIDE));
+    RG_HIP(c, c->d_albums_map.reserve(2 * max_files));  // a group's parts, and the plain route after them
+    RG_HIP(c, c->h_albums_map.reserve(2 * max_files));
+    RG_HIP(c, c->d_albums_res.reserve(max_packs));
+    RG_HIP(c, c->h_albums_res.reserve(max_packs));
+    uint32_t *const carry = c->d_albums_packs.p;
+    hipStream_t s = c->slots[0].stream;
+    auto album_status = [&](size_t a) -> int32_t {
+        for (size_t i = album_first[a]; i < album_first[a + 1]; ++i)
+            if (status_out[i] != RG_OK) return status_out[i];
+        return RG_OK;
+    };
+    for (const auto &g : groups) {
+        const size_t first = g.first, cnt = g.second;  // (a group holds at least one file)
+        AlbumFold fold;
+        fold.d_packs = carry + RG_ALBUMS_PACK_STRIDE;
+        fold.pack_of.resize(cnt);
+        for (size_t i = 0; i < cnt; ++i) {
+            const size_t a = album_of[first + i];
+            if (fold.album_of_pack.empty() || fold.album_of_pack.back() != a) fold.album_of_pack.push_back(a);
+            fold.pack_of[i] = (int32_t)(fold.album_of_pack.size() - 1);
+        }
+        fold.n_packs = fold.album_of_pack.size();
+        const size_t a_first = fold.album_of_pack.front(), a_last = fold.album_of_pack.back();
+        fold.carried = album_first[a_first] < first;
+        int rc = fold_init(c, &fold);
+        if (rc != RG_OK) return rc;
+        rc = analyze_tracks_group(c, paths, first, cnt, track_index, tracks_out, status_out, &fold);
+        if (rc != RG_OK) return rc;
+        const bool continues = album_first[a_last + 1] > first + cnt;
+        const size_t n_fin = fold.n_packs - (continues ? 1 : 0);
+        for (int k = 0; k < RG_SLOT_STREAMS; ++k) RG_HIP(c, hipStreamSynchronize(c->slots[k].stream));
+        if (n_fin) {
+            RG_HIP(c, rg_launch_album_results(fold.d_packs, 0, (uint32_t)n_fin, c->d_albums_res.p, s));
+            RG_HIP(c, hipMemcpyAsync(c->h_albums_res.p, c->d_albums_res.p, n_fin * sizeof(rg_album_result), hipMemcpyDeviceToHost, s));
+        }
+        if (continues)
+            RG_HIP(c, hipMemcpyAsync(carry, fold.d_packs + (fold.n_packs - 1) * (size_t)RG_ALBUMS_PACK_STRIDE,
+                                     (size_t)RG_ALBUMS_PACK_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        RG_HIP(c, hipStreamSynchronize(s));
+        *files_done = first + cnt;
+        for (size_t k = 0; k < n_fin; ++k) {
+            const size_t a = fold.album_of_pack[k];
+            album_status_out[a] = album_status(a);
+            if (album_status_out[a] == RG_OK) albums_out[a] = c->h_albums_res.p[k];
+            done[a] = 1;
+        }
+    }
+    // albums without files (they have no pack): what rg_analyze_album gives for n = 0, the read-out of an empty pack
+    if (std::find(done.begin(), done.end(), 0) != done.end()) {
+        RG_HIP(c, hipMemsetAsync(carry, 0, (size_t)RG_ALBUMS_PACK_STRIDE * sizeof(uint32_t), s));
+        RG_HIP(c, rg_launch_album_results(carry, 0, 1, c->d_albums_res.p, s));
+        RG_HIP(c, hipMemcpyAsync(c->h_albums_res.p, c->d_albums_res.p, sizeof(rg_album_result), hipMemcpyDeviceToHost, s));
+        RG_HIP(c, hipStreamSynchronize(s));
+        for (size_t a = 0; a < n_albums; ++a)
+            if (!done[a]) {
+                albums_out[a] = c->h_albums_res.p[0];
+                album_status_out[a] = RG_OK;
+                done[a] = 1;
+            }
+    }
+    return RG_OK;
+}
+
+extern "C" int rg_analyze_albums(rg_ctx *c, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                                 int32_t track_index, rg_track_result *tracks_out, int32_t *status_out, rg_album_result *albums_out,
+                                 int32_t *album_status_out) {
+    if (!c) return RG_ERR_INVALID_ARG;
+    if ((n && (!paths || !tracks_out || !status_out)) || (n_albums && (!albums_out || !album_status_out)))
+        return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_analyze_albums: null input or output array");
+    std::string why;
+    if (rg_albums_check(album_first, n_albums, n, &why) != RG_OK) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_analyze_albums: %s", why.c_str());
+    c->file_errors.assign(n, std::string());
+    for (size_t a = 0; a < n_albums; ++a) memset(&albums_out[a], 0, sizeof albums_out[a]);
+    std::vector<char> done(n_albums, 0);
+    size_t files_done = 0;
+    int rc = rg_bind_device(c);
+    if (rc == RG_OK)
+        rc = analyze_albums_impl(c, paths, n, album_first, n_albums, track_index, tracks_out, status_out, albums_out, album_status_out,
+                                 done, &files_done);
+    if (rc != RG_OK) {  // the call itself failed (a device error): what it did not finish carries the call's code and text
+        const std::string text = c->err;
+        for (size_t i = files_done; i < n; ++i) {
+            memset(&tracks_out[i], 0, sizeof tracks_out[i]);
+            status_out[i] = rc;
+            c->file_errors[i] = text;
+        }
+        for (size_t a = 0; a < n_albums; ++a)
+            if (!done[a]) {
+                memset(&albums_out[a], 0, sizeof albums_out[a]);
+                album_status_out[a] = rc;
+            }
+        c->err = text;
+    }
+    return rc;
 }
 
 // find_peak_amplitude (src/replaygain.rs:1140-1249): max |x| over ALL channels, no loudness analysis

@@ -194,6 +194,21 @@ extern "C" int rg_node_last_partition(const rg_node *nd, uint32_t *owner_out, si
     return RG_OK;
 }
 
+namespace {
+// the host fold's tail: the percentile of a merged histogram, as rg_album_result_kernel reads it
+rg_album_result host_album_result(const uint32_t *hist, double peak) {
+    uint64_t total = 0;
+    for (size_t b = 0; b < RG_HISTOGRAM_SIZE; ++b) total += hist[b];
+    rg_album_result r{};
+    r.album_loudness_db = rg_hist_loudness(hist);
+    r.album_gain_db = rg_gain_from_loudness(r.album_loudness_db);
+    r.album_peak = peak;
+    r.album_gain_steps = rg_gain_steps(r.album_gain_db);
+    r.windows = (uint32_t)total;
+    return r;
+}
+}  // namespace
+
 extern "C" int rg_analyze_album_node(rg_node *nd, const char *const *paths, size_t n, int32_t track_index, rg_track_result *tracks_out,
                                      rg_album_result *album_out) {
     if (!nd || (n && (!paths || !tracks_out)) || !album_out) return RG_ERR_INVALID_ARG;
@@ -253,21 +268,13 @@ extern "C" int rg_analyze_album_node(rg_node *nd, const char *const *paths, size
             if (sh[d].rc != RG_OK) return node_err(nd, sh[d].rc, "device %d: %s", nd->devices[d], sh[d].err.c_str());
         std::vector<uint32_t> hist(RG_HISTOGRAM_SIZE, 0u);
         double peak = 0.0;
-        uint64_t total = 0;
         for (size_t d = 0; d < D; ++d) {
             for (size_t b = 0; b < RG_HISTOGRAM_SIZE; ++b) hist[b] += sh[d].pack[b];  // u32, wrapping: the reference's release build
             double p;
             memcpy(&p, sh[d].pack.data() + RG_HISTOGRAM_SIZE, sizeof p);
             if (p > peak) peak = p;
         }
-        for (uint32_t v : hist) total += v;
-        rg_album_result r{};
-        r.album_loudness_db = rg_hist_loudness(hist.data());
-        r.album_gain_db = rg_gain_from_loudness(r.album_loudness_db);
-        r.album_peak = peak;
-        r.album_gain_steps = rg_gain_steps(r.album_gain_db);
-        r.windows = (uint32_t)total;
-        *album_out = r;
+        *album_out = host_album_result(hist.data(), peak);
     }
     for (size_t d = 0; d < D; ++d)
         for (size_t k = 0; k < shares[d].size(); ++k) tracks_out[shares[d][k]] = sh[d].out[k];
@@ -308,4 +315,96 @@ extern "C" int rg_analyze_tracks_node(rg_node *nd, const char *const *paths, siz
 extern "C" const char *rg_node_tracks_error(const rg_node *nd, size_t i) {
     if (!nd || i >= nd->track_errors.size()) return "";
     return nd->track_errors[i].c_str();
+}
+
+// Whole albums to devices, weighted by their files' bytes; one rg_analyze_albums call per device (on the built-in engine) over
+// its albums in input order; results scattered back.  No exchange: an album's files are all on one device.
+extern "C" int rg_analyze_albums_node(rg_node *nd, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                                      int32_t track_index, rg_track_result *tracks_out, int32_t *status_out,
+                                      rg_album_result *albums_out, int32_t *album_status_out) {
+    if (!nd) return RG_ERR_INVALID_ARG;
+    if ((n && (!paths || !tracks_out || !status_out)) || (n_albums && (!albums_out || !album_status_out)))
+        return node_err(nd, RG_ERR_INVALID_ARG, "rg_analyze_albums_node: null input or output array");
+    std::string why;
+    if (rg_albums_check(album_first, n_albums, n, &why) != RG_OK)
+        return node_err(nd, RG_ERR_INVALID_ARG, "rg_analyze_albums_node: %s", why.c_str());
+    const size_t D = nd->engines.size();
+    std::vector<uint64_t> bytes(n_albums, 0);
+    for (size_t a = 0; a < n_albums; ++a)
+        for (size_t i = album_first[a]; i < album_first[a + 1]; ++i) {
+            struct stat st;
+            if (paths[i] && stat(paths[i], &st) == 0 && st.st_size > 0) bytes[a] += (uint64_t)st.st_size;
+        }
+    std::vector<uint32_t> album_owner(n_albums, 0);
+    rg_node_partition(bytes.data(), n_albums, D, album_owner.data());
+    nd->owner.assign(n, 0);
+    std::vector<std::vector<size_t>> mine(D);  // albums of each device, ascending
+    for (size_t a = 0; a < n_albums; ++a) {
+        mine[album_owner[a]].push_back(a);
+        for (size_t i = album_first[a]; i < album_first[a + 1]; ++i) nd->owner[i] = album_owner[a];
+    }
+    nd->track_errors.assign(n, std::string());
+    for (size_t i = 0; i < n; ++i) memset(&tracks_out[i], 0, sizeof tracks_out[i]);
+    for (size_t a = 0; a < n_albums; ++a) memset(&albums_out[a], 0, sizeof albums_out[a]);
+    on_every_device(D, [&](size_t d) {
+        if (mine[d].empty()) return;
+        void *e = nd->engines[d];
+        if (nd->builtin) {
+            std::vector<const char *> p;
+            std::vector<size_t> first(1, 0), files;
+            for (size_t a : mine[d]) {
+                for (size_t i = album_first[a]; i < album_first[a + 1]; ++i) {
+                    p.push_back(paths[i]);
+                    files.push_back(i);
+                }
+                first.push_back(p.size());
+            }
+            std::vector<rg_track_result> res(files.size());
+            std::vector<int32_t> st(files.size(), RG_OK);
+            std::vector<rg_album_result> alb(mine[d].size());
+            std::vector<int32_t> ast(mine[d].size(), RG_OK);
+            rg_ctx *c = static_cast<rg_ctx *>(e);
+            // (a call that fails still fills every record: what it had not finished carries its code and text)
+            (void)rg_analyze_albums(c, p.data(), p.size(), first.data(), mine[d].size(), track_index, res.data(), st.data(), alb.data(),
+                                    ast.data());
+            for (size_t k = 0; k < files.size(); ++k) {
+                tracks_out[files[k]] = res[k];
+                status_out[files[k]] = st[k];
+                if (st[k] != RG_OK) nd->track_errors[files[k]] = rg_tracks_error(c, k);
+            }
+            for (size_t q = 0; q < mine[d].size(); ++q) {
+                albums_out[mine[d][q]] = alb[q];
+                album_status_out[mine[d][q]] = ast[q];
+            }
+            return;
+        }
+        // a caller-supplied engine: album by album through the album entries, the percentile on the host
+        for (size_t a : mine[d]) {
+            const size_t f0 = album_first[a], k = album_first[a + 1] - f0;
+            std::vector<rg_track_result> res(k);
+            size_t failed = (size_t)-1;
+            int rc = nd->be.album_begin(e, paths + f0, k, track_index, res.data(), &failed, nd->be.user);
+            std::vector<uint32_t> pack(RG_ALBUM_PACK_WORDS, 0u);
+            if (rc == RG_OK) rc = nd->be.album_pack(e, pack.data(), nd->be.user);
+            if (rc != RG_OK) {
+                const char *t = nd->be.last_error(e, nd->be.user);
+                const std::string text = t ? t : "";
+                album_status_out[a] = rc;
+                for (size_t i = f0; i < f0 + k; ++i) {
+                    status_out[i] = rc;
+                    nd->track_errors[i] = text;
+                }
+                continue;
+            }
+            for (size_t j = 0; j < k; ++j) {
+                tracks_out[f0 + j] = res[j];
+                status_out[f0 + j] = RG_OK;
+            }
+            double peak;
+            memcpy(&peak, pack.data() + RG_HISTOGRAM_SIZE, sizeof peak);
+            albums_out[a] = host_album_result(pack.data(), peak);
+            album_status_out[a] = RG_OK;
+        }
+    });
+    return RG_OK;
 }

@@ -309,6 +309,18 @@ class Analyzer:
                 res.append(ReplayGainError(int(status[i]), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace")))
         return res
 
+    def analyze_albums_files(self, albums, track_index: Optional[int] = None, timing: Optional[dict] = None) -> list:
+        """analyze_album_files for every album of `albums` (a sequence of file sequences), as ONE call (rg_analyze_albums: the
+        files of all albums loaded, decoded and analysed like analyze_track_files takes them).  -> per album an AlbumGainResult,
+        or the ReplayGainError analyze_album_files would have raised for it.  `timing`: as analyze_album_files."""
+        args = _albums_args(albums, track_index)
+        t0 = time.perf_counter()
+        rc = self._lib.rg_analyze_albums(self._ctx, *args[:-1])
+        if timing is not None:
+            timing["c_call_seconds"] = time.perf_counter() - t0
+        self._check(rc)
+        return _albums_results(args, lambda i: self._lib.rg_tracks_error(self._ctx, i))
+
     def find_peak_amplitude_file(self, file_path) -> PeakAmplitudeResult:
         pk = _capi.PeakResult()
         self._check(self._lib.rg_find_peak_amplitude(self._ctx, os.fsencode(os.fspath(file_path)), C.byref(pk)))
@@ -579,6 +591,12 @@ class Node:
         return AlbumGainResult([_to_result(out[i], out[i].file_type) for i in range(n)], alb.album_loudness_db,
                                alb.album_gain_db, alb.album_peak)
 
+    def analyze_albums_files(self, albums, track_index: Optional[int] = None) -> list:
+        """Analyzer.analyze_albums_files over all devices: whole albums dealt out by their files' bytes, one call per device."""
+        args = _albums_args(albums, track_index)
+        self._check(self._lib.rg_analyze_albums_node(self._node, *args[:-1]))
+        return _albums_results(args, lambda i: self._lib.rg_node_tracks_error(self._node, i))
+
     def analyze_track_files(self, files, track_index: Optional[int] = None) -> list:
         """analyze_track for every file (`-r`), the files dealt out over all devices; per file a result or its error."""
         n = len(files)
@@ -631,6 +649,38 @@ def node_partition(sizes: Sequence[int], world: int) -> List[int]:
     own = (C.c_uint32 * max(1, n))()
     lib.rg_node_partition(a, n, world, own)
     return [int(own[i]) for i in range(n)]
+
+
+def _albums_args(albums, track_index: Optional[int]):
+    """rg_analyze_albums' arguments after the context / node, plus the album sizes."""
+    sizes = [len(a) for a in albums]
+    files = [os.fsencode(os.fspath(f)) for a in albums for f in a]
+    n, n_albums = len(files), len(sizes)
+    first = [0]
+    for k in sizes:
+        first.append(first[-1] + k)
+    paths = (C.c_char_p * max(1, n))(*files)
+    album_first = (C.c_size_t * (n_albums + 1))(*first)
+    out = (_capi.TrackResult * max(1, n))()
+    status = (C.c_int32 * max(1, n))()
+    alb = (_capi.AlbumResult * max(1, n_albums))()
+    alb_status = (C.c_int32 * max(1, n_albums))()
+    return (paths, n, album_first, n_albums, -1 if track_index is None else int(track_index), out, status, alb, alb_status, first)
+
+
+def _albums_results(args, file_error) -> list:
+    _, _, _, n_albums, _, out, status, alb, alb_status, first = args
+    res = []
+    for a in range(n_albums):
+        files = range(first[a], first[a + 1])
+        if alb_status[a] != 0:
+            bad = next((i for i in files if status[i] != 0), None)
+            text = file_error(bad).decode("utf-8", "replace") if bad is not None else ""
+            res.append(ReplayGainError(int(alb_status[a]), text))
+            continue
+        res.append(AlbumGainResult([_to_result(out[i], out[i].file_type) for i in files], alb[a].album_loudness_db,
+                                   alb[a].album_gain_db, alb[a].album_peak))
+    return res
 
 
 def _to_result(r: _capi.TrackResult, file_type: AudioFileType) -> ReplayGainResult:
