@@ -2,7 +2,9 @@
 information, bit reservoir, scalefactors, Huffman) on the host, stages B-E (requantisation, joint stereo, reordering,
 alias reduction, IMDCT + overlap, polyphase synthesis) on the device.  The device half is written to reproduce the host
 decoder's float arithmetic exactly (same tables, same summation order, no FMA contraction), so the bar is EQUALITY
-with mp3dec.decode on every golden stream -- which in turn is pinned against ffmpeg's decoder by tests/test_mp3dec.py --
+with mp3dec.decode on every golden stream -- which in turn is pinned against ffmpeg's decoder by tests/test_mp3dec.py
+(how the syntax is read) and against a float64 reference decoder by tests/test_mp3_refdec.py (the arithmetic);
+tests/test_gpu_mp3_refdec.py holds the device half to that reference directly, on streams no int16 golden can carry --
 and the file-level entry points must give identical ReplayGain results with either decoder."""
 import shutil
 import sys

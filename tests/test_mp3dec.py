@@ -3,14 +3,17 @@ include/mp3rgain_amd_dec.h.
 
 The reference decodes with symphonia, whose source is not in its tree and which cannot run in this image, and none of
 its tests holds a decoded sample: parity with THAT decoder is unpinned.  What is pinned here:
-  * against an independent conformant decoder -- ffmpeg's, run through the image's headless Chromium by
+  * the ARITHMETIC is pinned elsewhere, by tests/test_mp3_refdec.py: a float64 reference decoder written from the
+    standard's formulas, the bar a few float32 rounding floors -- some 3000 times finer than the ffmpeg bar below, which
+    lets a table entry wrong in its third digit through;
+  * here, the INTERPRETATION OF THE SYNTAX against an independent conformant decoder -- ffmpeg's, run through the image's headless Chromium by
     tools/make_mp3_golden.py, outputs committed as tests/golden/mp3/*.ffmpeg.npy -- on the reference's own fixtures and
     on sixteen synthetic streams (oracle/mp3_bitstream.py) that walk the rest of the syntax: every Huffman codeword of
     every table, all block types and mixed blocks, sub-block gains, MS / intensity stereo in the MPEG-1 and the LSF
     form, scfsi, preflag, both count1 tables, CRC words, the bit reservoir, MPEG-2 and MPEG-2.5 at every rate family.
     That decoder is ffmpeg's fixed-point one (int16 output, itself good to about one step): the bar is
-    max |delta| <= 1.5 and RMS <= 0.6 steps of 2^-15, which any wrong table entry, window, sign or scale misses by
-    orders of magnitude;
+    max |delta| <= 1.5 and RMS <= 0.6 steps of 2^-15, which a wrong band table, block type, stereo mode, sign or scale
+    misses by orders of magnitude;
   * the fixtures are ffmpeg encodes of a 440 Hz sine (reference .github/workflows/ci.yml:66-69): spectral peak, SNR
     against the best-fit sine, and the loudness the ReplayGain oracle gives the decoded PCM against an ideal sine;
   * packet semantics of the reference's loop (src/replaygain.rs:881-904) and container handling (ID3v2, Xing/Info);
