@@ -16,6 +16,8 @@ from .replaygain import (  # noqa: F401
     Node,
     PcmTrack,
     PeakAmplitudeResult,
+    R128AlbumResult,
+    R128Result,
     ReplayGainError,
     ReplayGainResult,
     analyze_album,

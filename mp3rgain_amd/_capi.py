@@ -72,6 +72,30 @@ class PeakResult(C.Structure):
     ]
 
 
+class R128TrackResult(C.Structure):  # include/mp3rgain_amd_r128.h
+    _fields_ = [
+        ("loudness_lufs", C.c_double),
+        ("gain_db", C.c_double),
+        ("sample_peak", C.c_double),
+        ("true_peak", C.c_double),
+        ("sample_rate", C.c_uint32),
+        ("blocks", C.c_uint32),
+        ("blocks_gated", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+class R128AlbumResult(C.Structure):
+    _fields_ = [
+        ("loudness_lufs", C.c_double),
+        ("gain_db", C.c_double),
+        ("sample_peak", C.c_double),
+        ("true_peak", C.c_double),
+        ("blocks", C.c_uint32),
+        ("blocks_gated", C.c_uint32),
+    ]
+
+
 class DeviceView(C.Structure):
     _fields_ = [
         ("d_track_hist", C.c_void_p),
@@ -161,6 +185,18 @@ SYMBOLS = [
     ("rg_analyze_albums_node", _int, [_vp, _P(C.c_char_p), _sz, _P(_sz), _sz, _i32, _P(TrackResult), _P(_i32), _P(AlbumResult), _P(_i32)]),
 ]
 
+# include/mp3rgain_amd_r128.h (EBU R 128 / ReplayGain 2.0): a header of its own, bound beside SYMBOLS
+R128_SYMBOLS = [
+    ("rg_r128_supported_rate", _int, [_u32]),
+    ("rg_r128_design_info", _int, [_u32, _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_u32), _P(_u32)]),
+    ("rg_r128_block_count", _u64, [_u32, _u64]),
+    ("rg_r128_set_tuning", _int, [_vp, _int, C.c_int64]),
+    ("rg_r128_analyze_pcm_batch", _int, [_vp, _P(TrackDesc), _sz, _vp, _sz, _int, _int, _P(R128TrackResult), _vp]),
+    ("rg_r128_analyze_album_pcm", _int, [_vp, _P(TrackDesc), _sz, _vp, _sz, _int, _int, _P(R128TrackResult), _P(R128AlbumResult), _vp]),
+    ("rg_r128_analyze_tracks", _int, [_vp, _P(C.c_char_p), _sz, _i32, _int, _P(R128TrackResult), _P(_i32)]),
+    ("rg_r128_analyze_album", _int, [_vp, _P(C.c_char_p), _sz, _i32, _int, _P(R128TrackResult), _P(R128AlbumResult)]),
+]
+
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions
 NODE_OPEN = C.CFUNCTYPE(_vp, _int, _vp)
 NODE_CLOSE = C.CFUNCTYPE(None, _vp, _vp)
@@ -201,7 +237,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

@@ -60,6 +60,8 @@ class Options:  # src/main.rs:65-96
     use_temp_file: bool = False
     assume_mpeg2: bool = False
     decoder: Optional[str] = None  # this façade only
+    r128: bool = False       # this façade only: EBU R 128 / ReplayGain 2.0 analysis instead of ReplayGain 1.0
+    true_peak: bool = False  # with --r128: report and clip-limit on the true peak
     files: List[Path] = field(default_factory=list)
 
 
@@ -113,6 +115,10 @@ def parse_args(args: List[str], out, err) -> Options:
         elif arg == "--version":
             print_version(out)
             raise Exit(0)
+        elif arg == "--r128":  # not in the reference: integrated loudness (BS.1770), gain to -18 LUFS
+            o.r128 = True
+        elif arg == "--true-peak":
+            o.true_peak = True
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -210,7 +216,7 @@ def parse_args(args: List[str], out, err) -> Options:
 
 # ---- JSON shapes (src/main.rs:101-165): field order of the structs, None fields skipped -----------------------
 _FILE_KEYS = ("file", "status", "frames", "mpeg_version", "channel_mode", "min_gain", "max_gain", "avg_gain",
-              "headroom_steps", "headroom_db", "gain_applied_steps", "gain_applied_db", "loudness_db", "peak",
+              "headroom_steps", "headroom_db", "gain_applied_steps", "gain_applied_db", "loudness_db", "loudness_lufs", "peak",
               "max_amplitude", "error", "warning", "dry_run")
 
 
@@ -235,6 +241,20 @@ def _is_flac(file) -> bool:
             return f.read(4) == b"fLaC"
     except OSError:
         return False
+
+
+def _lufs(rg):
+    """loudness_lufs of a result of the --r128 analysis, None (no JSON field) otherwise."""
+    return getattr(rg, "loudness_lufs", None)
+
+
+def _rg_of_r128(r, file):
+    """An R128Result in the shape everything downstream of the analysis reads (gain_db, peak, gain_steps(), file_type):
+    the peak is the true peak when it was asked for, the loudness is in LUFS."""
+    ft = rgmod.AudioFileType.Aac if mp4meta.is_mp4_file(file) else rgmod.AudioFileType.Mp3
+    res = rgmod.ReplayGainResult(r.loudness_lufs, r.gain_db, r.peak, r.sample_rate, ft, r.blocks, r.flags)
+    res.loudness_lufs = r.loudness_lufs
+    return res
 
 
 def _file_result(file: Path, **kw) -> dict:
@@ -327,6 +347,8 @@ class Cli:
         then finds its result -- or the error it would have raised -- here; the reference analyses file by file
         (src/main.rs:1937-2001), the results are the same."""
         files = self.o.files
+        if self.o.r128:
+            return self._analyze_track_r128(file)
         # (a file named twice is analysed again after its first occurrence has been patched, as in the reference: no batch)
         if len(files) > 1 and len({_file_identity(f) for f in files}) == len(files):
             if self._batch is None:
@@ -338,6 +360,32 @@ class Cli:
                     raise r
                 return r
         return self.analyzer().analyze_track_file(file, self.o.track_index)
+
+    def _analyze_track_r128(self, file):
+        """The --r128 analysis: every file of the command line as one batch on the first GPU (the R 128 path has no node route)."""
+        files = self.o.files
+        an = self.analyzer().analyzer(0)
+        if len(files) > 1 and len({_file_identity(f) for f in files}) == len(files):
+            if self._batch is None:
+                res = an.analyze_track_files_r128(files, self.o.true_peak, self.o.track_index)
+                self._batch = {os.fspath(f): r for f, r in zip(files, res)}
+            r = self._batch.get(os.fspath(file))
+        else:
+            r = an.analyze_track_files_r128([file], self.o.true_peak, self.o.track_index)[0]
+        if isinstance(r, rgmod.ReplayGainError):
+            raise r
+        return _rg_of_r128(r, file)
+
+    def _analyze_album_r128(self):
+        a = self.analyzer().analyzer(0).analyze_album_files_r128(self.o.files, self.o.true_peak, self.o.track_index)
+        album = rgmod.AlbumGainResult([_rg_of_r128(t, f) for t, f in zip(a.tracks, self.o.files)], a.loudness_lufs, a.gain_db, a.peak)
+        album.loudness_lufs = a.loudness_lufs
+        return album
+
+    def _target_line(self) -> str:
+        if self.o.r128:
+            return "  Target: -18 LUFS (ReplayGain 2.0, EBU R 128)"
+        return f"  Target: {_rust_float(REFERENCE_DB)} dB (ReplayGain 1.0)"
 
     def p(self, *a):
         print(*a, file=self.out)
@@ -686,7 +734,7 @@ class Cli:
             gain_db = rg.gain_db + o.gain_modifier_db  # -d shifts the suggested gain
             steps = mp3gain.db_to_steps(gain_db)
             self.p(f"{name}\t{steps}\t{gain_db:.6f}\t{rg.peak * 32768.0:.6f}\t{max_gain}\t{min_gain}")
-            return _file_result(file, loudness_db=rg.loudness_db, gain_applied_db=gain_db, gain_applied_steps=steps, peak=rg.peak,
+            return _file_result(file, loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), gain_applied_db=gain_db, gain_applied_steps=steps, peak=rg.peak,
                                 max_amplitude=max_amp, max_gain=max_gain, min_gain=min_gain)
         if mp4meta.is_mp4_file(file):
             if self.text:
@@ -764,7 +812,7 @@ class Cli:
         pre = "[DRY RUN] " if o.dry_run else ""
         if self.talk:
             self.p(f"{pre}mp3rgain Analyzing and {'would apply' if o.dry_run else 'applying'} track gain to {len(o.files)} file(s)")
-            self.p(f"  Target: {_rust_float(REFERENCE_DB)} dB (ReplayGain 1.0)")
+            self.p(self._target_line())
             if o.gain_modifier != 0:
                 self.p(f"  Gain modifier: {o.gain_modifier:+d} steps")
             self.p()
@@ -800,7 +848,7 @@ class Cli:
         if modified == 0:
             if self.talk:
                 self.p(f"  . {name} (no adjustment needed)")
-            return _file_result(file, status="skipped", loudness_db=rg.loudness_db, peak=rg.peak, gain_applied_steps=0,
+            return _file_result(file, status="skipped", loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), peak=rg.peak, gain_applied_steps=0,
                                 gain_applied_db=0.0)
         return self.apply_replaygain(file, modified, rg, None)
 
@@ -828,7 +876,7 @@ class Cli:
         if o.dry_run:
             if self.talk:
                 self.p(f"  ~ [DRY RUN] {name} (would apply {actual * GAIN_STEP_DB:+.1f} dB, {actual} steps{' (tags only)' if is_aac else ''})")
-            return _file_result(file, status="dry_run", loudness_db=rg.loudness_db, peak=rg.peak, gain_applied_steps=actual,
+            return _file_result(file, status="dry_run", loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), peak=rg.peak, gain_applied_steps=actual,
                                 gain_applied_db=actual * GAIN_STEP_DB, warning=warning, dry_run=True)
         if is_aac:  # AAC samples cannot be changed losslessly: ReplayGain tags only
             tags = mp4meta.ReplayGainTags()
@@ -844,7 +892,7 @@ class Cli:
             _restore(file, mtime)
             if self.talk:
                 self.p(f"  v {name} ({'track+album tags' if album is not None else 'tags'} written, {rg.gain_db:+.1f} dB)")
-            return _file_result(file, status="success", loudness_db=rg.loudness_db, peak=rg.peak, gain_applied_steps=rg.gain_steps(),
+            return _file_result(file, status="success", loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), peak=rg.peak, gain_applied_steps=rg.gain_steps(),
                                 gain_applied_db=rg.gain_db, warning=warning)
         if _is_riff_wave(file):
             # The reference cannot get here (its probe knows no WAV); this library analyses WAV, but PCM has no global_gain
@@ -869,7 +917,7 @@ class Cli:
         _restore(file, mtime)
         if self.talk:
             self.p(f"  v {name} ({frames} frames, {actual * GAIN_STEP_DB:+.1f} dB)")
-        return _file_result(file, status="success", frames=frames, loudness_db=rg.loudness_db, peak=rg.peak, gain_applied_steps=actual,
+        return _file_result(file, status="success", frames=frames, loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), peak=rg.peak, gain_applied_steps=actual,
                             gain_applied_db=actual * GAIN_STEP_DB, warning=warning)
 
     # ---- -a, src/main.rs:1284-1452 -------------------------------------------------------------------------------------
@@ -878,13 +926,13 @@ class Cli:
         pre = "[DRY RUN] " if o.dry_run else ""
         if self.talk:
             self.p(f"{pre}mp3rgain Analyzing album gain for {len(o.files)} file(s)")
-            self.p(f"  Target: {_rust_float(REFERENCE_DB)} dB (ReplayGain 1.0)")
+            self.p(self._target_line())
             if o.gain_modifier != 0:
                 self.p(f"  Gain modifier: {o.gain_modifier:+d} steps")
             self.p()
             self.p("  -> Analyzing tracks...")
         try:
-            album = self.analyzer().analyze_album_files(o.files, o.track_index)
+            album = self._analyze_album_r128() if o.r128 else self.analyzer().analyze_album_files(o.files, o.track_index)
         except rgmod.ReplayGainError as ex:
             if o.output_format == "json":
                 _print_json(self.out, summary=_summary(len(o.files), 0, len(o.files), o.dry_run))
@@ -901,9 +949,11 @@ class Cli:
             self.p(f"  Album peak:     {album.album_peak:.4f}")
             self.p()
         album_json = {"loudness_db": album.album_loudness_db, "gain_db": album.album_gain_db, "gain_steps": steps, "peak": album.album_peak}
+        if _lufs(album) is not None:
+            album_json["loudness_lufs"] = _lufs(album)
         if steps == 0:
             if o.output_format == "json":
-                files = [_file_result(f, status="skipped", loudness_db=t.loudness_db, peak=t.peak, gain_applied_steps=0, gain_applied_db=0.0)
+                files = [_file_result(f, status="skipped", loudness_db=t.loudness_db, loudness_lufs=_lufs(t), peak=t.peak, gain_applied_steps=0, gain_applied_db=0.0)
                          for f, t in zip(o.files, album.tracks)]
                 _print_json(self.out, files=files, album=album_json, summary=_summary(len(o.files), 0, 0, o.dry_run))
             elif not o.quiet:
@@ -1004,6 +1054,8 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "--dry-run   Same as -n",
         "-o <fmt>    Output format: 'text' (default), 'json', or 'tsv'",
         "--decoder <cmd>  Decoder command for files that are not WAV: writes a WAV stream to stdout, {} = file",
+        "--r128      Analyse after EBU R 128 / ITU-R BS.1770 (ReplayGain 2.0: gain to -18 LUFS) instead of ReplayGain 1.0",
+        "--true-peak With --r128: report and clip-limit on the true peak (4x / 2x oversampled)",
         "-v          Show version",
         "-h          Show this help",
     ):

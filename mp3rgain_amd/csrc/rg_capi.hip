@@ -329,6 +329,8 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_mp3_main.release();
     if (c->mp3_pipe && c->mp3_pipe_free) c->mp3_pipe_free(c->mp3_pipe);
     c->mp3_pipe = nullptr;
+    if (c->r128 && c->r128_free) c->r128_free(c->r128);
+    c->r128 = nullptr;
     c->d_mp3_stage[0].release();
     c->d_mp3_stage[1].release();
     c->d_mp3_results.release();
@@ -482,10 +484,8 @@ extern "C" int rg_timing_read(rg_ctx *c, double *sum_ms, uint64_t *launches, dou
     return RG_OK;
 }
 
-namespace {
-
 // copy a host PCM arena to the device staging buffer
-int stage_pcm(rg_ctx *c, const void *pcm_base, size_t pcm_bytes, int on_device, const void **d_base) {
+int rg_stage_pcm(rg_ctx *c, const void *pcm_base, size_t pcm_bytes, int on_device, const void **d_base) {
     if (on_device) {
         *d_base = pcm_base;
         return RG_OK;
@@ -499,8 +499,6 @@ int stage_pcm(rg_ctx *c, const void *pcm_base, size_t pcm_bytes, int on_device, 
     *d_base = c->d_arena.p;
     return RG_OK;
 }
-
-}  // namespace
 
 extern "C" int rg_enqueue_pcm_batch(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_pcm_base,
                                     size_t pcm_bytes, int album) {
@@ -930,7 +928,7 @@ extern "C" int rg_analyze_pcm_batch(rg_ctx *c, const rg_track_desc *tracks, size
         return analyze_host_streamed(c, tracks, n, (const unsigned char *)pcm_base, 0, out, hist_out, nullptr, nullptr, chunk);
     }
     const void *d_base = nullptr;
-    int rc = stage_pcm(c, pcm_base, pcm_bytes, on_device, &d_base);
+    int rc = rg_stage_pcm(c, pcm_base, pcm_bytes, on_device, &d_base);
     if (rc != RG_OK) return rc;
     OneShot one(c);
     rc = rg_enqueue_impl(c, tracks, n, d_base, pcm_bytes, 0);
@@ -985,7 +983,7 @@ extern "C" int rg_analyze_album_pcm(rg_ctx *c, const rg_track_desc *tracks, size
 int rg_album_local_pcm(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *pcm_base, size_t pcm_bytes, int on_device,
                        rg_track_result *tracks_out) {
     const void *d_base = nullptr;
-    int rc = stage_pcm(c, pcm_base, pcm_bytes, on_device, &d_base);
+    int rc = rg_stage_pcm(c, pcm_base, pcm_bytes, on_device, &d_base);
     if (rc != RG_OK) return rc;
     OneShot one(c);
     rc = rg_enqueue_impl(c, tracks, n, d_base, pcm_bytes, 1);
@@ -1056,7 +1054,7 @@ extern "C" int rg_find_peak_pcm(rg_ctx *c, const rg_track_desc *track, const voi
     const uint64_t total = (uint64_t)track->channels * track->frames;
     if (track->offset_bytes + total * bps > pcm_bytes) return rg_set_err(c, RG_ERR_INVALID_ARG, "track extends past arena");
     const void *d_base = nullptr;
-    int rc = stage_pcm(c, pcm_base, pcm_bytes, on_device, &d_base);
+    int rc = rg_stage_pcm(c, pcm_base, pcm_bytes, on_device, &d_base);
     if (rc != RG_OK) return rc;
     RG_HIP(c, c->d_peak_bits.reserve(1));
     RG_HIP(c, hipMemsetAsync(c->d_peak_bits.p, 0, sizeof(unsigned long long), (c->user_attached ? c->user_stream : c->slot().stream)));

@@ -225,6 +225,8 @@ struct rg_ctx {
     std::string decoder_cmd;                 // rg_set_decoder_command
     std::vector<unsigned char> force_exact;  // per track of the next enqueue: 1 = use variant 1 (exact repeat of flagged tracks)
     bool one_shot = false;  // the enqueue is a synchronous entry point's: ONE batch in flight, not one per pipeline stream (cost model)
+    void *r128 = nullptr;                    // rg_r128.hip: buffers and tuning of the EBU R 128 path
+    void (*r128_free)(void *) = nullptr;
     void *comm = nullptr;                    // ncclComm_t of rg_comm_init (owned)
     int comm_world = 1;
 
@@ -256,6 +258,8 @@ int rg_album_local_pcm(rg_ctx *c, const rg_track_desc *tracks, size_t n, const v
 // adopt a communicator made elsewhere (ncclCommInitAll in rg_node.hip); the context owns it from here on
 int rg_comm_adopt(rg_ctx *c, void *comm, int world);
 int rg_comm_init_all(rg_ctx **ctxs, size_t n);
+// a host PCM arena -> the context's device staging buffer (*d_base); a device arena is passed through (rg_capi.hip)
+int rg_stage_pcm(rg_ctx *c, const void *pcm_base, size_t pcm_bytes, int on_device, const void **d_base);
 unsigned rg_usable_cores();  // rg_files.hip: the affinity mask cut by the cgroup CPU quota
 int rg_validate_batch(rg_ctx *c, const rg_track_desc *tracks, size_t n, size_t pcm_bytes);  // argument checks of an enqueue
 // rg_analyze_albums' album_first: RG_OK, or RG_ERR_INVALID_ARG with the reason in *msg (rg_files.hip; the node checks the same)

@@ -39,6 +39,7 @@
 #include "../../include/mp3rgain_amd_demux.h"
 #include "rg_albums.h"
 #include "rg_ctx.h"
+#include "rg_r128.h"
 #include "rg_flac.h"
 #include "rg_mp3dev.h"
 #include "rg_mp3dev_host.h"
@@ -909,7 +910,7 @@ bool read_whole_file(const char *path, Mp3Scratch *sc, size_t *len) {
 // What one file of a list comes to before any analysis, in the order the reference meets its errors
 // (src/replaygain.rs:804-873): open / read, track selection, probe, sample rate.  RG_OK, or the code with `msg` set.
 int file_outcome(const LoadedAudio &la, int load_rc, const std::string &load_err, const char *path, int32_t track_index,
-                        std::string *msg) {
+                        std::string *msg, bool r128 = false /* the EBU R 128 path's rate rule */) {
     if (load_rc != RG_OK) {
         *msg = load_err;
         return load_rc;
@@ -928,6 +929,13 @@ int file_outcome(const LoadedAudio &la, int load_rc, const std::string &load_err
             *msg = std::string("Failed to probe format: ") + path;
             return RG_ERR_FORMAT;
         }
+    }
+    if (r128) {
+        if (rg_r128_supported_rate(rate)) return RG_OK;
+        char m[128];
+        snprintf(m, sizeof m, "Unsupported sample rate: %u Hz. Supported rates: %u to %u", rate, RG_R128_MIN_RATE, RG_R128_MAX_RATE);
+        *msg = m;
+        return RG_ERR_UNSUPPORTED_RATE;
     }
     if (!rg_supported_rate(rate)) {
         char m[256];
@@ -2122,4 +2130,87 @@ extern "C" int rg_flac_decode_device(void *ctx, const void *data, size_t len, in
         RG_HIP(c, hipMemcpy(planes[ch], c->d_arena.p + (size_t)ch * st.samples * sizeof(int32_t), (size_t)st.samples * sizeof(int32_t), hipMemcpyDeviceToHost));
     c->user_dirty = true;
     return RG_OK;
+}
+
+// ---- EBU R 128 (include/mp3rgain_amd_r128.h): the same loaders, decoders and groups; the analysis is rg_r128.hip's ---------
+// one group of files -> their results; album: the first failing file in input order aborts (its index in *failed), else a
+// failing file fails alone
+static int r128_files_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, int32_t track_index, int want_tp, bool album,
+                            rg_r128_track_result *out, int32_t *status_out) {
+    paths += first;
+    out += first;
+    std::vector<LoadedAudio> &in = file_pool(c, n);
+    std::vector<int> rcs;
+    std::vector<std::string> errs;
+    c->file_track_index = track_index;
+    int rc = load_many(c, paths, n, &in, &rcs, &errs, nullptr);
+    c->file_track_index = -1;
+    if (rc != RG_OK) return rc;
+    std::vector<size_t> slot;
+    for (size_t i = 0; i < n; ++i) {
+        memset(&out[i], 0, sizeof out[i]);
+        std::string msg;
+        int frc = file_outcome(in[i], rcs[i], errs[i], paths[i], track_index, &msg, true);
+        if (frc == RG_OK && !stageable(in[i])) {
+            frc = RG_ERR_FORMAT;
+            msg = std::string("Failed to probe format: ") + paths[i];
+        }
+        if (frc != RG_OK && album) return rg_set_err(c, frc, "%s", msg.c_str());
+        if (status_out) {
+            status_out[first + i] = frc;
+            c->file_errors[first + i] = msg;
+        }
+        if (frc == RG_OK) slot.push_back(i);
+    }
+    if (slot.empty()) return RG_OK;
+    for (size_t k = 0; k < slot.size(); ++k)
+        if (slot[k] != k) std::swap(in[k], in[slot[k]]);
+    std::vector<rg_track_desc> descs;
+    size_t arena_bytes = 0;
+    rc = stage_loaded(c, in, slot.size(), &descs, &arena_bytes);
+    std::vector<rg_r128_track_result> res(slot.size());
+    if (rc == RG_OK) rc = rg_r128_run(c, descs.data(), slot.size(), c->d_arena.p, arena_bytes, want_tp, album ? 1 : 0, res.data(), nullptr);
+    if (rc != RG_OK) {
+        if (album) return rc;
+        for (size_t k = 0; k < slot.size(); ++k) {  // a failure of the batch itself: every file in it carries it
+            status_out[first + slot[k]] = rc;
+            c->file_errors[first + slot[k]] = c->err;
+        }
+        return RG_OK;
+    }
+    for (size_t k = 0; k < slot.size(); ++k) out[slot[k]] = res[k];
+    return RG_OK;
+}
+
+extern "C" int rg_r128_analyze_tracks(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                                      rg_r128_track_result *out, int32_t *status_out) {
+    if (!c || (n && (!paths || !out || !status_out))) return RG_ERR_INVALID_ARG;
+    c->file_errors.assign(n, std::string());
+    int rc = rg_bind_device(c);
+    if (rc != RG_OK) return rc;
+    std::vector<std::pair<size_t, size_t>> groups;
+    file_groups(c, paths, n, &groups);
+    for (const auto &g : groups) {
+        rc = r128_files_group(c, paths, g.first, g.second, track_index, want_true_peak, false, out, status_out);
+        if (rc != RG_OK) return rc;
+    }
+    return RG_OK;
+}
+
+extern "C" int rg_r128_analyze_album(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                                     rg_r128_track_result *tracks_out, rg_r128_album_result *album_out) {
+    if (!c || (n && (!paths || !tracks_out)) || !album_out) return RG_ERR_INVALID_ARG;
+    int rc = rg_bind_device(c);
+    if (rc != RG_OK) return rc;
+    std::vector<std::pair<size_t, size_t>> groups;
+    file_groups(c, paths, n, &groups);
+    rg_r128_album_reset(c);
+    for (const auto &g : groups) {
+        rc = r128_files_group(c, paths, g.first, g.second, track_index, want_true_peak, true, tracks_out, nullptr);
+        if (rc != RG_OK) {
+            rg_r128_album_reset(c);
+            return rc;
+        }
+    }
+    return rg_r128_album_end(c, want_true_peak, album_out);
 }

@@ -1,0 +1,43 @@
+// rg_r128.h -- what the EBU R 128 path's translation units share: the host design (rg_r128_design.cpp), the device
+// descriptors and the host driver (rg_r128.hip), the file-level entry points (rg_files.hip).
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/mp3rgain_amd_r128.h"
+
+#define RG_R128_TP_TAPS 49
+#define RG_R128_WARM_HOPS 3   // a lane starts this many hops early from the zero state
+#define RG_R128_MAX_S 4096
+
+struct RgR128Design {
+    double b1[3], a1[3], b2[3], a2[3];
+    uint32_t hop, tp_factor;
+};
+// long double derivation from the analogue prototypes; false outside 8000..384000 Hz
+bool rg_r128_design(uint32_t rate, RgR128Design *out);
+// the interpolator's taps, generated here and nowhere else: f64, rounded once to f32
+void rg_r128_tp_table(uint32_t factor, float *taps /* RG_R128_TP_TAPS */);
+
+// One track of a launch.  Lanes [lane_base, lane_base + nch * runs) belong to it, channel-major: lane = c * runs + r owns hops
+// [r S, min((r + 1) S, H)) of channel c.
+struct RgR128TrackDev {
+    const unsigned char *ch[2];  // ch[1] = nullptr for one channel
+    double *e;                   // hop energies [nch][H]
+    uint64_t frames;
+    uint64_t lane_base;
+    uint64_t z_base;             // first block of the track in block_z_out
+    uint64_t tile_base;          // true peak: first block (a chunk of tiles) of the track in its launch
+    uint32_t hop, H, runs, nch, S, index, tp_factor, sample_rate, format, pad;
+    double b[3];                 // stage 1 numerator times the format's full-scale factor (a power of two: exact)
+    double a1[2], a2[2];         // denominators of stage 1 and stage 2 (a[1], a[2])
+};
+
+struct rg_ctx;
+// Loudness (and true peak) of n tracks whose PCM is on the device.  keep_for_album: the tracks' hop energies stay on the
+// device until rg_r128_album_end gates their union (call rg_r128_album_reset first).
+int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_base, size_t pcm_bytes, int want_true_peak,
+                int keep_for_album, rg_r128_track_result *out, double *block_z_out);
+void rg_r128_album_reset(rg_ctx *c);
+int rg_r128_album_end(rg_ctx *c, int want_true_peak, rg_r128_album_result *album_out);

@@ -79,6 +79,60 @@ class PeakAmplitudeResult:
     sample_rate: int
 
 
+R128_REFERENCE_LUFS = -18.0
+
+
+@dataclass
+class R128Result:
+    """EBU R 128 / ReplayGain 2.0 result of one track (rg_r128_track_result, include/mp3rgain_amd_r128.h).  `peak` is what
+    the gain-step and clip-limiting code downstream reads: the true peak when it was asked for, else the sample peak."""
+
+    loudness_lufs: float
+    gain_db: float
+    sample_peak: float
+    true_peak: float  # NaN when not asked for
+    sample_rate: int
+    blocks: int = 0
+    blocks_gated: int = 0
+    flags: int = 0
+    file_type: AudioFileType = AudioFileType.Mp3
+
+    @property
+    def peak(self) -> float:
+        return self.sample_peak if self.true_peak != self.true_peak else self.true_peak
+
+    def gain_steps(self) -> int:
+        return _capi.load().rg_gain_steps(self.gain_db)
+
+
+@dataclass
+class R128AlbumResult:
+    tracks: List[R128Result]
+    loudness_lufs: float
+    gain_db: float
+    sample_peak: float
+    true_peak: float
+    blocks: int = 0
+    blocks_gated: int = 0
+
+    @property
+    def peak(self) -> float:
+        return self.sample_peak if self.true_peak != self.true_peak else self.true_peak
+
+    def album_gain_steps(self) -> int:
+        return _capi.load().rg_gain_steps(self.gain_db)
+
+
+def r128_design_info(sample_rate: int) -> dict:
+    """The K-weighting biquads, hop and true-peak factor of one rate (rg_r128_design_info; host only)."""
+    b1, a1, b2, a2 = ((C.c_double * 3)() for _ in range(4))
+    hop, fac = C.c_uint32(), C.c_uint32()
+    rc = _capi.load().rg_r128_design_info(sample_rate, b1, a1, b2, a2, C.byref(hop), C.byref(fac))
+    if rc != _capi.RG_OK:
+        raise ReplayGainError(rc, f"Unsupported sample rate: {sample_rate} Hz. Supported rates: 8000 to 384000")
+    return {"b1": list(b1), "a1": list(a1), "b2": list(b2), "a2": list(a2), "hop": hop.value, "tp_factor": fac.value}
+
+
 _NP_FMT = {
     np.dtype(np.float32): _capi.FMT_F32_PLANAR,
     np.dtype(np.int16): _capi.FMT_S16_PLANAR,
@@ -111,6 +165,23 @@ class PcmTrack:
     @property
     def frames(self) -> int:
         return int(self.channels[0].shape[0])
+
+
+def _to_r128(r, file_type) -> R128Result:
+    return R128Result(r.loudness_lufs, r.gain_db, r.sample_peak, r.true_peak, r.sample_rate, r.blocks, r.blocks_gated, r.flags,
+                      AudioFileType(int(file_type)))
+
+
+def _to_r128_album(tracks, a) -> R128AlbumResult:
+    return R128AlbumResult(tracks, a.loudness_lufs, a.gain_db, a.sample_peak, a.true_peak, a.blocks, a.blocks_gated)
+
+
+def _split_blocks(z, counts):
+    out, p = [], 0
+    for k in counts:
+        out.append(z[p:p + k].copy())
+        p += k
+    return out
 
 
 def is_available() -> bool:
@@ -252,6 +323,59 @@ class Analyzer:
         res = AlbumGainResult([_to_result(out[i], tracks[i].file_type) for i in range(n)],
                               alb.album_loudness_db, alb.album_gain_db, alb.album_peak)
         return (res, hist) if return_histogram else res
+
+    # -- EBU R 128 / ReplayGain 2.0 (include/mp3rgain_amd_r128.h) ------------------------------------
+    def set_tuning_r128(self, key: int, value: int):
+        """key 1: hops per lane of the loudness kernel; 0 = chosen from the batch."""
+        self._check(self._lib.rg_r128_set_tuning(self._ctx, key, value))
+
+    def _r128_blocks(self, tracks):
+        counts = [int(self._lib.rg_r128_block_count(t.sample_rate, t.frames)) for t in tracks]
+        return counts, np.zeros(max(1, sum(counts)), dtype=np.float64)
+
+    def analyze_tracks_r128(self, tracks: Sequence[PcmTrack], true_peak: bool = False, return_blocks: bool = False):
+        """Integrated loudness (BS.1770), gain to -18 LUFS, sample peak and optionally true peak of each track.
+        return_blocks: also every track's gating-block mean squares (a list of float64 arrays)."""
+        n = len(tracks)
+        arena, descs = pack_tracks(tracks)
+        out = (_capi.R128TrackResult * max(1, n))()
+        counts, z = self._r128_blocks(tracks) if return_blocks else (None, None)
+        self._check(self._lib.rg_r128_analyze_pcm_batch(self._ctx, descs, n, arena.ctypes.data, arena.nbytes, 0, int(true_peak), out,
+                                                        z.ctypes.data if z is not None else None))
+        res = [_to_r128(out[i], tracks[i].file_type) for i in range(n)]
+        return (res, _split_blocks(z, counts)) if return_blocks else res
+
+    def analyze_album_r128(self, tracks: Sequence[PcmTrack], true_peak: bool = False, return_blocks: bool = False):
+        """The tracks, and the album: both gates over the union of the tracks' blocks."""
+        n = len(tracks)
+        arena, descs = pack_tracks(tracks)
+        out = (_capi.R128TrackResult * max(1, n))()
+        alb = _capi.R128AlbumResult()
+        counts, z = self._r128_blocks(tracks) if return_blocks else (None, None)
+        self._check(self._lib.rg_r128_analyze_album_pcm(self._ctx, descs, n, arena.ctypes.data, arena.nbytes, 0, int(true_peak), out,
+                                                        C.byref(alb), z.ctypes.data if z is not None else None))
+        res = _to_r128_album([_to_r128(out[i], tracks[i].file_type) for i in range(n)], alb)
+        return (res, _split_blocks(z, counts)) if return_blocks else res
+
+    def analyze_track_files_r128(self, files, true_peak: bool = False, track_index: Optional[int] = None) -> list:
+        """analyze_track_files on the R 128 path: per file an R128Result, or the ReplayGainError it failed with."""
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (_capi.R128TrackResult * max(1, n))()
+        status = (C.c_int32 * max(1, n))()
+        self._check(self._lib.rg_r128_analyze_tracks(self._ctx, paths, n, -1 if track_index is None else int(track_index),
+                                                     int(true_peak), out, status))
+        return [_to_r128(out[i], AudioFileType.Mp3) if status[i] == 0 else
+                ReplayGainError(int(status[i]), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace")) for i in range(n)]
+
+    def analyze_album_files_r128(self, files, true_peak: bool = False, track_index: Optional[int] = None) -> R128AlbumResult:
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (_capi.R128TrackResult * max(1, n))()
+        alb = _capi.R128AlbumResult()
+        self._check(self._lib.rg_r128_analyze_album(self._ctx, paths, n, -1 if track_index is None else int(track_index),
+                                                    int(true_peak), out, C.byref(alb)))
+        return _to_r128_album([_to_r128(out[i], AudioFileType.Mp3) for i in range(n)], alb)
 
     def find_peak_amplitude(self, track: PcmTrack) -> PeakAmplitudeResult:
         """find_peak_amplitude's scan over ALL channels (src/replaygain.rs:1210-1249)."""
