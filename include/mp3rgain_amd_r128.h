@@ -21,8 +21,27 @@
  *  - a track with samples that are not finite carries RG_TRACK_FLAG_NONFINITE, its loudness and gain are NaN, its peaks are
  *    the max over finite values; an album with such a track has NaN loudness; other tracks of the batch are unaffected.
  *
- * Out of scope here: many albums in one call, node / multi-GPU and asynchronous variants, loudness range, momentary and
- * short-term maxima, surround channel weights, writing R128_* Opus tags.
+ * Loudness range (EBU Tech 3342) and the momentary / short-term maxima (rg_r128_dynamics, the *_dynamics entry points), as
+ * this library and their checker (tests/r128range_ref.py) both implement them, from the same hop energies:
+ *  - maximum momentary loudness: -0.691 + 10 log10(max over b of z[b]) over all max(H - 3, 0) gating blocks, ungated; no
+ *    block, or a maximum of 0: -inf;
+ *  - short-term blocks: st[s] = (e[s] + ... + e[s+29]) / (30 hop) for s = 0 .. H-30, one every 100 ms (3 s blocks that
+ *    overlap by 2.9 s); a track of H whole hops has max(H - 29, 0) of them (rg_r128_short_term_count); e[h] is the sum over
+ *    channels 0 and 1 of hop h, and the 30 terms are added one after another in ascending h: the value depends on nothing
+ *    but the 30 energies;
+ *  - maximum short-term loudness: -0.691 + 10 log10(max over s of st[s]), -inf as above;
+ *  - loudness range: A = the blocks with st >= 10^((-70 + 0.691) / 10); thr = 0.01 * mean(A) (-20 LU); K = the blocks of A
+ *    with st >= thr, sorted ascending, n = |K|; low = K[(10 (n - 1) + 50) / 100], high = K[(95 (n - 1) + 50) / 100], both
+ *    in integer division; LRA = 10 log10(high / low) LU; range_low and range_high are low and high in LUFS; n = 0: LRA 0.0
+ *    and both bounds -inf.  low and high are elements of the block list, bit for bit: selected, not interpolated and not
+ *    read from a histogram;
+ *  - an album: the union of its tracks' short-term blocks in track order (a block never spans two tracks), the same two
+ *    gates and the same selection; its maxima are the maxima over its tracks;
+ *  - a track that carries RG_TRACK_FLAG_NONFINITE has NaN in all five values (and st_blocks_gated 0), an album with such a
+ *    track too; other tracks of the batch are unaffected.
+ *
+ * Out of scope here: many albums in one call, node / multi-GPU and asynchronous variants, surround channel weights, writing
+ * R128_* Opus tags or range tags.
  */
 #ifndef MP3RGAIN_AMD_R128_H
 #define MP3RGAIN_AMD_R128_H
@@ -57,6 +76,16 @@ typedef struct rg_r128_album_result {
     uint32_t blocks_gated;
 } rg_r128_album_result;
 
+typedef struct rg_r128_dynamics {
+    double loudness_range_lu;
+    double range_low_lufs;      /* the 10th percentile of the gated short-term blocks */
+    double range_high_lufs;     /* the 95th */
+    double max_momentary_lufs;
+    double max_short_term_lufs;
+    uint32_t st_blocks;         /* short-term blocks of the track (of the album: of all its tracks) */
+    uint32_t st_blocks_gated;   /* those both gates of the loudness range kept (n above) */
+} rg_r128_dynamics;
+
 /* ---- pure helpers (host) ---------------------------------------------------------------- */
 int rg_r128_supported_rate(uint32_t sample_rate); /* 8000 .. 384000 Hz */
 /* The K-weighting of one rate: stage 1 (shelf) b1 / a1, stage 2 (RLB high-pass) b2 / a2, three values each, a[0] = 1;
@@ -64,10 +93,16 @@ int rg_r128_supported_rate(uint32_t sample_rate); /* 8000 .. 384000 Hz */
 int rg_r128_design_info(uint32_t sample_rate, double *b1, double *a1, double *b2, double *a2, uint32_t *hop, uint32_t *tp_factor);
 /* gating blocks of a track of `frames` frames (0 for an unsupported rate) */
 uint64_t rg_r128_block_count(uint32_t sample_rate, uint64_t frames);
+/* short-term (3 s) blocks of a track of `frames` frames (0 for an unsupported rate) */
+uint64_t rg_r128_short_term_count(uint32_t sample_rate, uint64_t frames);
 
 /* key 1 = hops per lane S of the loudness kernel (0 = chosen from the batch; at most 4096).  A lane runs the recursion over S
  * consecutive hops of one channel and starts three hops early from the zero state; results do not depend on S beyond f64
- * rounding of what a lane has not seen (below 1e-30 of the signal before its start). */
+ * rounding of what a lane has not seen (below 1e-30 of the signal before its start).
+ * key 2 = how an album's loudness range is selected: 0 = chosen from the album's size (wide from 16384 short-term blocks),
+ * 1 = one workgroup makes every pass over the album's short-term blocks, 2 = every pass is a wide launch counting into an
+ * integer histogram.  Both select the same elements; the threshold's sum is rounded in another order, which shows only for
+ * a block within an ulp of it. */
 int rg_r128_set_tuning(rg_ctx *ctx, int key, int64_t value);
 
 /* ---- analysis (synchronous) ----------------------------------------------------------------- */
@@ -87,6 +122,23 @@ int rg_r128_analyze_tracks(rg_ctx *ctx, const char *const *paths, size_t n, int3
                            rg_r128_track_result *out, int32_t *status_out);
 int rg_r128_analyze_album(rg_ctx *ctx, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
                           rg_r128_track_result *tracks_out, rg_r128_album_result *album_out);
+
+/* ---- the same four, and loudness range and momentary / short-term maxima ------------------------------------------------ */
+/* Everything the call of the same name without _dynamics returns is returned bit for bit; dyn_out has one entry per track
+ * (per file: zeroed where the file failed), album_dyn_out is the album's.  st_z_out: NULL, or room for the sum of
+ * rg_r128_short_term_count over the tracks: every short-term block's mean square st, track after track. */
+int rg_r128_analyze_pcm_batch_dynamics(rg_ctx *ctx, const rg_track_desc *tracks, size_t n, const void *pcm_base, size_t pcm_bytes,
+                                       int pcm_on_device, int want_true_peak, rg_r128_track_result *out, double *block_z_out,
+                                       rg_r128_dynamics *dyn_out, double *st_z_out);
+int rg_r128_analyze_album_pcm_dynamics(rg_ctx *ctx, const rg_track_desc *tracks, size_t n, const void *pcm_base, size_t pcm_bytes,
+                                       int pcm_on_device, int want_true_peak, rg_r128_track_result *tracks_out,
+                                       rg_r128_album_result *album_out, double *block_z_out, rg_r128_dynamics *dyn_out,
+                                       rg_r128_dynamics *album_dyn_out, double *st_z_out);
+int rg_r128_analyze_tracks_dynamics(rg_ctx *ctx, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                                    rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out);
+int rg_r128_analyze_album_dynamics(rg_ctx *ctx, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                                   rg_r128_track_result *tracks_out, rg_r128_album_result *album_out, rg_r128_dynamics *dyn_out,
+                                   rg_r128_dynamics *album_dyn_out);
 
 #ifdef __cplusplus
 }

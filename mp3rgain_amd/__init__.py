@@ -17,6 +17,7 @@ from .replaygain import (  # noqa: F401
     PcmTrack,
     PeakAmplitudeResult,
     R128AlbumResult,
+    R128Dynamics,
     R128Result,
     ReplayGainError,
     ReplayGainResult,

@@ -96,6 +96,18 @@ class R128AlbumResult(C.Structure):
     ]
 
 
+class R128Dynamics(C.Structure):  # rg_r128_dynamics
+    _fields_ = [
+        ("loudness_range_lu", C.c_double),
+        ("range_low_lufs", C.c_double),
+        ("range_high_lufs", C.c_double),
+        ("max_momentary_lufs", C.c_double),
+        ("max_short_term_lufs", C.c_double),
+        ("st_blocks", C.c_uint32),
+        ("st_blocks_gated", C.c_uint32),
+    ]
+
+
 class DeviceView(C.Structure):
     _fields_ = [
         ("d_track_hist", C.c_void_p),
@@ -195,6 +207,15 @@ R128_SYMBOLS = [
     ("rg_r128_analyze_album_pcm", _int, [_vp, _P(TrackDesc), _sz, _vp, _sz, _int, _int, _P(R128TrackResult), _P(R128AlbumResult), _vp]),
     ("rg_r128_analyze_tracks", _int, [_vp, _P(C.c_char_p), _sz, _i32, _int, _P(R128TrackResult), _P(_i32)]),
     ("rg_r128_analyze_album", _int, [_vp, _P(C.c_char_p), _sz, _i32, _int, _P(R128TrackResult), _P(R128AlbumResult)]),
+    # loudness range and momentary / short-term maxima
+    ("rg_r128_short_term_count", _u64, [_u32, _u64]),
+    ("rg_r128_analyze_pcm_batch_dynamics", _int, [_vp, _P(TrackDesc), _sz, _vp, _sz, _int, _int, _P(R128TrackResult), _vp,
+                                                  _P(R128Dynamics), _vp]),
+    ("rg_r128_analyze_album_pcm_dynamics", _int, [_vp, _P(TrackDesc), _sz, _vp, _sz, _int, _int, _P(R128TrackResult), _P(R128AlbumResult),
+                                                  _vp, _P(R128Dynamics), _P(R128Dynamics), _vp]),
+    ("rg_r128_analyze_tracks_dynamics", _int, [_vp, _P(C.c_char_p), _sz, _i32, _int, _P(R128TrackResult), _P(_i32), _P(R128Dynamics)]),
+    ("rg_r128_analyze_album_dynamics", _int, [_vp, _P(C.c_char_p), _sz, _i32, _int, _P(R128TrackResult), _P(R128AlbumResult),
+                                              _P(R128Dynamics), _P(R128Dynamics)]),
 ]
 
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions

@@ -62,6 +62,7 @@ class Options:  # src/main.rs:65-96
     decoder: Optional[str] = None  # this façade only
     r128: bool = False       # this façade only: EBU R 128 / ReplayGain 2.0 analysis instead of ReplayGain 1.0
     true_peak: bool = False  # with --r128: report and clip-limit on the true peak
+    loudness_range: bool = False  # with --r128 (--range): loudness range, maximum momentary and short-term loudness
     files: List[Path] = field(default_factory=list)
 
 
@@ -119,6 +120,8 @@ def parse_args(args: List[str], out, err) -> Options:
             o.r128 = True
         elif arg == "--true-peak":
             o.true_peak = True
+        elif arg == "--range":
+            o.loudness_range = True
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -216,7 +219,8 @@ def parse_args(args: List[str], out, err) -> Options:
 
 # ---- JSON shapes (src/main.rs:101-165): field order of the structs, None fields skipped -----------------------
 _FILE_KEYS = ("file", "status", "frames", "mpeg_version", "channel_mode", "min_gain", "max_gain", "avg_gain",
-              "headroom_steps", "headroom_db", "gain_applied_steps", "gain_applied_db", "loudness_db", "loudness_lufs", "peak",
+              "headroom_steps", "headroom_db", "gain_applied_steps", "gain_applied_db", "loudness_db", "loudness_lufs",
+              "loudness_range_lu", "max_momentary_lufs", "max_short_term_lufs", "peak",
               "max_amplitude", "error", "warning", "dry_run")
 
 
@@ -248,12 +252,29 @@ def _lufs(rg):
     return getattr(rg, "loudness_lufs", None)
 
 
+def _dyn(rg) -> dict:
+    """The JSON fields of --range (loudness_range_lu, max_momentary_lufs, max_short_term_lufs) of a result of the --r128
+    analysis that carries them, nothing otherwise."""
+    d = getattr(rg, "dynamics", None)
+    if d is None:
+        return {}
+    return {"loudness_range_lu": d.loudness_range_lu, "max_momentary_lufs": d.max_momentary_lufs,
+            "max_short_term_lufs": d.max_short_term_lufs}
+
+
+def _dyn_text(d) -> str:
+    return (f"Loudness range: {d.loudness_range_lu:.1f} LU, Max momentary: {d.max_momentary_lufs:.1f} LUFS, "
+            f"Max short-term: {d.max_short_term_lufs:.1f} LUFS")
+
+
 def _rg_of_r128(r, file):
     """An R128Result in the shape everything downstream of the analysis reads (gain_db, peak, gain_steps(), file_type):
     the peak is the true peak when it was asked for, the loudness is in LUFS."""
     ft = rgmod.AudioFileType.Aac if mp4meta.is_mp4_file(file) else rgmod.AudioFileType.Mp3
     res = rgmod.ReplayGainResult(r.loudness_lufs, r.gain_db, r.peak, r.sample_rate, ft, r.blocks, r.flags)
     res.loudness_lufs = r.loudness_lufs
+    if r.dynamics is not None:
+        res.dynamics = r.dynamics
     return res
 
 
@@ -367,19 +388,22 @@ class Cli:
         an = self.analyzer().analyzer(0)
         if len(files) > 1 and len({_file_identity(f) for f in files}) == len(files):
             if self._batch is None:
-                res = an.analyze_track_files_r128(files, self.o.true_peak, self.o.track_index)
+                res = an.analyze_track_files_r128(files, self.o.true_peak, self.o.track_index, self.o.loudness_range)
                 self._batch = {os.fspath(f): r for f, r in zip(files, res)}
             r = self._batch.get(os.fspath(file))
         else:
-            r = an.analyze_track_files_r128([file], self.o.true_peak, self.o.track_index)[0]
+            r = an.analyze_track_files_r128([file], self.o.true_peak, self.o.track_index, self.o.loudness_range)[0]
         if isinstance(r, rgmod.ReplayGainError):
             raise r
         return _rg_of_r128(r, file)
 
     def _analyze_album_r128(self):
-        a = self.analyzer().analyzer(0).analyze_album_files_r128(self.o.files, self.o.true_peak, self.o.track_index)
+        a = self.analyzer().analyzer(0).analyze_album_files_r128(self.o.files, self.o.true_peak, self.o.track_index,
+                                                                     self.o.loudness_range)
         album = rgmod.AlbumGainResult([_rg_of_r128(t, f) for t, f in zip(a.tracks, self.o.files)], a.loudness_lufs, a.gain_db, a.peak)
         album.loudness_lufs = a.loudness_lufs
+        if a.dynamics is not None:
+            album.dynamics = a.dynamics
         return album
 
     def _target_line(self) -> str:
@@ -734,7 +758,7 @@ class Cli:
             gain_db = rg.gain_db + o.gain_modifier_db  # -d shifts the suggested gain
             steps = mp3gain.db_to_steps(gain_db)
             self.p(f"{name}\t{steps}\t{gain_db:.6f}\t{rg.peak * 32768.0:.6f}\t{max_gain}\t{min_gain}")
-            return _file_result(file, loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), gain_applied_db=gain_db, gain_applied_steps=steps, peak=rg.peak,
+            return _file_result(file, loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), **_dyn(rg), gain_applied_db=gain_db, gain_applied_steps=steps, peak=rg.peak,
                                 max_amplitude=max_amp, max_gain=max_gain, min_gain=min_gain)
         if mp4meta.is_mp4_file(file):
             if self.text:
@@ -845,10 +869,12 @@ class Cli:
         if self.talk:
             extra = f" + {o.gain_modifier} = {modified}" if o.gain_modifier != 0 else ""
             self.p(f"      Loudness: {rg.loudness_db:.1f} dB, Gain: {rg.gain_db:+.1f} dB ({base} steps{extra}), Peak: {rg.peak:.4f}")
+            if getattr(rg, "dynamics", None) is not None:
+                self.p(f"      {_dyn_text(rg.dynamics)}")
         if modified == 0:
             if self.talk:
                 self.p(f"  . {name} (no adjustment needed)")
-            return _file_result(file, status="skipped", loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), peak=rg.peak, gain_applied_steps=0,
+            return _file_result(file, status="skipped", loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), **_dyn(rg), peak=rg.peak, gain_applied_steps=0,
                                 gain_applied_db=0.0)
         return self.apply_replaygain(file, modified, rg, None)
 
@@ -876,7 +902,7 @@ class Cli:
         if o.dry_run:
             if self.talk:
                 self.p(f"  ~ [DRY RUN] {name} (would apply {actual * GAIN_STEP_DB:+.1f} dB, {actual} steps{' (tags only)' if is_aac else ''})")
-            return _file_result(file, status="dry_run", loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), peak=rg.peak, gain_applied_steps=actual,
+            return _file_result(file, status="dry_run", loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), **_dyn(rg), peak=rg.peak, gain_applied_steps=actual,
                                 gain_applied_db=actual * GAIN_STEP_DB, warning=warning, dry_run=True)
         if is_aac:  # AAC samples cannot be changed losslessly: ReplayGain tags only
             tags = mp4meta.ReplayGainTags()
@@ -892,7 +918,7 @@ class Cli:
             _restore(file, mtime)
             if self.talk:
                 self.p(f"  v {name} ({'track+album tags' if album is not None else 'tags'} written, {rg.gain_db:+.1f} dB)")
-            return _file_result(file, status="success", loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), peak=rg.peak, gain_applied_steps=rg.gain_steps(),
+            return _file_result(file, status="success", loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), **_dyn(rg), peak=rg.peak, gain_applied_steps=rg.gain_steps(),
                                 gain_applied_db=rg.gain_db, warning=warning)
         if _is_riff_wave(file):
             # The reference cannot get here (its probe knows no WAV); this library analyses WAV, but PCM has no global_gain
@@ -917,7 +943,7 @@ class Cli:
         _restore(file, mtime)
         if self.talk:
             self.p(f"  v {name} ({frames} frames, {actual * GAIN_STEP_DB:+.1f} dB)")
-        return _file_result(file, status="success", frames=frames, loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), peak=rg.peak, gain_applied_steps=actual,
+        return _file_result(file, status="success", frames=frames, loudness_db=rg.loudness_db, loudness_lufs=_lufs(rg), **_dyn(rg), peak=rg.peak, gain_applied_steps=actual,
                             gain_applied_db=actual * GAIN_STEP_DB, warning=warning)
 
     # ---- -a, src/main.rs:1284-1452 -------------------------------------------------------------------------------------
@@ -947,13 +973,18 @@ class Cli:
             extra = f" + {o.gain_modifier} = {steps}" if o.gain_modifier != 0 else ""
             self.p(f"  Album gain:     {album.album_gain_db:+.1f} dB ({base} steps{extra})")
             self.p(f"  Album peak:     {album.album_peak:.4f}")
+            if getattr(album, "dynamics", None) is not None:
+                self.p(f"  Album {_dyn_text(album.dynamics)}")
+                for f, t in zip(o.files, album.tracks):
+                    self.p(f"    {_name(f)}: {_dyn_text(t.dynamics)}")
             self.p()
         album_json = {"loudness_db": album.album_loudness_db, "gain_db": album.album_gain_db, "gain_steps": steps, "peak": album.album_peak}
         if _lufs(album) is not None:
             album_json["loudness_lufs"] = _lufs(album)
+        album_json.update(_dyn(album))
         if steps == 0:
             if o.output_format == "json":
-                files = [_file_result(f, status="skipped", loudness_db=t.loudness_db, loudness_lufs=_lufs(t), peak=t.peak, gain_applied_steps=0, gain_applied_db=0.0)
+                files = [_file_result(f, status="skipped", loudness_db=t.loudness_db, loudness_lufs=_lufs(t), **_dyn(t), peak=t.peak, gain_applied_steps=0, gain_applied_db=0.0)
                          for f, t in zip(o.files, album.tracks)]
                 _print_json(self.out, files=files, album=album_json, summary=_summary(len(o.files), 0, 0, o.dry_run))
             elif not o.quiet:
@@ -1056,6 +1087,7 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "--decoder <cmd>  Decoder command for files that are not WAV: writes a WAV stream to stdout, {} = file",
         "--r128      Analyse after EBU R 128 / ITU-R BS.1770 (ReplayGain 2.0: gain to -18 LUFS) instead of ReplayGain 1.0",
         "--true-peak With --r128: report and clip-limit on the true peak (4x / 2x oversampled)",
+        "--range     With --r128: also report loudness range (EBU Tech 3342), maximum momentary and short-term loudness",
         "-v          Show version",
         "-h          Show this help",
     ):

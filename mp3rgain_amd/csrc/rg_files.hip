@@ -2136,9 +2136,13 @@ extern "C" int rg_flac_decode_device(void *ctx, const void *data, size_t len, in
 // one group of files -> their results; album: the first failing file in input order aborts (its index in *failed), else a
 // failing file fails alone
 static int r128_files_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, int32_t track_index, int want_tp, bool album,
-                            rg_r128_track_result *out, int32_t *status_out) {
+                            rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out /* tracks only; may be nullptr */) {
     paths += first;
     out += first;
+    if (dyn_out) {
+        dyn_out += first;
+        memset(dyn_out, 0, n * sizeof *dyn_out);
+    }
     std::vector<LoadedAudio> &in = file_pool(c, n);
     std::vector<int> rcs;
     std::vector<std::string> errs;
@@ -2169,7 +2173,10 @@ static int r128_files_group(rg_ctx *c, const char *const *paths, size_t first, s
     size_t arena_bytes = 0;
     rc = stage_loaded(c, in, slot.size(), &descs, &arena_bytes);
     std::vector<rg_r128_track_result> res(slot.size());
-    if (rc == RG_OK) rc = rg_r128_run(c, descs.data(), slot.size(), c->d_arena.p, arena_bytes, want_tp, album ? 1 : 0, res.data(), nullptr);
+    std::vector<rg_r128_dynamics> dyn(dyn_out ? slot.size() : 0);
+    if (rc == RG_OK)
+        rc = rg_r128_run(c, descs.data(), slot.size(), c->d_arena.p, arena_bytes, want_tp, album ? 1 : 0, res.data(), nullptr,
+                         dyn_out ? dyn.data() : nullptr, nullptr);
     if (rc != RG_OK) {
         if (album) return rc;
         for (size_t k = 0; k < slot.size(); ++k) {  // a failure of the batch itself: every file in it carries it
@@ -2178,12 +2185,15 @@ static int r128_files_group(rg_ctx *c, const char *const *paths, size_t first, s
         }
         return RG_OK;
     }
-    for (size_t k = 0; k < slot.size(); ++k) out[slot[k]] = res[k];
+    for (size_t k = 0; k < slot.size(); ++k) {
+        out[slot[k]] = res[k];
+        if (dyn_out) dyn_out[slot[k]] = dyn[k];
+    }
     return RG_OK;
 }
 
-extern "C" int rg_r128_analyze_tracks(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
-                                      rg_r128_track_result *out, int32_t *status_out) {
+static int r128_tracks(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                       rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out) {
     if (!c || (n && (!paths || !out || !status_out))) return RG_ERR_INVALID_ARG;
     c->file_errors.assign(n, std::string());
     int rc = rg_bind_device(c);
@@ -2191,14 +2201,15 @@ extern "C" int rg_r128_analyze_tracks(rg_ctx *c, const char *const *paths, size_
     std::vector<std::pair<size_t, size_t>> groups;
     file_groups(c, paths, n, &groups);
     for (const auto &g : groups) {
-        rc = r128_files_group(c, paths, g.first, g.second, track_index, want_true_peak, false, out, status_out);
+        rc = r128_files_group(c, paths, g.first, g.second, track_index, want_true_peak, false, out, status_out, dyn_out);
         if (rc != RG_OK) return rc;
     }
     return RG_OK;
 }
 
-extern "C" int rg_r128_analyze_album(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
-                                     rg_r128_track_result *tracks_out, rg_r128_album_result *album_out) {
+static int r128_album(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                      rg_r128_track_result *tracks_out, rg_r128_album_result *album_out, rg_r128_dynamics *dyn_out,
+                      rg_r128_dynamics *album_dyn_out) {
     if (!c || (n && (!paths || !tracks_out)) || !album_out) return RG_ERR_INVALID_ARG;
     int rc = rg_bind_device(c);
     if (rc != RG_OK) return rc;
@@ -2206,11 +2217,34 @@ extern "C" int rg_r128_analyze_album(rg_ctx *c, const char *const *paths, size_t
     file_groups(c, paths, n, &groups);
     rg_r128_album_reset(c);
     for (const auto &g : groups) {
-        rc = r128_files_group(c, paths, g.first, g.second, track_index, want_true_peak, true, tracks_out, nullptr);
+        rc = r128_files_group(c, paths, g.first, g.second, track_index, want_true_peak, true, tracks_out, nullptr, nullptr);
         if (rc != RG_OK) {
             rg_r128_album_reset(c);
             return rc;
         }
     }
-    return rg_r128_album_end(c, want_true_peak, album_out);
+    return rg_r128_album_end(c, want_true_peak, album_out, dyn_out, album_dyn_out, nullptr);
+}
+
+extern "C" int rg_r128_analyze_tracks(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                                      rg_r128_track_result *out, int32_t *status_out) {
+    return r128_tracks(c, paths, n, track_index, want_true_peak, out, status_out, nullptr);
+}
+
+extern "C" int rg_r128_analyze_album(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                                     rg_r128_track_result *tracks_out, rg_r128_album_result *album_out) {
+    return r128_album(c, paths, n, track_index, want_true_peak, tracks_out, album_out, nullptr, nullptr);
+}
+
+extern "C" int rg_r128_analyze_tracks_dynamics(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                                               rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out) {
+    if (c && n && !dyn_out) return rg_set_err(c, RG_ERR_INVALID_ARG, "null dyn_out");
+    return r128_tracks(c, paths, n, track_index, want_true_peak, out, status_out, dyn_out);
+}
+
+extern "C" int rg_r128_analyze_album_dynamics(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                                              rg_r128_track_result *tracks_out, rg_r128_album_result *album_out,
+                                              rg_r128_dynamics *dyn_out, rg_r128_dynamics *album_dyn_out) {
+    if (c && ((n && !dyn_out) || !album_dyn_out)) return rg_set_err(c, RG_ERR_INVALID_ARG, "null dynamics output");
+    return r128_album(c, paths, n, track_index, want_true_peak, tracks_out, album_out, dyn_out, album_dyn_out);
 }

@@ -36,8 +36,20 @@ struct RgR128TrackDev {
 
 struct rg_ctx;
 // Loudness (and true peak) of n tracks whose PCM is on the device.  keep_for_album: the tracks' hop energies stay on the
-// device until rg_r128_album_end gates their union (call rg_r128_album_reset first).
+// device until rg_r128_album_end gates their union (call rg_r128_album_reset first).  dyn_out (without keep_for_album) and
+// dyn_out / album_dyn_out of rg_r128_album_end (every kept track, in input order): nullptr, or loudness range and maxima
+// are computed too (rg_r128_range.hip) after the launches of the plain call, which do not change; st_z_out goes with them.
 int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_base, size_t pcm_bytes, int want_true_peak,
-                int keep_for_album, rg_r128_track_result *out, double *block_z_out);
+                int keep_for_album, rg_r128_track_result *out, double *block_z_out, rg_r128_dynamics *dyn_out = nullptr,
+                double *st_z_out = nullptr);
 void rg_r128_album_reset(rg_ctx *c);
-int rg_r128_album_end(rg_ctx *c, int want_true_peak, rg_r128_album_result *album_out);
+int rg_r128_album_end(rg_ctx *c, int want_true_peak, rg_r128_album_result *album_out, rg_r128_dynamics *dyn_out = nullptr,
+                      rg_r128_dynamics *album_dyn_out = nullptr, double *st_z_out = nullptr);
+
+// rg_r128_range.hip: loudness range and momentary / short-term maxima of n tracks whose hop energies (tr[i].e) are on the
+// device; res[i].flags marks the tracks that are not finite.  album_out: nullptr, or the n tracks are one album too.
+// *slot holds the stage's device buffers between calls (rg_r128_range_free).  album_select: tuning key 2.
+int rg_r128_dynamics_run(rg_ctx *c, void **slot, int album_select, const RgR128TrackDev *tr, const rg_r128_track_result *res,
+                         size_t n, rg_r128_dynamics *out, rg_r128_dynamics *album_out, double *st_z_out);
+void rg_r128_dynamics_none(rg_r128_dynamics *d);  // the values of a track or an album without blocks
+void rg_r128_range_free(void *slot);

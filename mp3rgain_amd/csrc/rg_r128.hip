@@ -427,6 +427,8 @@ namespace {
 
 struct R128State {
     uint32_t tune_S = 0;
+    int tune_album_select = 0;
+    void *range = nullptr;  // rg_r128_range.hip's buffers
     DevBuf<unsigned char> d_desc;
     DevBuf<uint32_t> d_words;  // [sample peak | true peak | flags] x n
     DevBuf<rg_r128_track_result> d_res;
@@ -450,6 +452,7 @@ R128State &state(rg_ctx *c) {
         c->r128_free = [](void *p) {
             R128State *s = static_cast<R128State *>(p);
             s->drop_album();
+            rg_r128_range_free(s->range);
             s->d_desc.release();
             s->d_words.release();
             s->d_res.release();
@@ -514,6 +517,11 @@ uint32_t choose_S(const R128State &st, uint64_t channel_hops) {
 
 extern "C" int rg_r128_set_tuning(rg_ctx *c, int key, int64_t value) {
     if (!c) return RG_ERR_INVALID_ARG;
+    if (key == 2) {
+        if (value < 0 || value > 2) return rg_set_err(c, RG_ERR_INVALID_ARG, "album selection must be 0..2");
+        state(c).tune_album_select = (int)value;
+        return RG_OK;
+    }
     if (key != 1) return rg_set_err(c, RG_ERR_INVALID_ARG, "unknown R 128 tuning key %d", key);
     if (value < 0 || value > RG_R128_MAX_S) return rg_set_err(c, RG_ERR_INVALID_ARG, "hops per lane must be 0..%d", RG_R128_MAX_S);
     state(c).tune_S = (uint32_t)value;
@@ -523,7 +531,7 @@ extern "C" int rg_r128_set_tuning(rg_ctx *c, int key, int64_t value) {
 void rg_r128_album_reset(rg_ctx *c) { state(c).drop_album(); }
 
 int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_base, size_t pcm_bytes, int want_tp, int keep,
-                rg_r128_track_result *out, double *block_z_out) {
+                rg_r128_track_result *out, double *block_z_out, rg_r128_dynamics *dyn_out, double *st_z_out) {
     if (!c) return RG_ERR_INVALID_ARG;
     if (n && (!tracks || !out || !d_base)) return rg_set_err(c, RG_ERR_INVALID_ARG, "null argument");
     int rc = r128_validate(c, tracks, n, pcm_bytes);
@@ -653,15 +661,19 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
             st.kept.push_back(tr[i]);
             st.kept_res.push_back(out[i]);
         }
+    else if (dyn_out)
+        return rg_r128_dynamics_run(c, &st.range, st.tune_album_select, tr.data(), out, n, dyn_out, nullptr, st_z_out);
     return RG_OK;
 }
 
-int rg_r128_album_end(rg_ctx *c, int want_tp, rg_r128_album_result *album_out) {
+int rg_r128_album_end(rg_ctx *c, int want_tp, rg_r128_album_result *album_out, rg_r128_dynamics *dyn_out,
+                      rg_r128_dynamics *album_dyn_out, double *st_z_out) {
     if (!c || !album_out) return RG_ERR_INVALID_ARG;
     R128State &st = state(c);
     memset(album_out, 0, sizeof *album_out);
     album_out->loudness_lufs = -INFINITY;
     album_out->true_peak = want_tp ? 0.0 : NAN;
+    if (album_dyn_out) rg_r128_dynamics_none(album_dyn_out);
     const size_t n = st.kept.size();
     if (n) {
         int rc = rg_bind_device(c);
@@ -691,13 +703,23 @@ int rg_r128_album_end(rg_ctx *c, int want_tp, rg_r128_album_result *album_out) {
         album_out->sample_peak = sp;
         album_out->true_peak = want_tp ? tp : NAN;
         if (bad) album_out->loudness_lufs = album_out->gain_db = NAN;
+        if (album_dyn_out) {
+            rc = rg_r128_dynamics_run(c, &st.range, st.tune_album_select, st.kept.data(), st.kept_res.data(), n, dyn_out, album_dyn_out,
+                                      st_z_out);
+            if (rc != RG_OK) {
+                st.drop_album();
+                return rc;
+            }
+        }
     }
     st.drop_album();
     return RG_OK;
 }
 
-extern "C" int rg_r128_analyze_pcm_batch(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *pcm_base, size_t pcm_bytes,
-                                         int on_device, int want_tp, rg_r128_track_result *out, double *block_z_out) {
+namespace {
+
+int pcm_batch(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *pcm_base, size_t pcm_bytes, int on_device, int want_tp,
+              rg_r128_track_result *out, double *block_z_out, rg_r128_dynamics *dyn_out, double *st_z_out) {
     if (!c) return RG_ERR_INVALID_ARG;
     if (n && !pcm_base) return rg_set_err(c, RG_ERR_INVALID_ARG, "null pcm_base");
     int rc = r128_validate(c, tracks, n, pcm_bytes);  // before anything is copied
@@ -705,12 +727,12 @@ extern "C" int rg_r128_analyze_pcm_batch(rg_ctx *c, const rg_track_desc *tracks,
     const void *d_base = nullptr;
     rc = rg_stage_pcm(c, pcm_base, pcm_bytes, on_device, &d_base);
     if (rc != RG_OK) return rc;
-    return rg_r128_run(c, tracks, n, d_base, pcm_bytes, want_tp, 0, out, block_z_out);
+    return rg_r128_run(c, tracks, n, d_base, pcm_bytes, want_tp, 0, out, block_z_out, dyn_out, st_z_out);
 }
 
-extern "C" int rg_r128_analyze_album_pcm(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *pcm_base, size_t pcm_bytes,
-                                         int on_device, int want_tp, rg_r128_track_result *tracks_out,
-                                         rg_r128_album_result *album_out, double *block_z_out) {
+int album_pcm(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *pcm_base, size_t pcm_bytes, int on_device, int want_tp,
+              rg_r128_track_result *tracks_out, rg_r128_album_result *album_out, double *block_z_out, rg_r128_dynamics *dyn_out,
+              rg_r128_dynamics *album_dyn_out, double *st_z_out) {
     if (!c || !album_out) return RG_ERR_INVALID_ARG;
     if (n && !pcm_base) return rg_set_err(c, RG_ERR_INVALID_ARG, "null pcm_base");
     int rc = r128_validate(c, tracks, n, pcm_bytes);
@@ -724,5 +746,34 @@ extern "C" int rg_r128_analyze_album_pcm(rg_ctx *c, const rg_track_desc *tracks,
         rg_r128_album_reset(c);
         return rc;
     }
-    return rg_r128_album_end(c, want_tp, album_out);
+    return rg_r128_album_end(c, want_tp, album_out, dyn_out, album_dyn_out, st_z_out);
+}
+
+}  // namespace
+
+extern "C" int rg_r128_analyze_pcm_batch(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *pcm_base, size_t pcm_bytes,
+                                         int on_device, int want_tp, rg_r128_track_result *out, double *block_z_out) {
+    return pcm_batch(c, tracks, n, pcm_base, pcm_bytes, on_device, want_tp, out, block_z_out, nullptr, nullptr);
+}
+
+extern "C" int rg_r128_analyze_album_pcm(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *pcm_base, size_t pcm_bytes,
+                                         int on_device, int want_tp, rg_r128_track_result *tracks_out,
+                                         rg_r128_album_result *album_out, double *block_z_out) {
+    return album_pcm(c, tracks, n, pcm_base, pcm_bytes, on_device, want_tp, tracks_out, album_out, block_z_out, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rg_r128_analyze_pcm_batch_dynamics(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *pcm_base,
+                                                  size_t pcm_bytes, int on_device, int want_tp, rg_r128_track_result *out,
+                                                  double *block_z_out, rg_r128_dynamics *dyn_out, double *st_z_out) {
+    if (c && n && !dyn_out) return rg_set_err(c, RG_ERR_INVALID_ARG, "null dyn_out");
+    return pcm_batch(c, tracks, n, pcm_base, pcm_bytes, on_device, want_tp, out, block_z_out, dyn_out, st_z_out);
+}
+
+extern "C" int rg_r128_analyze_album_pcm_dynamics(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *pcm_base,
+                                                  size_t pcm_bytes, int on_device, int want_tp, rg_r128_track_result *tracks_out,
+                                                  rg_r128_album_result *album_out, double *block_z_out, rg_r128_dynamics *dyn_out,
+                                                  rg_r128_dynamics *album_dyn_out, double *st_z_out) {
+    if (c && ((n && !dyn_out) || !album_dyn_out)) return rg_set_err(c, RG_ERR_INVALID_ARG, "null dynamics output");
+    return album_pcm(c, tracks, n, pcm_base, pcm_bytes, on_device, want_tp, tracks_out, album_out, block_z_out, dyn_out, album_dyn_out,
+                     st_z_out);
 }

@@ -70,3 +70,9 @@ extern "C" uint64_t rg_r128_block_count(uint32_t rate, uint64_t frames) {
     const uint64_t H = frames / ((rate + 5u) / 10u);
     return H > 3 ? H - 3 : 0;
 }
+
+extern "C" uint64_t rg_r128_short_term_count(uint32_t rate, uint64_t frames) {
+    if (!rg_r128_supported_rate(rate)) return 0;
+    const uint64_t H = frames / ((rate + 5u) / 10u);
+    return H > 29 ? H - 29 : 0;
+}

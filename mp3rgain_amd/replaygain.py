@@ -83,6 +83,19 @@ R128_REFERENCE_LUFS = -18.0
 
 
 @dataclass
+class R128Dynamics:
+    """Loudness range (EBU Tech 3342) and the momentary / short-term maxima of a track or an album (rg_r128_dynamics)."""
+
+    loudness_range_lu: float
+    range_low_lufs: float
+    range_high_lufs: float
+    max_momentary_lufs: float
+    max_short_term_lufs: float
+    st_blocks: int = 0
+    st_blocks_gated: int = 0
+
+
+@dataclass
 class R128Result:
     """EBU R 128 / ReplayGain 2.0 result of one track (rg_r128_track_result, include/mp3rgain_amd_r128.h).  `peak` is what
     the gain-step and clip-limiting code downstream reads: the true peak when it was asked for, else the sample peak."""
@@ -96,6 +109,7 @@ class R128Result:
     blocks_gated: int = 0
     flags: int = 0
     file_type: AudioFileType = AudioFileType.Mp3
+    dynamics: Optional[R128Dynamics] = None  # asked for with dynamics=True
 
     @property
     def peak(self) -> float:
@@ -114,6 +128,7 @@ class R128AlbumResult:
     true_peak: float
     blocks: int = 0
     blocks_gated: int = 0
+    dynamics: Optional[R128Dynamics] = None  # asked for with dynamics=True
 
     @property
     def peak(self) -> float:
@@ -167,13 +182,20 @@ class PcmTrack:
         return int(self.channels[0].shape[0])
 
 
-def _to_r128(r, file_type) -> R128Result:
+def _to_dynamics(d) -> Optional[R128Dynamics]:
+    if d is None:
+        return None
+    return R128Dynamics(d.loudness_range_lu, d.range_low_lufs, d.range_high_lufs, d.max_momentary_lufs, d.max_short_term_lufs,
+                        d.st_blocks, d.st_blocks_gated)
+
+
+def _to_r128(r, file_type, dyn=None) -> R128Result:
     return R128Result(r.loudness_lufs, r.gain_db, r.sample_peak, r.true_peak, r.sample_rate, r.blocks, r.blocks_gated, r.flags,
-                      AudioFileType(int(file_type)))
+                      AudioFileType(int(file_type)), _to_dynamics(dyn))
 
 
-def _to_r128_album(tracks, a) -> R128AlbumResult:
-    return R128AlbumResult(tracks, a.loudness_lufs, a.gain_db, a.sample_peak, a.true_peak, a.blocks, a.blocks_gated)
+def _to_r128_album(tracks, a, dyn=None) -> R128AlbumResult:
+    return R128AlbumResult(tracks, a.loudness_lufs, a.gain_db, a.sample_peak, a.true_peak, a.blocks, a.blocks_gated, _to_dynamics(dyn))
 
 
 def _split_blocks(z, counts):
@@ -326,56 +348,100 @@ class Analyzer:
 
     # -- EBU R 128 / ReplayGain 2.0 (include/mp3rgain_amd_r128.h) ------------------------------------
     def set_tuning_r128(self, key: int, value: int):
-        """key 1: hops per lane of the loudness kernel; 0 = chosen from the batch."""
+        """key 1: hops per lane of the loudness kernel; 0 = chosen from the batch.  key 2: an album's loudness range selection,
+        0 = chosen by the library, 1 = one workgroup, 2 = wide counting passes."""
         self._check(self._lib.rg_r128_set_tuning(self._ctx, key, value))
 
-    def _r128_blocks(self, tracks):
-        counts = [int(self._lib.rg_r128_block_count(t.sample_rate, t.frames)) for t in tracks]
+    def _r128_blocks(self, tracks, short_term=False):
+        count = self._lib.rg_r128_short_term_count if short_term else self._lib.rg_r128_block_count
+        counts = [int(count(t.sample_rate, t.frames)) for t in tracks]
         return counts, np.zeros(max(1, sum(counts)), dtype=np.float64)
 
-    def analyze_tracks_r128(self, tracks: Sequence[PcmTrack], true_peak: bool = False, return_blocks: bool = False):
+    def analyze_tracks_r128(self, tracks: Sequence[PcmTrack], true_peak: bool = False, return_blocks: bool = False,
+                            dynamics: bool = False, return_short_term: bool = False):
         """Integrated loudness (BS.1770), gain to -18 LUFS, sample peak and optionally true peak of each track.
-        return_blocks: also every track's gating-block mean squares (a list of float64 arrays)."""
+        return_blocks: also every track's gating-block mean squares (a list of float64 arrays).
+        dynamics: every result carries an R128Dynamics (loudness range, momentary and short-term maxima).
+        return_short_term (with dynamics): also every track's short-term block mean squares, after the gating blocks if both
+        are asked for."""
+        if return_short_term and not dynamics:
+            raise ValueError("return_short_term needs dynamics=True")
         n = len(tracks)
         arena, descs = pack_tracks(tracks)
         out = (_capi.R128TrackResult * max(1, n))()
         counts, z = self._r128_blocks(tracks) if return_blocks else (None, None)
-        self._check(self._lib.rg_r128_analyze_pcm_batch(self._ctx, descs, n, arena.ctypes.data, arena.nbytes, 0, int(true_peak), out,
-                                                        z.ctypes.data if z is not None else None))
-        res = [_to_r128(out[i], tracks[i].file_type) for i in range(n)]
-        return (res, _split_blocks(z, counts)) if return_blocks else res
+        zp = z.ctypes.data if z is not None else None
+        dyn = None
+        if dynamics:
+            dyn = (_capi.R128Dynamics * max(1, n))()
+            st_counts, st = self._r128_blocks(tracks, True) if return_short_term else (None, None)
+            self._check(self._lib.rg_r128_analyze_pcm_batch_dynamics(self._ctx, descs, n, arena.ctypes.data, arena.nbytes, 0, int(true_peak),
+                                                                     out, zp, dyn, st.ctypes.data if st is not None else None))
+        else:
+            self._check(self._lib.rg_r128_analyze_pcm_batch(self._ctx, descs, n, arena.ctypes.data, arena.nbytes, 0, int(true_peak), out, zp))
+        res = [_to_r128(out[i], tracks[i].file_type, dyn[i] if dyn is not None else None) for i in range(n)]
+        extra = ([_split_blocks(z, counts)] if return_blocks else []) + ([_split_blocks(st, st_counts)] if return_short_term else [])
+        return (res, *extra) if extra else res
 
-    def analyze_album_r128(self, tracks: Sequence[PcmTrack], true_peak: bool = False, return_blocks: bool = False):
-        """The tracks, and the album: both gates over the union of the tracks' blocks."""
+    def analyze_album_r128(self, tracks: Sequence[PcmTrack], true_peak: bool = False, return_blocks: bool = False,
+                           dynamics: bool = False, return_short_term: bool = False):
+        """The tracks, and the album: both gates over the union of the tracks' blocks.  dynamics, return_short_term: as in
+        analyze_tracks_r128; the album's R128Dynamics is over the union of the tracks' short-term blocks."""
+        if return_short_term and not dynamics:
+            raise ValueError("return_short_term needs dynamics=True")
         n = len(tracks)
         arena, descs = pack_tracks(tracks)
         out = (_capi.R128TrackResult * max(1, n))()
         alb = _capi.R128AlbumResult()
         counts, z = self._r128_blocks(tracks) if return_blocks else (None, None)
-        self._check(self._lib.rg_r128_analyze_album_pcm(self._ctx, descs, n, arena.ctypes.data, arena.nbytes, 0, int(true_peak), out,
-                                                        C.byref(alb), z.ctypes.data if z is not None else None))
-        res = _to_r128_album([_to_r128(out[i], tracks[i].file_type) for i in range(n)], alb)
-        return (res, _split_blocks(z, counts)) if return_blocks else res
+        zp = z.ctypes.data if z is not None else None
+        dyn = adyn = None
+        if dynamics:
+            dyn = (_capi.R128Dynamics * max(1, n))()
+            adyn = _capi.R128Dynamics()
+            st_counts, st = self._r128_blocks(tracks, True) if return_short_term else (None, None)
+            self._check(self._lib.rg_r128_analyze_album_pcm_dynamics(self._ctx, descs, n, arena.ctypes.data, arena.nbytes, 0, int(true_peak),
+                                                                     out, C.byref(alb), zp, dyn, C.byref(adyn),
+                                                                     st.ctypes.data if st is not None else None))
+        else:
+            self._check(self._lib.rg_r128_analyze_album_pcm(self._ctx, descs, n, arena.ctypes.data, arena.nbytes, 0, int(true_peak), out,
+                                                            C.byref(alb), zp))
+        res = _to_r128_album([_to_r128(out[i], tracks[i].file_type, dyn[i] if dyn is not None else None) for i in range(n)], alb, adyn)
+        extra = ([_split_blocks(z, counts)] if return_blocks else []) + ([_split_blocks(st, st_counts)] if return_short_term else [])
+        return (res, *extra) if extra else res
 
-    def analyze_track_files_r128(self, files, true_peak: bool = False, track_index: Optional[int] = None) -> list:
+    def analyze_track_files_r128(self, files, true_peak: bool = False, track_index: Optional[int] = None, dynamics: bool = False) -> list:
         """analyze_track_files on the R 128 path: per file an R128Result, or the ReplayGainError it failed with."""
         n = len(files)
         paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
         out = (_capi.R128TrackResult * max(1, n))()
         status = (C.c_int32 * max(1, n))()
-        self._check(self._lib.rg_r128_analyze_tracks(self._ctx, paths, n, -1 if track_index is None else int(track_index),
-                                                     int(true_peak), out, status))
-        return [_to_r128(out[i], AudioFileType.Mp3) if status[i] == 0 else
+        ti = -1 if track_index is None else int(track_index)
+        dyn = None
+        if dynamics:
+            dyn = (_capi.R128Dynamics * max(1, n))()
+            self._check(self._lib.rg_r128_analyze_tracks_dynamics(self._ctx, paths, n, ti, int(true_peak), out, status, dyn))
+        else:
+            self._check(self._lib.rg_r128_analyze_tracks(self._ctx, paths, n, ti, int(true_peak), out, status))
+        return [_to_r128(out[i], AudioFileType.Mp3, dyn[i] if dyn is not None else None) if status[i] == 0 else
                 ReplayGainError(int(status[i]), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace")) for i in range(n)]
 
-    def analyze_album_files_r128(self, files, true_peak: bool = False, track_index: Optional[int] = None) -> R128AlbumResult:
+    def analyze_album_files_r128(self, files, true_peak: bool = False, track_index: Optional[int] = None,
+                                 dynamics: bool = False) -> R128AlbumResult:
         n = len(files)
         paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
         out = (_capi.R128TrackResult * max(1, n))()
         alb = _capi.R128AlbumResult()
-        self._check(self._lib.rg_r128_analyze_album(self._ctx, paths, n, -1 if track_index is None else int(track_index),
-                                                    int(true_peak), out, C.byref(alb)))
-        return _to_r128_album([_to_r128(out[i], AudioFileType.Mp3) for i in range(n)], alb)
+        ti = -1 if track_index is None else int(track_index)
+        dyn = adyn = None
+        if dynamics:
+            dyn = (_capi.R128Dynamics * max(1, n))()
+            adyn = _capi.R128Dynamics()
+            self._check(self._lib.rg_r128_analyze_album_dynamics(self._ctx, paths, n, ti, int(true_peak), out, C.byref(alb), dyn,
+                                                                 C.byref(adyn)))
+        else:
+            self._check(self._lib.rg_r128_analyze_album(self._ctx, paths, n, ti, int(true_peak), out, C.byref(alb)))
+        return _to_r128_album([_to_r128(out[i], AudioFileType.Mp3, dyn[i] if dyn is not None else None) for i in range(n)], alb, adyn)
 
     def find_peak_amplitude(self, track: PcmTrack) -> PeakAmplitudeResult:
         """find_peak_amplitude's scan over ALL channels (src/replaygain.rs:1210-1249)."""
