@@ -64,7 +64,12 @@ typedef enum rg_file_type { RG_FILE_MP3 = 0, RG_FILE_AAC = 1 } rg_file_type;
 /* One decoded track inside a caller-owned PCM arena.  Channel c of the track starts at
  * pcm_base + offset_bytes + c * frames * bytes_per_sample (planar, the layout
  * `buf.chan(c)[frame]` of src/replaygain.rs:966,972).  Only channels 0 and 1 are read
- * (src/replaygain.rs:971); channels == 1 selects add_mono_sample (:731-740). */
+ * (src/replaygain.rs:971); channels == 1 selects add_mono_sample (:731-740).
+ * Layout (pinned by tests/test_gpu_arena_layouts.py): offset_bytes and pcm_base -- a host pointer or, with pcm_on_device = 1, a
+ * device pointer -- need only be aligned to the sample (2 bytes for S16, 4 for F32 / S32), nothing more; the descriptors may
+ * appear in any order relative to where their PCM is stored, tracks may abut, and two descriptors may describe the same
+ * bytes.  Nothing outside [offset_bytes, offset_bytes + channels * frames * bytes_per_sample) influences a track's result,
+ * whatever lies there (other tracks, NaN, full-scale values); that range must lie inside [0, pcm_bytes). */
 typedef struct rg_track_desc {
     uint64_t offset_bytes;
     uint64_t frames;

@@ -106,8 +106,11 @@ uint64_t rg_r128_short_term_count(uint32_t sample_rate, uint64_t frames);
 int rg_r128_set_tuning(rg_ctx *ctx, int key, int64_t value);
 
 /* ---- analysis (synchronous) ----------------------------------------------------------------- */
-/* n independent tracks of a planar PCM arena (rg_track_desc, mp3rgain_amd.h).  block_z_out: NULL, or room for the sum of
- * rg_r128_block_count over the tracks: every block's mean square z, track after track. */
+/* n independent tracks of a planar PCM arena (rg_track_desc, mp3rgain_amd.h: sample alignment only, any storage order,
+ * descriptors may alias, nothing outside a track's bytes counts).  block_z_out: NULL, or room for the sum of
+ * rg_r128_block_count over the tracks: every block's mean square z, track after track.
+ * pcm_on_device = 1: pcm_base is a device pointer and the kernels read it on the context's own stream, which is not ordered
+ * behind any stream of the caller's: the PCM must be complete (the producing stream synchronised) before the call. */
 int rg_r128_analyze_pcm_batch(rg_ctx *ctx, const rg_track_desc *tracks, size_t n, const void *pcm_base, size_t pcm_bytes,
                               int pcm_on_device, int want_true_peak, rg_r128_track_result *out, double *block_z_out);
 /* the same, and the n tracks as one album */
