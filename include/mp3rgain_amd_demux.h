@@ -12,7 +12,7 @@
  *                         stsz|stz2 + stsc + stco|co64
  *   rg_adts_scan / rg_adts_access_units   the same for a raw ADTS stream (.aac)
  *
- * What the library does with them (rg_files.hip): an MP4 file's audio tracks are counted ("No audio track found",
+ * What the library does with them (rg_file_load.hip): an MP4 file's audio tracks are counted ("No audio track found",
  * "Track index {} out of range (file has {} audio track(s))"), the selected track's rate is known before anything is decoded,
  * MPEG Layer III in MP4 is decoded by the library's own decoder from the sample table, and AAC goes to the decoder command
  * (rg_set_decoder_command; "{track}" in it is replaced by the audio track index) -- an AAC-LC decoder is not built: nothing in

@@ -165,7 +165,7 @@ struct rg_ctx {
     DevBuf<uint32_t> d_mp3_perm_set[2];
     DevBuf<uint32_t> d_mp3_sortw_set[2];
     PinnedBuf<uint32_t> h_mp3_results;
-    // An album of MPEG streams is analysed chunk by chunk while later chunks are still being copied and decoded (rg_files.hip:
+    // An album of MPEG streams is analysed chunk by chunk while later chunks are still being copied and decoded (rg_mp3_pipe.hip:
     // album parts): the batch enqueued next waits for `enqueue_wait_ev` (the chunk's decode) on its own stream; per chunk a copy
     // of the frame parser's counts, and every part's per-track results, land in pinned memory without a host synchronise
     hipEvent_t enqueue_wait_ev = nullptr;
@@ -173,16 +173,16 @@ struct rg_ctx {
     PinnedBuf<uint32_t> h_mp3_part_counts;
     PinnedBuf<rg_track_result> h_part_results;
     hipEvent_t *mp3_bench_ev = nullptr;      // rg_mp3_decode_bench: four events recorded around the three decode stages of a chunk
-    void *mp3_pipe = nullptr;                // rg_files.hip: pinned staging blocks of the loader pipeline
+    void *mp3_pipe = nullptr;                // rg_mp3_pipe.hip: pinned staging blocks of the loader pipeline
     void (*mp3_pipe_free)(void *) = nullptr;
-    // host buffers of the file layer (rg_files.hip), kept between calls: freeing and re-mapping hundreds of MB that
+    // host buffers of the file layer (rg_file_load.hip), kept between calls: freeing and re-mapping hundreds of MB that
     // were the source of H2D copies cost more than decoding them (munmap of such pages: 0.4 ms per MB)
     void *file_pool = nullptr;
     std::vector<std::string> file_errors;    // rg_analyze_tracks: message per file of the last call
     void (*file_pool_free)(void *) = nullptr;
     int gpu_mp3_decode = 3;                  // tuning key 6: 0 = host decoder, 1 = stages B-E of MP3 decoding run on the device,
                                              // 2 = scalefactors + Huffman too, 3 (default) = side-information parsing too: the host
-                                             // only finds the frames and strips their headers (loader pipeline, rg_files.hip)
+                                             // only finds the frames and strips their headers (loader pipeline, rg_mp3_pipe.hip)
     int gpu_flac_decode = 1;                 // tuning key 14: 0 = host FLAC decoder, 1 (default) = the device decoder (rg_flacdev.hip)
     DevBuf<unsigned char> d_flac_blob;       // rg_flacdev.hip: the staged FLAC streams, their frame index and stream table
     DevBuf<unsigned char> d_flac_work;       // per frame: good / dropped flags and output offsets; per stream: results
@@ -221,7 +221,7 @@ struct rg_ctx {
     hipStream_t ingest_stream = nullptr;     // H2D copies of the streamed ingest
     hipEvent_t ingest_copied[2] = {nullptr, nullptr}, ingest_free[2] = {nullptr, nullptr};
     uint64_t tune_ingest_chunk_kib = 0;      // 0 = default (2 GiB)
-    DevBuf<unsigned char> d_wav;             // interleaved WAV samples awaiting de-interleave (rg_files.hip)
+    DevBuf<unsigned char> d_wav;             // interleaved WAV samples awaiting de-interleave (rg_wav.hip)
     std::string decoder_cmd;                 // rg_set_decoder_command
     std::vector<unsigned char> force_exact;  // per track of the next enqueue: 1 = use variant 1 (exact repeat of flagged tracks)
     bool one_shot = false;  // the enqueue is a synchronous entry point's: ONE batch in flight, not one per pipeline stream (cost model)
@@ -236,6 +236,15 @@ struct rg_ctx {
     hipEvent_t timing_first = nullptr;  // start event of the first bracketed launch since the last reset
     double timing_span_ms = 0.0;        // first start -> last end over all bracketed launches
 };
+
+// wait for the streams of slots [0, n): n = c->n_slots for the slots in use, RG_SLOT_STREAMS for every pipeline stream
+static inline hipError_t rg_sync_slots(rg_ctx *c, int n) {
+    for (int k = 0; k < n; ++k) {
+        const hipError_t e = hipStreamSynchronize(c->slots[k].stream);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 int rg_set_err(rg_ctx *c, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 int rg_rate_index(uint32_t sr);
@@ -260,7 +269,7 @@ int rg_comm_adopt(rg_ctx *c, void *comm, int world);
 int rg_comm_init_all(rg_ctx **ctxs, size_t n);
 // a host PCM arena -> the context's device staging buffer (*d_base); a device arena is passed through (rg_capi.hip)
 int rg_stage_pcm(rg_ctx *c, const void *pcm_base, size_t pcm_bytes, int on_device, const void **d_base);
-unsigned rg_usable_cores();  // rg_files.hip: the affinity mask cut by the cgroup CPU quota
+unsigned rg_usable_cores();  // rg_file_load.hip: the affinity mask cut by the cgroup CPU quota
 int rg_validate_batch(rg_ctx *c, const rg_track_desc *tracks, size_t n, size_t pcm_bytes);  // argument checks of an enqueue
 // rg_analyze_albums' album_first: RG_OK, or RG_ERR_INVALID_ARG with the reason in *msg (rg_files.hip; the node checks the same)
 int rg_albums_check(const size_t *album_first, size_t n_albums, size_t n, std::string *msg);

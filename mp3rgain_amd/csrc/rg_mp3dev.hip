@@ -1226,7 +1226,7 @@ rg_mp3_huffman_kernel(const RgMp3DevTables *__restrict__ T, const RgMp3DevHuff *
     // longest lane, and in stream order a wave holds mid and side channels, loud and quiet granules side by side -- 2 to 3
     // times the iterations its units need on average.
 #ifndef RG_HF_STRIPE
-    // Blocks in the order of the sort, heaviest first: a chunk is several generations of blocks (rg_files.hip: 768 K units
+    // Blocks in the order of the sort, heaviest first: a chunk is several generations of blocks (rg_pipe_plan.h: 768 K units
     // against 262 144 resident lanes), the long blocks start first and the short ones fill in behind them.
     const uint32_t slot = blockIdx.x * kHuffThreads + (uint32_t)tid;
 #else

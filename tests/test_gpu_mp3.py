@@ -377,7 +377,7 @@ def test_loader_pipeline_with_tiny_staging_blocks(oracle, tmp_path, monkeypatch)
 
 
 def test_album_parts_give_the_plain_route_results(tmp_path, monkeypatch):
-    """Album parts (rg_files.hip: PartsRun): the tracks of a decoded chunk are analysed while later chunks are copied and decoded,
+    """Album parts (rg_mp3_pipe.hip: PipeCall::analyze_part): the tracks of a decoded chunk are analysed while later chunks are copied and decoded,
     and the album is the fold of the parts' packs.  With tiny staging blocks (dozens of chunks) and every chunk made a part, only
     copy-bound chunks (the default rule: the rest waits and joins a later part -- unless the device had to wait for it), and no
     parts at all, an album of 45 files --
