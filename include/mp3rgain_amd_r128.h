@@ -40,13 +40,17 @@
  *  - a track that carries RG_TRACK_FLAG_NONFINITE has NaN in all five values (and st_blocks_gated 0), an album with such a
  *    track too; other tracks of the batch are unaffected.
  *
- * Out of scope here: many albums in one call, node / multi-GPU and asynchronous variants, surround channel weights, writing
- * R128_* Opus tags or range tags.
+ * Many albums in one call (rg_r128_analyze_albums*, below) gate every album on the device in the same launches, and the node
+ * entry points deal whole albums (or files) out over the GPUs of a node.
+ *
+ * Out of scope here: one album across several GPUs (it would need an exchange of hop energies), asynchronous variants,
+ * surround channel weights, writing R128_* Opus tags or range tags.
  */
 #ifndef MP3RGAIN_AMD_R128_H
 #define MP3RGAIN_AMD_R128_H
 
 #include "mp3rgain_amd.h"
+#include "mp3rgain_amd_node.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -96,6 +100,15 @@ uint64_t rg_r128_block_count(uint32_t sample_rate, uint64_t frames);
 /* short-term (3 s) blocks of a track of `frames` frames (0 for an unsupported rate) */
 uint64_t rg_r128_short_term_count(uint32_t sample_rate, uint64_t frames);
 
+/* How an album of st_blocks short-term blocks is selected under tuning key 2 = album_select: 1 = one workgroup, 2 = wide
+ * passes.  rg_r128_albums_count_workgroups: the workgroups of one wide counting pass over such an album (each takes at
+ * least 4096 values, 256 at most).  rg_r128_albums_wide_rounds: a call's wide albums are selected 64 at a time, the rounds
+ * that many albums take; *state_bytes (may be NULL): the device memory of their selection states (203264 bytes per album
+ * of a round, 12.4 MiB at most). */
+int rg_r128_album_select_form(int album_select, uint64_t st_blocks);
+uint32_t rg_r128_albums_count_workgroups(uint64_t st_blocks);
+size_t rg_r128_albums_wide_rounds(size_t wide_albums, size_t *state_bytes);
+
 /* key 1 = hops per lane S of the loudness kernel (0 = chosen from the batch; at most 4096).  A lane runs the recursion over S
  * consecutive hops of one channel and starts three hops early from the zero state; results do not depend on S beyond f64
  * rounding of what a lane has not seen (below 1e-30 of the signal before its start).
@@ -142,6 +155,58 @@ int rg_r128_analyze_tracks_dynamics(rg_ctx *ctx, const char *const *paths, size_
 int rg_r128_analyze_album_dynamics(rg_ctx *ctx, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
                                    rg_r128_track_result *tracks_out, rg_r128_album_result *album_out, rg_r128_dynamics *dyn_out,
                                    rg_r128_dynamics *album_dyn_out);
+
+/* ---- many albums in one call ------------------------------------------------------------------------------------------------ */
+/* Albums as in rg_analyze_albums: album a is tracks (files) [album_first[a], album_first[a + 1]); album_first[n_albums + 1]
+ * ascends from 0 to n.  A malformed album_first is refused with RG_ERR_INVALID_ARG and the function's name in front of the
+ * reason, before any output is touched.  One pass over all n tracks, then every album's gates (and, with _dynamics, every
+ * album's loudness range) in the same launches: for a PCM call whose wide albums fit one round of 64, the number of kernel
+ * launches does not depend on n_albums.
+ *  - Equality: album a's record, every track's record and, with _dynamics, both rg_r128_dynamics are bit for bit what the
+ *    single-album call of the same kind returns on that album's tracks or files under the same tuning: the same hops per
+ *    lane (key 1 set, or both batches small enough that the library chooses S = 4) and the same album selection mode
+ *    (key 2; with key 2 = 0 the form is chosen per album from that album's own short-term block count, as the single-album
+ *    call does).
+ *  - An album without tracks gets what rg_r128_analyze_album gives for n = 0.
+ *  - An album with a track that is not finite has NaN loudness and NaN dynamics; other albums are unaffected.
+ * block_z_out, st_z_out: as in rg_r128_analyze_pcm_batch[_dynamics], over all n tracks. */
+int rg_r128_analyze_albums_pcm(rg_ctx *ctx, const rg_track_desc *tracks, size_t n, const size_t *album_first, size_t n_albums,
+                               const void *pcm_base, size_t pcm_bytes, int pcm_on_device, int want_true_peak,
+                               rg_r128_track_result *tracks_out, rg_r128_album_result *albums_out, double *block_z_out);
+int rg_r128_analyze_albums_pcm_dynamics(rg_ctx *ctx, const rg_track_desc *tracks, size_t n, const size_t *album_first,
+                                        size_t n_albums, const void *pcm_base, size_t pcm_bytes, int pcm_on_device,
+                                        int want_true_peak, rg_r128_track_result *tracks_out, rg_r128_album_result *albums_out,
+                                        double *block_z_out, rg_r128_dynamics *dyn_out, rg_r128_dynamics *albums_dyn_out,
+                                        double *st_z_out);
+/* Files: the groups of rg_r128_analyze_tracks over the whole list, with its per-file status and texts (rg_tracks_error; a
+ * WAV of a format no de-interleave reads fails alone with "Failed to probe format").  After each group every album whose
+ * last file lies in the groups taken so far is gated, all of them in one album stage; an album that goes on into the next
+ * group keeps its hop energies on the device until then.  album_status_out[a]: RG_OK, or the code of the album's first
+ * failing file in input order -- code and text are what rg_r128_analyze_album reports for that album; albums_out[a] and
+ * albums_dyn_out[a] are then zero.  A failing file or album does not stop the others, a file's result is valid whenever its
+ * status is RG_OK, and the return value is RG_OK when the call itself worked.  When it did not (a device error), everything
+ * not finished carries the call's code and text, as in rg_analyze_albums. */
+int rg_r128_analyze_albums(rg_ctx *ctx, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                           int32_t track_index, int want_true_peak, rg_r128_track_result *tracks_out, int32_t *status_out,
+                           rg_r128_album_result *albums_out, int32_t *album_status_out);
+int rg_r128_analyze_albums_dynamics(rg_ctx *ctx, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                                    int32_t track_index, int want_true_peak, rg_r128_track_result *tracks_out, int32_t *status_out,
+                                    rg_r128_album_result *albums_out, int32_t *album_status_out, rg_r128_dynamics *dyn_out,
+                                    rg_r128_dynamics *albums_dyn_out);
+
+/* ---- all GPUs of a node (mp3rgain_amd_node.h) ---------------------------------------------------------------------------- */
+/* Files (rg_r128_analyze_tracks_node) or whole albums (rg_r128_analyze_albums_node) are dealt out by their bytes with
+ * rg_node_partition; every device makes one rg_r128_analyze_tracks[_dynamics] / rg_r128_analyze_albums[_dynamics] call on
+ * its share and the results go back to input order: bit for bit those of one context.  There is no exchange: an album is
+ * never split.  dyn_out / albums_dyn_out may be NULL (both, for the albums): without dynamics.  rg_node_last_partition and
+ * rg_node_tracks_error work as for rg_analyze_albums_node.  A node made by rg_node_create_backend has no R 128 entries:
+ * RG_ERR_STATE. */
+int rg_r128_analyze_tracks_node(rg_node *node, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                                rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out);
+int rg_r128_analyze_albums_node(rg_node *node, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                                int32_t track_index, int want_true_peak, rg_r128_track_result *tracks_out, int32_t *status_out,
+                                rg_r128_album_result *albums_out, int32_t *album_status_out, rg_r128_dynamics *dyn_out,
+                                rg_r128_dynamics *albums_dyn_out);
 
 #ifdef __cplusplus
 }

@@ -216,6 +216,21 @@ R128_SYMBOLS = [
     ("rg_r128_analyze_tracks_dynamics", _int, [_vp, _P(C.c_char_p), _sz, _i32, _int, _P(R128TrackResult), _P(_i32), _P(R128Dynamics)]),
     ("rg_r128_analyze_album_dynamics", _int, [_vp, _P(C.c_char_p), _sz, _i32, _int, _P(R128TrackResult), _P(R128AlbumResult),
                                               _P(R128Dynamics), _P(R128Dynamics)]),
+    # many albums in one call, and the node
+    ("rg_r128_album_select_form", _int, [_int, _u64]),
+    ("rg_r128_albums_count_workgroups", _u32, [_u64]),
+    ("rg_r128_albums_wide_rounds", _sz, [_sz, _P(_sz)]),
+    ("rg_r128_analyze_albums_pcm", _int, [_vp, _P(TrackDesc), _sz, _P(_sz), _sz, _vp, _sz, _int, _int, _P(R128TrackResult),
+                                          _P(R128AlbumResult), _vp]),
+    ("rg_r128_analyze_albums_pcm_dynamics", _int, [_vp, _P(TrackDesc), _sz, _P(_sz), _sz, _vp, _sz, _int, _int, _P(R128TrackResult),
+                                                   _P(R128AlbumResult), _vp, _P(R128Dynamics), _P(R128Dynamics), _vp]),
+    ("rg_r128_analyze_albums", _int, [_vp, _P(C.c_char_p), _sz, _P(_sz), _sz, _i32, _int, _P(R128TrackResult), _P(_i32),
+                                      _P(R128AlbumResult), _P(_i32)]),
+    ("rg_r128_analyze_albums_dynamics", _int, [_vp, _P(C.c_char_p), _sz, _P(_sz), _sz, _i32, _int, _P(R128TrackResult), _P(_i32),
+                                               _P(R128AlbumResult), _P(_i32), _P(R128Dynamics), _P(R128Dynamics)]),
+    ("rg_r128_analyze_tracks_node", _int, [_vp, _P(C.c_char_p), _sz, _i32, _int, _P(R128TrackResult), _P(_i32), _P(R128Dynamics)]),
+    ("rg_r128_analyze_albums_node", _int, [_vp, _P(C.c_char_p), _sz, _P(_sz), _sz, _i32, _int, _P(R128TrackResult), _P(_i32),
+                                           _P(R128AlbumResult), _P(_i32), _P(R128Dynamics), _P(R128Dynamics)]),
 ]
 
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions

@@ -482,8 +482,12 @@ extern "C" int rg_find_peak_amplitude(rg_ctx *c, const char *path, rg_peak_resul
 // ---- EBU R 128 (include/mp3rgain_amd_r128.h): the same loaders, decoders and groups; the analysis is rg_r128.hip's ---------
 // one group of files -> their results; album: the first failing file in input order aborts (its index in *failed), else a
 // failing file fails alone
+// (kept_tr / kept_slot / kept_e, rg_r128_analyze_albums: the device descriptors of the files that were analysed, their indices in
+// the group, and their hop energies in a buffer that is the caller's to free)
 static int r128_files_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, int32_t track_index, int want_tp, bool album,
-                            rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out /* tracks only; may be nullptr */) {
+                            rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out /* tracks only; may be nullptr */,
+                            std::vector<RgR128TrackDev> *kept_tr = nullptr, std::vector<size_t> *kept_slot = nullptr,
+                            double **kept_e = nullptr) {
     paths += first;
     out += first;
     if (dyn_out) {
@@ -515,14 +519,18 @@ static int r128_files_group(rg_ctx *c, const char *const *paths, size_t first, s
     }
     if (slot.empty()) return RG_OK;
     std::vector<rg_r128_dynamics> dyn(dyn_out ? slot.size() : 0);
+    if (kept_tr) kept_tr->resize(slot.size());
     rc = run_good_files(c, in, slot, out, [&](const rg_track_desc *descs, size_t k, size_t arena_bytes, rg_r128_track_result *res) {
-        return rg_r128_run(c, descs, k, c->d_arena.p, arena_bytes, want_tp, album ? 1 : 0, res, nullptr, dyn_out ? dyn.data() : nullptr, nullptr);
+        return rg_r128_run(c, descs, k, c->d_arena.p, arena_bytes, want_tp, album ? 1 : 0, res, nullptr, dyn_out ? dyn.data() : nullptr, nullptr,
+                           kept_tr ? kept_tr->data() : nullptr, kept_e);
     });
     if (rc != RG_OK) {
         if (album) return rc;
+        if (kept_tr) kept_tr->clear();
         fail_batch(c, slot, first, rc, status_out + first);
         return RG_OK;
     }
+    if (kept_slot) *kept_slot = slot;
     for (size_t k = 0; k < slot.size() && dyn_out; ++k) dyn_out[slot[k]] = dyn[k];
     return RG_OK;
 }
@@ -582,4 +590,139 @@ extern "C" int rg_r128_analyze_album_dynamics(rg_ctx *c, const char *const *path
                                               rg_r128_dynamics *dyn_out, rg_r128_dynamics *album_dyn_out) {
     if (c && ((n && !dyn_out) || !album_dyn_out)) return rg_set_err(c, RG_ERR_INVALID_ARG, "null dynamics output");
     return r128_album(c, paths, n, track_index, want_true_peak, tracks_out, album_out, dyn_out, album_dyn_out);
+}
+
+// Many albums in one call: rg_r128_analyze_tracks' groups over the whole list, every group's hop energies kept on the device.
+// After each group the albums whose last file lies in the groups taken so far are gated in one album stage
+// (rg_r128_albums.hip); a group's energies are freed as soon as no unfinished album has tracks in them, so what is live is
+// the current group plus the groups the one straddling album spans.  Per album the first failing file in input order decides;
+// the good files of such an album keep their results (and, with dynamics, get theirs from the same stage).
+static int r128_albums_impl(rg_ctx *c, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                            int32_t track_index, int want_tp, rg_r128_track_result *tracks_out, int32_t *status_out,
+                            rg_r128_album_result *albums_out, int32_t *album_status_out, bool dynamics, rg_r128_dynamics *dyn_out,
+                            rg_r128_dynamics *albums_dyn_out, std::vector<char> &done, size_t *files_done,
+                            std::vector<std::pair<size_t, double *>> &bufs /* (end of the group, its energies) */) {
+    std::vector<std::pair<size_t, size_t>> groups;
+    file_groups(c, paths, n, &groups);
+    std::vector<RgR128TrackDev> kept(n);  // by file; valid where the file's status is RG_OK
+    size_t next_album = 0;                // the albums before it are finished
+    // albums [next_album, a_end): one stage over their files (the failed albums' good files after the last album's)
+    auto finish = [&](size_t a_end) -> int {
+        std::vector<RgR128TrackDev> tr;
+        std::vector<rg_r128_track_result> res;
+        std::vector<size_t> seg(1, 0), seg_album, file_of;
+        auto take = [&](size_t i) {
+            tr.push_back(kept[i]);
+            res.push_back(tracks_out[i]);
+            file_of.push_back(i);
+        };
+        for (size_t a = next_album; a < a_end; ++a) {
+            album_status_out[a] = RG_OK;
+            for (size_t i = album_first[a]; i < album_first[a + 1] && album_status_out[a] == RG_OK; ++i) album_status_out[a] = status_out[i];
+            if (album_status_out[a] != RG_OK) continue;
+            for (size_t i = album_first[a]; i < album_first[a + 1]; ++i) take(i);
+            seg.push_back(tr.size());
+            seg_album.push_back(a);
+        }
+        if (dynamics)
+            for (size_t a = next_album; a < a_end; ++a)
+                for (size_t i = album_first[a]; i < album_first[a + 1] && album_status_out[a] != RG_OK; ++i)
+                    if (status_out[i] == RG_OK) take(i);
+        const size_t k = seg_album.size();
+        std::vector<rg_r128_album_result> alb(k + 1);
+        std::vector<rg_r128_dynamics> dyn(tr.size() + 1), adyn(k + 1);
+        const int rc = rg_r128_albums_stage(c, tr.data(), res.data(), tr.size(), seg.data(), k, want_tp, alb.data(),
+                                            dynamics ? dyn.data() : nullptr, dynamics ? adyn.data() : nullptr, nullptr);
+        if (rc != RG_OK) return rc;
+        for (size_t q = 0; q < k; ++q) {
+            albums_out[seg_album[q]] = alb[q];
+            if (dynamics) albums_dyn_out[seg_album[q]] = adyn[q];
+        }
+        for (size_t j = 0; j < tr.size() && dynamics; ++j) dyn_out[file_of[j]] = dyn[j];
+        for (size_t a = next_album; a < a_end; ++a) done[a] = 1;
+        next_album = a_end;
+        return RG_OK;
+    };
+    for (const auto &g : groups) {
+        const size_t first = g.first, end = g.first + g.second;
+        std::vector<RgR128TrackDev> tr;
+        std::vector<size_t> slot;
+        double *e = nullptr;
+        int rc = r128_files_group(c, paths, first, g.second, track_index, want_tp, false, tracks_out, status_out, nullptr, &tr, &slot, &e);
+        if (e) bufs.push_back(std::make_pair(end, e));
+        if (rc != RG_OK) return rc;
+        for (size_t k = 0; k < tr.size(); ++k) kept[first + slot[k]] = tr[k];
+        size_t a_end = next_album;
+        while (a_end < n_albums && album_first[a_end + 1] <= end) ++a_end;
+        if (a_end > next_album) {
+            rc = finish(a_end);
+            if (rc != RG_OK) return rc;
+        }
+        *files_done = end;
+        const size_t live_from = next_album < n_albums ? album_first[next_album] : n;  // the first file of an unfinished album
+        while (!bufs.empty() && bufs.front().first <= live_from) {
+            (void)hipFree(bufs.front().second);
+            bufs.erase(bufs.begin());
+        }
+    }
+    if (next_album < n_albums) return finish(n_albums);  // (albums without files after the last group, or a call without files)
+    return RG_OK;
+}
+
+static int r128_albums(rg_ctx *c, const char *fn, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                       int32_t track_index, int want_tp, rg_r128_track_result *tracks_out, int32_t *status_out,
+                       rg_r128_album_result *albums_out, int32_t *album_status_out, bool dynamics, rg_r128_dynamics *dyn_out,
+                       rg_r128_dynamics *albums_dyn_out) {
+    if (!c) return RG_ERR_INVALID_ARG;
+    if ((n && (!paths || !tracks_out || !status_out || (dynamics && !dyn_out))) ||
+        (n_albums && (!albums_out || !album_status_out || (dynamics && !albums_dyn_out))))
+        return rg_set_err(c, RG_ERR_INVALID_ARG, "%s: null input or output array", fn);
+    std::string why;
+    if (rg_albums_check(album_first, n_albums, n, &why) != RG_OK) return rg_set_err(c, RG_ERR_INVALID_ARG, "%s: %s", fn, why.c_str());
+    c->file_errors.assign(n, std::string());
+    for (size_t a = 0; a < n_albums; ++a) {
+        memset(&albums_out[a], 0, sizeof albums_out[a]);
+        if (dynamics) memset(&albums_dyn_out[a], 0, sizeof albums_dyn_out[a]);
+    }
+    if (dynamics && n) memset(dyn_out, 0, n * sizeof *dyn_out);
+    std::vector<char> done(n_albums, 0);
+    size_t files_done = 0;
+    std::vector<std::pair<size_t, double *>> bufs;
+    int rc = rg_bind_device(c);
+    if (rc == RG_OK)
+        rc = r128_albums_impl(c, paths, n, album_first, n_albums, track_index, want_tp, tracks_out, status_out, albums_out,
+                              album_status_out, dynamics, dyn_out, albums_dyn_out, done, &files_done, bufs);
+    for (const auto &b : bufs) (void)hipFree(b.second);
+    if (rc != RG_OK) {  // the call itself failed (a device error): what it did not finish carries the call's code and text
+        const std::string text = c->err;
+        for (size_t i = files_done; i < n; ++i) {
+            memset(&tracks_out[i], 0, sizeof tracks_out[i]);
+            if (dynamics) memset(&dyn_out[i], 0, sizeof dyn_out[i]);
+            status_out[i] = rc;
+            c->file_errors[i] = text;
+        }
+        for (size_t a = 0; a < n_albums; ++a)
+            if (!done[a]) {
+                memset(&albums_out[a], 0, sizeof albums_out[a]);
+                if (dynamics) memset(&albums_dyn_out[a], 0, sizeof albums_dyn_out[a]);
+                album_status_out[a] = rc;
+            }
+        c->err = text;
+    }
+    return rc;
+}
+
+extern "C" int rg_r128_analyze_albums(rg_ctx *c, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                                      int32_t track_index, int want_true_peak, rg_r128_track_result *tracks_out, int32_t *status_out,
+                                      rg_r128_album_result *albums_out, int32_t *album_status_out) {
+    return r128_albums(c, "rg_r128_analyze_albums", paths, n, album_first, n_albums, track_index, want_true_peak, tracks_out, status_out,
+                       albums_out, album_status_out, false, nullptr, nullptr);
+}
+
+extern "C" int rg_r128_analyze_albums_dynamics(rg_ctx *c, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                                               int32_t track_index, int want_true_peak, rg_r128_track_result *tracks_out,
+                                               int32_t *status_out, rg_r128_album_result *albums_out, int32_t *album_status_out,
+                                               rg_r128_dynamics *dyn_out, rg_r128_dynamics *albums_dyn_out) {
+    return r128_albums(c, "rg_r128_analyze_albums_dynamics", paths, n, album_first, n_albums, track_index, want_true_peak, tracks_out,
+                       status_out, albums_out, album_status_out, true, dyn_out, albums_dyn_out);
 }

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/mp3rgain_amd_node.h"
+#include "../../include/mp3rgain_amd_r128.h"
 #include "rg_ctx.h"
 
 namespace {
@@ -404,6 +405,114 @@ extern "C" int rg_analyze_albums_node(rg_node *nd, const char *const *paths, siz
             memcpy(&peak, pack.data() + RG_HISTOGRAM_SIZE, sizeof peak);
             albums_out[a] = host_album_result(pack.data(), peak);
             album_status_out[a] = RG_OK;
+        }
+    });
+    return RG_OK;
+}
+
+// ---- EBU R 128 (include/mp3rgain_amd_r128.h) on the node: the dealing of the two functions above, the library's own
+// ---- contexts only (the backend table has no R 128 entries)
+extern "C" int rg_r128_analyze_tracks_node(rg_node *nd, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
+                                           rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out) {
+    if (!nd) return RG_ERR_INVALID_ARG;
+    if (!nd->builtin) return node_err(nd, RG_ERR_STATE, "rg_r128_analyze_tracks_node: a backend node has no R 128 entries");
+    if (n && (!paths || !out || !status_out)) return node_err(nd, RG_ERR_INVALID_ARG, "rg_r128_analyze_tracks_node: null input or output array");
+    const size_t D = nd->engines.size();
+    std::vector<std::vector<size_t>> shares;
+    deal(nd, paths, n, &shares);
+    nd->track_errors.assign(n, std::string());
+    on_every_device(D, [&](size_t d) {
+        const std::vector<size_t> &mine = shares[d];
+        if (mine.empty()) return;
+        rg_ctx *c = static_cast<rg_ctx *>(nd->engines[d]);
+        std::vector<const char *> p;
+        for (size_t i : mine) p.push_back(paths[i]);
+        std::vector<rg_r128_track_result> res(mine.size());
+        std::vector<rg_r128_dynamics> dyn(mine.size());
+        std::vector<int32_t> st(mine.size(), RG_OK);
+        const int rc = dyn_out ? rg_r128_analyze_tracks_dynamics(c, p.data(), p.size(), track_index, want_true_peak, res.data(), st.data(), dyn.data())
+                               : rg_r128_analyze_tracks(c, p.data(), p.size(), track_index, want_true_peak, res.data(), st.data());
+        for (size_t k = 0; k < mine.size(); ++k) {
+            const size_t i = mine[k];
+            if (rc != RG_OK) {  // the call itself failed (a device error): every file of the share carries it
+                memset(&out[i], 0, sizeof out[0]);
+                if (dyn_out) memset(&dyn_out[i], 0, sizeof dyn_out[0]);
+                status_out[i] = rc;
+                nd->track_errors[i] = rg_last_error(c);
+                continue;
+            }
+            out[i] = res[k];
+            if (dyn_out) dyn_out[i] = dyn[k];
+            status_out[i] = st[k];
+            if (st[k] != RG_OK) nd->track_errors[i] = rg_tracks_error(c, k);
+        }
+    });
+    return RG_OK;
+}
+
+extern "C" int rg_r128_analyze_albums_node(rg_node *nd, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,
+                                           int32_t track_index, int want_true_peak, rg_r128_track_result *tracks_out,
+                                           int32_t *status_out, rg_r128_album_result *albums_out, int32_t *album_status_out,
+                                           rg_r128_dynamics *dyn_out, rg_r128_dynamics *albums_dyn_out) {
+    if (!nd) return RG_ERR_INVALID_ARG;
+    if (!nd->builtin) return node_err(nd, RG_ERR_STATE, "rg_r128_analyze_albums_node: a backend node has no R 128 entries");
+    const bool dynamics = dyn_out || albums_dyn_out;
+    if ((n && (!paths || !tracks_out || !status_out || (dynamics && !dyn_out))) ||
+        (n_albums && (!albums_out || !album_status_out || (dynamics && !albums_dyn_out))))
+        return node_err(nd, RG_ERR_INVALID_ARG, "rg_r128_analyze_albums_node: null input or output array");
+    std::string why;
+    if (rg_albums_check(album_first, n_albums, n, &why) != RG_OK)
+        return node_err(nd, RG_ERR_INVALID_ARG, "rg_r128_analyze_albums_node: %s", why.c_str());
+    const size_t D = nd->engines.size();
+    std::vector<uint64_t> bytes(n_albums, 0);
+    for (size_t a = 0; a < n_albums; ++a)
+        for (size_t i = album_first[a]; i < album_first[a + 1]; ++i) {
+            struct stat st;
+            if (paths[i] && stat(paths[i], &st) == 0 && st.st_size > 0) bytes[a] += (uint64_t)st.st_size;
+        }
+    std::vector<uint32_t> album_owner(n_albums, 0);
+    rg_node_partition(bytes.data(), n_albums, D, album_owner.data());
+    nd->owner.assign(n, 0);
+    std::vector<std::vector<size_t>> mine(D);  // albums of each device, ascending
+    for (size_t a = 0; a < n_albums; ++a) {
+        mine[album_owner[a]].push_back(a);
+        for (size_t i = album_first[a]; i < album_first[a + 1]; ++i) nd->owner[i] = album_owner[a];
+    }
+    nd->track_errors.assign(n, std::string());
+    on_every_device(D, [&](size_t d) {
+        if (mine[d].empty()) return;
+        rg_ctx *c = static_cast<rg_ctx *>(nd->engines[d]);
+        std::vector<const char *> p;
+        std::vector<size_t> first(1, 0), files;
+        for (size_t a : mine[d]) {
+            for (size_t i = album_first[a]; i < album_first[a + 1]; ++i) {
+                p.push_back(paths[i]);
+                files.push_back(i);
+            }
+            first.push_back(p.size());
+        }
+        const size_t k_albums = mine[d].size();
+        std::vector<rg_r128_track_result> res(files.size() + 1);
+        std::vector<rg_r128_dynamics> dyn(files.size() + 1), adyn(k_albums);
+        std::vector<int32_t> st(files.size() + 1, RG_OK), ast(k_albums, RG_OK);
+        std::vector<rg_r128_album_result> alb(k_albums);
+        // (a call that fails still fills every record: what it had not finished carries its code and text)
+        if (dynamics)
+            (void)rg_r128_analyze_albums_dynamics(c, p.data(), p.size(), first.data(), k_albums, track_index, want_true_peak, res.data(),
+                                                  st.data(), alb.data(), ast.data(), dyn.data(), adyn.data());
+        else
+            (void)rg_r128_analyze_albums(c, p.data(), p.size(), first.data(), k_albums, track_index, want_true_peak, res.data(), st.data(),
+                                         alb.data(), ast.data());
+        for (size_t k = 0; k < files.size(); ++k) {
+            tracks_out[files[k]] = res[k];
+            if (dynamics) dyn_out[files[k]] = dyn[k];
+            status_out[files[k]] = st[k];
+            if (st[k] != RG_OK) nd->track_errors[files[k]] = rg_tracks_error(c, k);
+        }
+        for (size_t q = 0; q < k_albums; ++q) {
+            albums_out[mine[d][q]] = alb[q];
+            if (dynamics) albums_dyn_out[mine[d][q]] = adyn[q];
+            album_status_out[mine[d][q]] = ast[q];
         }
     });
     return RG_OK;

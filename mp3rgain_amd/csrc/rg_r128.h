@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/mp3rgain_amd_r128.h"
 
 #define RG_R128_TP_TAPS 49
@@ -39,9 +41,11 @@ struct rg_ctx;
 // device until rg_r128_album_end gates their union (call rg_r128_album_reset first).  dyn_out (without keep_for_album) and
 // dyn_out / album_dyn_out of rg_r128_album_end (every kept track, in input order): nullptr, or loudness range and maxima
 // are computed too (rg_r128_range.hip) after the launches of the plain call, which do not change; st_z_out goes with them.
+// tr_out: nullptr, or the tracks' device descriptors go there (rg_r128_albums_stage reads them); their hop energies are in
+// the context's own buffer until the next call, or, with e_out, in a buffer of their own that the caller frees (hipFree).
 int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_base, size_t pcm_bytes, int want_true_peak,
                 int keep_for_album, rg_r128_track_result *out, double *block_z_out, rg_r128_dynamics *dyn_out = nullptr,
-                double *st_z_out = nullptr);
+                double *st_z_out = nullptr, RgR128TrackDev *tr_out = nullptr, double **e_out = nullptr);
 void rg_r128_album_reset(rg_ctx *c);
 int rg_r128_album_end(rg_ctx *c, int want_true_peak, rg_r128_album_result *album_out, rg_r128_dynamics *dyn_out = nullptr,
                       rg_r128_dynamics *album_dyn_out = nullptr, double *st_z_out = nullptr);
@@ -53,3 +57,29 @@ int rg_r128_dynamics_run(rg_ctx *c, void **slot, int album_select, const RgR128T
                          size_t n, rg_r128_dynamics *out, rg_r128_dynamics *album_out, double *st_z_out);
 void rg_r128_dynamics_none(rg_r128_dynamics *d);  // the values of a track or an album without blocks
 void rg_r128_range_free(void *slot);
+void rg_r128_dynamics_nan(rg_r128_dynamics *d);   // the values of a track or an album that is not finite
+
+// Stage 1 and the per-track selection over n tracks, launched on the context's stream and not waited for: what they leave
+// on the device (in *slot's buffers, until the next call) and where every track's short-term blocks lie.
+struct RgR128RangeDev {
+    const double *st = nullptr;                  // every track's short-term blocks, track after track
+    const unsigned long long *max_bits = nullptr;  // [n][2]: momentary, short-term
+    const rg_r128_dynamics *dyn = nullptr;       // [n]
+    uint64_t total = 0;
+    std::vector<uint64_t> st_base;               // [n + 1]
+};
+int rg_r128_range_tracks(rg_ctx *c, void **slot, const RgR128TrackDev *tr, size_t n, RgR128RangeDev *dev);
+
+// rg_r128_albums.hip: the album stage of many albums at once.  tr / res: n tracks whose hop energies are on the device;
+// album a is tracks [first[a], first[a + 1]), first[n_albums] <= n (tracks past it belong to no album and get their own
+// dynamics only).  albums_dyn_out: nullptr, or loudness range and maxima of every track (dyn_out, may be nullptr) and every
+// album are computed too.  Empty albums get the record of rg_r128_analyze_album for n = 0.
+#define RG_R128A_ROUND 64  // wide albums whose selection state is on the device at once
+int rg_r128_albums_stage(rg_ctx *c, const RgR128TrackDev *tr, const rg_r128_track_result *res, size_t n, const size_t *first,
+                         size_t n_albums, int want_true_peak, rg_r128_album_result *albums_out, rg_r128_dynamics *dyn_out,
+                         rg_r128_dynamics *albums_dyn_out, double *st_z_out);
+// the context's album selection mode and the slot of its range buffers (rg_r128.hip owns both)
+int rg_r128_album_select(rg_ctx *c);
+void **rg_r128_range_slot(rg_ctx *c);
+void **rg_r128_albums_slot(rg_ctx *c);  // the stage's device buffers between calls
+void rg_r128_albums_free(void *slot);

@@ -10,6 +10,7 @@
 
 #include "rg_ctx.h"
 #include "rg_r128.h"
+#include "rg_r128_inl.h"
 
 namespace {
 
@@ -320,39 +321,6 @@ rg_r128_truepeak_kernel(const RgR128TrackDev *__restrict__ tracks, const uint32_
 // tracks listed in album_list, in list order).  Block values from hop energies in a fixed order, both gates, the logarithm.
 // Every thread sums its blocks in ascending order and the workgroup folds the 256 partial sums in a fixed tree: the same
 // input gives the same bits on every run.
-namespace {
-
-__device__ __forceinline__ double r128_block_z(const RgR128TrackDev &T, const uint32_t b) {
-    const double *e0 = T.e + b;
-    double s;
-    if (T.nch >= 2) {
-        const double *e1 = e0 + T.H;
-        s = (((e0[0] + e1[0]) + (e0[1] + e1[1])) + (e0[2] + e1[2])) + (e0[3] + e1[3]);
-    } else {
-        s = ((e0[0] + e0[1]) + e0[2]) + e0[3];
-    }
-    return s / (4.0 * (double)T.hop);
-}
-
-__device__ __forceinline__ void r128_fold(double *sh_sum, uint32_t *sh_cnt, double &sum, uint32_t &cnt) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh_sum[tid] = sum;
-    sh_cnt[tid] = cnt;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            sh_sum[tid] += sh_sum[tid + s];
-            sh_cnt[tid] += sh_cnt[tid + s];
-        }
-        __syncthreads();
-    }
-    sum = sh_sum[0];
-    cnt = sh_cnt[0];
-}
-
-}  // namespace
-
 __global__ void __launch_bounds__(256)
 rg_r128_gate_kernel(const RgR128TrackDev *__restrict__ tracks, const uint32_t track_blocks, const uint32_t *__restrict__ album_list,
                     const uint32_t n_album, const double abs_gate, const uint32_t *__restrict__ peak_bits,
@@ -429,6 +397,7 @@ struct R128State {
     uint32_t tune_S = 0;
     int tune_album_select = 0;
     void *range = nullptr;  // rg_r128_range.hip's buffers
+    void *albums = nullptr;  // rg_r128_albums.hip's
     DevBuf<unsigned char> d_desc;
     DevBuf<uint32_t> d_words;  // [sample peak | true peak | flags] x n
     DevBuf<rg_r128_track_result> d_res;
@@ -453,6 +422,7 @@ R128State &state(rg_ctx *c) {
             R128State *s = static_cast<R128State *>(p);
             s->drop_album();
             rg_r128_range_free(s->range);
+            rg_r128_albums_free(s->albums);
             s->d_desc.release();
             s->d_words.release();
             s->d_res.release();
@@ -530,8 +500,14 @@ extern "C" int rg_r128_set_tuning(rg_ctx *c, int key, int64_t value) {
 
 void rg_r128_album_reset(rg_ctx *c) { state(c).drop_album(); }
 
+int rg_r128_album_select(rg_ctx *c) { return state(c).tune_album_select; }
+void **rg_r128_range_slot(rg_ctx *c) { return &state(c).range; }
+void **rg_r128_albums_slot(rg_ctx *c) { return &state(c).albums; }
+
 int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_base, size_t pcm_bytes, int want_tp, int keep,
-                rg_r128_track_result *out, double *block_z_out, rg_r128_dynamics *dyn_out, double *st_z_out) {
+                rg_r128_track_result *out, double *block_z_out, rg_r128_dynamics *dyn_out, double *st_z_out, RgR128TrackDev *tr_out,
+                double **e_out) {
+    if (e_out) *e_out = nullptr;
     if (!c) return RG_ERR_INVALID_ARG;
     if (n && (!tracks || !out || !d_base)) return rg_set_err(c, RG_ERR_INVALID_ARG, "null argument");
     int rc = r128_validate(c, tracks, n, pcm_bytes);
@@ -578,6 +554,9 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
     if (keep) {
         RG_HIP(c, hipMalloc((void **)&d_e, (total_e ? total_e : 1) * sizeof(double)));
         st.kept_e.push_back(d_e);
+    } else if (e_out) {  // (an error below leaves it to the caller, which frees what it was given)
+        RG_HIP(c, hipMalloc((void **)&d_e, (total_e ? total_e : 1) * sizeof(double)));
+        *e_out = d_e;
     } else {
         RG_HIP(c, st.d_e.reserve(total_e ? total_e : 1));
         d_e = st.d_e.p;
@@ -656,6 +635,7 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
     RG_HIP(c, hipMemcpyAsync(out, st.d_res.p, n * sizeof(rg_r128_track_result), hipMemcpyDeviceToHost, s));
     if (block_z_out && total_z) RG_HIP(c, hipMemcpyAsync(block_z_out, st.d_z.p, total_z * sizeof(double), hipMemcpyDeviceToHost, s));
     RG_HIP(c, hipStreamSynchronize(s));
+    if (tr_out) std::copy(tr.begin(), tr.end(), tr_out);
     if (keep)
         for (size_t i = 0; i < n; ++i) {
             st.kept.push_back(tr[i]);

@@ -22,187 +22,9 @@
 
 #include "rg_ctx.h"
 #include "rg_r128.h"
+#include "rg_r128_inl.h"
 
 #define RG_R128R_CHUNK 1024
-#define RG_R128R_ST_HOPS 30
-#define RG_R128R_BINS 4096      // 12-bit digit: two histograms are 32 KiB of LDS
-#define RG_R128R_PASSES 6       // 5 x 12 bits + 4 bits
-#define RG_R128R_WIDE 256       // workgroups of a wide album pass
-#define RG_R128R_WIDE_FROM 16384u  // measured: one workgroup is ahead at 7 k blocks, level at 18 k, 0.4 ms behind at 66 k
-
-struct RgR128RangeTrack {
-    const double *e;     // hop energies [nch][H]
-    uint64_t st_base;    // first short-term block of the track in the block array
-    uint32_t chunk_base; // first workgroup of the track in stage 1
-    uint32_t H, nch, hop, st_count, pad;
-};
-
-struct RgR128RangeSel {  // the state of a wide album selection, on the device
-    double thr;
-    uint64_t prefix[2], mask;
-    uint32_t rank[2];
-    uint32_t n, pad;
-};
-
-namespace {
-
-__device__ __forceinline__ unsigned long long r128r_umax(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
-
-__device__ __forceinline__ int r128r_shift(const int pass) { return pass < RG_R128R_PASSES - 1 ? 52 - 12 * pass : 0; }
-__device__ __forceinline__ int r128r_width(const int pass) { return pass < RG_R128R_PASSES - 1 ? 12 : 4; }
-
-// sum and count over the workgroup, in a fixed tree
-__device__ __forceinline__ void r128r_fold(double *sh_sum, uint32_t *sh_cnt, double &sum, uint32_t &cnt) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh_sum[tid] = sum;
-    sh_cnt[tid] = cnt;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            sh_sum[tid] += sh_sum[tid + s];
-            sh_cnt[tid] += sh_cnt[tid + s];
-        }
-        __syncthreads();
-    }
-    sum = sh_sum[0];
-    cnt = sh_cnt[0];
-}
-
-// hist: RG_R128R_BINS counters in LDS.  The bin that holds the element of rank `rank` (0-based, below the counters' sum) and
-// its rank within that bin go to pick[0], pick[1]; every thread may read them after the call.
-__device__ __forceinline__ void r128r_find_bin(const uint32_t *hist, uint32_t *scan, uint32_t *pick, const uint32_t rank) {
-    constexpr int PER = RG_R128R_BINS / 256;
-    const int tid = threadIdx.x;
-    uint32_t t = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) t += hist[tid * PER + k];
-    __syncthreads();  // the last call's readers of pick are through
-    scan[tid] = t;
-    if (tid == 0) pick[0] = pick[1] = 0;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const uint32_t v = tid >= d ? scan[tid - d] : 0u;
-        __syncthreads();
-        scan[tid] += v;
-        __syncthreads();
-    }
-    const uint32_t incl = scan[tid], excl = incl - t;
-    if (rank >= excl && rank < incl) {  // one thread at most
-        uint32_t r = rank - excl;
-        for (int k = 0; k < PER; ++k) {
-            const uint32_t cnt = hist[tid * PER + k];
-            if (r < cnt) {
-                pick[0] = (uint32_t)(tid * PER + k);
-                pick[1] = r;
-                break;
-            }
-            r -= cnt;
-        }
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void r128r_ranks(const uint32_t n, uint32_t *rank) {
-    rank[0] = (uint32_t)((10ull * (n - 1u) + 50ull) / 100ull);
-    rank[1] = (uint32_t)((95ull * (n - 1u) + 50ull) / 100ull);
-}
-
-// the state of a selection before its first counting pass
-__device__ __forceinline__ void r128r_start(RgR128RangeSel &s, const double thr, const uint32_t n) {
-    s.thr = thr;
-    s.prefix[0] = s.prefix[1] = s.mask = 0;
-    s.rank[0] = s.rank[1] = 0;
-    s.n = n;
-    s.pad = 0;
-    if (n) r128r_ranks(n, s.rank);
-}
-
-// One value for a histogram.  The values of a wave are neighbours in time and often share a digit (the upper passes see one
-// or two exponents): the first two distinct digits of a wave are added once per wave, what is left lane by lane.  The wave
-// is converged here (the callers' loops are uniform).
-__device__ __forceinline__ void r128r_count(uint32_t *hist, const uint32_t digit, bool pred) {
-    unsigned long long todo = __ballot(pred);
-    for (int it = 0; it < 2 && todo; ++it) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t d = __shfl(digit, leader, 64);
-        const bool mine = pred && digit == d;
-        const unsigned long long m = __ballot(mine);
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&hist[d], (uint32_t)__popcll(m));
-        pred = pred && !mine;
-        todo &= ~m;
-    }
-    if (pred) atomicAdd(&hist[digit], 1u);
-}
-
-// Counting pass `pass` over v[i0, i1): the digit of every value both gates keep and whose upper bits are a percentile's
-// prefix so far, into that percentile's histogram (hist, hist + BINS).  While both percentiles share their prefix the two
-// histograms would be equal: only the first is counted then, and r128r_advance reads it for both.
-__device__ __forceinline__ void r128r_count_slice(uint32_t *hist, const double *__restrict__ v, const uint64_t i0, const uint64_t i1,
-                                                  const double abs_gate, const RgR128RangeSel &s, const int pass) {
-    const int shift = r128r_shift(pass), width = r128r_width(pass);
-    const bool same = s.prefix[0] == s.prefix[1];
-    for (uint64_t base = i0; base < i1; base += 256) {
-        const uint64_t i = base + threadIdx.x;
-        const double x = i < i1 ? v[i] : 0.0;
-        const bool kept = i < i1 && x >= abs_gate && x >= s.thr;
-        const uint64_t bits = (uint64_t)__double_as_longlong(x);
-        const uint32_t digit = (uint32_t)(bits >> shift) & ((1u << width) - 1u);
-        r128r_count(hist, digit, kept && (bits & s.mask) == s.prefix[0]);
-        if (!same) r128r_count(hist + RG_R128R_BINS, digit, kept && (bits & s.mask) == s.prefix[1]);
-    }
-}
-
-// after counting pass `pass`: the digit of both percentiles, their ranks within it
-__device__ __forceinline__ void r128r_advance(RgR128RangeSel &s, const uint32_t *hist, uint32_t *scan, uint32_t *pick, const int pass) {
-    const int shift = r128r_shift(pass), width = r128r_width(pass);
-    const bool same = s.prefix[0] == s.prefix[1];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        r128r_find_bin(hist + (q && !same ? RG_R128R_BINS : 0), scan, pick, s.rank[q]);
-        s.prefix[q] |= (uint64_t)pick[0] << shift;
-        s.rank[q] = pick[1];
-    }
-    s.mask |= (uint64_t)((1u << width) - 1u) << shift;
-}
-
-__device__ __forceinline__ double r128r_lufs(const double ms) { return ms > 0.0 ? -0.691 + 10.0 * log10(ms) : -__builtin_inf(); }
-
-__device__ __forceinline__ void r128r_finish(rg_r128_dynamics &d, const uint32_t total, const uint32_t n, const uint64_t low_bits,
-                                             const uint64_t high_bits, const unsigned long long m_bits, const unsigned long long s_bits) {
-    const double low = __longlong_as_double((long long)low_bits), high = __longlong_as_double((long long)high_bits);
-    d.loudness_range_lu = n ? 10.0 * log10(high / low) : 0.0;
-    d.range_low_lufs = n ? r128r_lufs(low) : -__builtin_inf();
-    d.range_high_lufs = n ? r128r_lufs(high) : -__builtin_inf();
-    d.max_momentary_lufs = r128r_lufs(__longlong_as_double((long long)m_bits));
-    d.max_short_term_lufs = r128r_lufs(__longlong_as_double((long long)s_bits));
-    d.st_blocks = total;
-    d.st_blocks_gated = n;
-}
-
-// max over the tracks' maxima, by the whole workgroup; the result is in sh_max[0] (momentary) and sh_max[1] (short-term)
-__device__ __forceinline__ void r128r_album_maxima(const unsigned long long *__restrict__ max_bits, const uint32_t n_tracks,
-                                                   unsigned long long *sh_max /* 512 */) {
-    const int tid = threadIdx.x;
-    unsigned long long m = 0, s = 0;
-    for (uint32_t i = tid; i < n_tracks; i += 256) {
-        m = r128r_umax(m, max_bits[2 * i]);
-        s = r128r_umax(s, max_bits[2 * i + 1]);
-    }
-    __syncthreads();
-    sh_max[2 * tid] = m;
-    sh_max[2 * tid + 1] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (tid < k) {
-            sh_max[2 * tid] = r128r_umax(sh_max[2 * tid], sh_max[2 * (tid + k)]);
-            sh_max[2 * tid + 1] = r128r_umax(sh_max[2 * tid + 1], sh_max[2 * (tid + k) + 1]);
-        }
-        __syncthreads();
-    }
-}
-
-}  // namespace
 
 // =================================================================================================
 // Stage 1: short-term blocks and the two maxima.
@@ -424,14 +246,13 @@ struct RangeState {
     DevBuf<unsigned char> d_wide;
 };
 
-constexpr size_t kWideSel = 0, kWidePsum = 512, kWidePcnt = kWidePsum + 2 * RG_R128R_WIDE * sizeof(double),
-                 kWideHist = kWidePcnt + 2 * RG_R128R_WIDE * sizeof(uint32_t),
-                 kWideBytes = kWideHist + (size_t)RG_R128R_PASSES * 2 * RG_R128R_BINS * sizeof(uint32_t);
-static_assert((RG_R128R_PASSES + 1) * sizeof(RgR128RangeSel) <= kWidePsum, "the selection states fit their slot");
-
 double r128r_abs_gate() { return pow(10.0, (-70.0 + 0.691) / 10.0); }
 
 }  // namespace
+
+extern "C" int rg_r128_album_select_form(int album_select, uint64_t st_blocks) {
+    return album_select == 2 || (album_select == 0 && st_blocks >= RG_R128R_WIDE_FROM) ? 2 : 1;
+}
 
 void rg_r128_range_free(void *p) {
     RangeState *s = static_cast<RangeState *>(p);
@@ -449,15 +270,14 @@ void rg_r128_dynamics_none(rg_r128_dynamics *d) {
     d->range_low_lufs = d->range_high_lufs = d->max_momentary_lufs = d->max_short_term_lufs = -INFINITY;
 }
 
-int rg_r128_dynamics_run(rg_ctx *c, void **slot, int album_select, const RgR128TrackDev *tr, const rg_r128_track_result *res,
-                         size_t n, rg_r128_dynamics *out, rg_r128_dynamics *album_out, double *st_z_out) {
-    if (album_out) rg_r128_dynamics_none(album_out);
-    if (n == 0) return RG_OK;
-    if (!*slot) *slot = new RangeState();
-    RangeState &st = *static_cast<RangeState *>(*slot);
-    hipStream_t s = c->slot().stream;
+namespace {
 
-    std::vector<RgR128RangeTrack> list(n);
+// Stage 1 over n tracks: the track list and the block array's layout, the buffers, the launch.  *total_out: short-term blocks.
+int range_blocks(rg_ctx *c, RangeState &st, const RgR128TrackDev *tr, size_t n, size_t dyn_slots, uint64_t *total_out,
+                 std::vector<RgR128RangeTrack> *list_out) {
+    hipStream_t s = c->slot().stream;
+    std::vector<RgR128RangeTrack> &list = *list_out;
+    list.resize(n);
     uint64_t total = 0, chunks = 0;
     for (size_t i = 0; i < n; ++i) {
         RgR128RangeTrack &o = list[i];
@@ -473,19 +293,63 @@ int rg_r128_dynamics_run(rg_ctx *c, void **slot, int album_select, const RgR128T
         chunks += o.H > 3u ? (o.H - 3u + RG_R128R_CHUNK - 1) / RG_R128R_CHUNK : 0u;
         if (total > 0x7FFFFFFFull || chunks > 0x7FFFFFFFull) return rg_set_err(c, RG_ERR_INVALID_ARG, "batch too long for the loudness range");
     }
-    const bool wide = album_out && (album_select == 2 || (album_select == 0 && total >= RG_R128R_WIDE_FROM));
     RG_HIP(c, st.d_tr.reserve(n));
     RG_HIP(c, st.d_st.reserve(total ? total : 1));
     RG_HIP(c, st.d_max.reserve(2 * n));
-    RG_HIP(c, st.d_dyn.reserve(n + 1));
+    RG_HIP(c, st.d_dyn.reserve(dyn_slots));
     RG_HIP(c, hipMemcpyAsync(st.d_tr.p, list.data(), n * sizeof(RgR128RangeTrack), hipMemcpyHostToDevice, s));
     RG_HIP(c, hipMemsetAsync(st.d_max.p, 0, 2 * n * sizeof(unsigned long long), s));
-    const double gate = r128r_abs_gate();
     if (chunks) {
         hipLaunchKernelGGL(rg_r128r_blocks_kernel, dim3((uint32_t)chunks), dim3(256), 0, s, (const RgR128RangeTrack *)st.d_tr.p,
                            (uint32_t)n, st.d_st.p, st.d_max.p);
         RG_HIP(c, hipGetLastError());
     }
+    *total_out = total;
+    return RG_OK;
+}
+
+}  // namespace
+
+int rg_r128_range_tracks(rg_ctx *c, void **slot, const RgR128TrackDev *tr, size_t n, RgR128RangeDev *dev) {
+    if (!*slot) *slot = new RangeState();
+    RangeState &st = *static_cast<RangeState *>(*slot);
+    hipStream_t s = c->slot().stream;
+    std::vector<RgR128RangeTrack> list;
+    uint64_t total = 0;
+    const int rc = range_blocks(c, st, tr, n, n, &total, &list);
+    if (rc != RG_OK) return rc;
+    hipLaunchKernelGGL(rg_r128r_select_kernel, dim3((uint32_t)n), dim3(256), 0, s, (const RgR128RangeTrack *)st.d_tr.p, (uint32_t)n,
+                       (const double *)st.d_st.p, (uint32_t)total, r128r_abs_gate(), (const unsigned long long *)st.d_max.p, st.d_dyn.p);
+    RG_HIP(c, hipGetLastError());
+    dev->st = st.d_st.p;
+    dev->max_bits = st.d_max.p;
+    dev->dyn = st.d_dyn.p;
+    dev->total = total;
+    dev->st_base.resize(n + 1);
+    for (size_t i = 0; i < n; ++i) dev->st_base[i] = list[i].st_base;
+    dev->st_base[n] = total;
+    return RG_OK;
+}
+
+void rg_r128_dynamics_nan(rg_r128_dynamics *d) {
+    d->loudness_range_lu = d->range_low_lufs = d->range_high_lufs = d->max_momentary_lufs = d->max_short_term_lufs = NAN;
+    d->st_blocks_gated = 0;
+}
+
+int rg_r128_dynamics_run(rg_ctx *c, void **slot, int album_select, const RgR128TrackDev *tr, const rg_r128_track_result *res,
+                         size_t n, rg_r128_dynamics *out, rg_r128_dynamics *album_out, double *st_z_out) {
+    if (album_out) rg_r128_dynamics_none(album_out);
+    if (n == 0) return RG_OK;
+    if (!*slot) *slot = new RangeState();
+    RangeState &st = *static_cast<RangeState *>(*slot);
+    hipStream_t s = c->slot().stream;
+
+    std::vector<RgR128RangeTrack> list;
+    uint64_t total = 0;
+    const int rc = range_blocks(c, st, tr, n, n + 1, &total, &list);
+    if (rc != RG_OK) return rc;
+    const bool wide = album_out && rg_r128_album_select_form(album_select, total) == 2;
+    const double gate = r128r_abs_gate();
     hipLaunchKernelGGL(rg_r128r_select_kernel, dim3((uint32_t)n + (album_out && !wide ? 1u : 0u)), dim3(256), 0, s,
                        (const RgR128RangeTrack *)st.d_tr.p, (uint32_t)n, (const double *)st.d_st.p, (uint32_t)total, gate,
                        (const unsigned long long *)st.d_max.p, st.d_dyn.p);
@@ -517,19 +381,13 @@ int rg_r128_dynamics_run(rg_ctx *c, void **slot, int album_select, const RgR128T
     for (size_t i = 0; i < n; ++i) {
         if (res[i].flags & RG_TRACK_FLAG_NONFINITE) {
             bad = true;
-            rg_r128_dynamics &d = host[i];
-            d.loudness_range_lu = d.range_low_lufs = d.range_high_lufs = d.max_momentary_lufs = d.max_short_term_lufs = NAN;
-            d.st_blocks_gated = 0;
+            rg_r128_dynamics_nan(&host[i]);
         }
         if (out) out[i] = host[i];
     }
     if (album_out) {
         *album_out = host[n];
-        if (bad) {
-            album_out->loudness_range_lu = album_out->range_low_lufs = album_out->range_high_lufs = NAN;
-            album_out->max_momentary_lufs = album_out->max_short_term_lufs = NAN;
-            album_out->st_blocks_gated = 0;
-        }
+        if (bad) rg_r128_dynamics_nan(album_out);
     }
     return RG_OK;
 }

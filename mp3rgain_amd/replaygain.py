@@ -427,21 +427,81 @@ class Analyzer:
                 ReplayGainError(int(status[i]), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace")) for i in range(n)]
 
     def analyze_album_files_r128(self, files, true_peak: bool = False, track_index: Optional[int] = None,
-                                 dynamics: bool = False) -> R128AlbumResult:
+                                 dynamics: bool = False, timing: Optional[dict] = None) -> R128AlbumResult:
+        """`timing`: as analyze_album_files."""
         n = len(files)
         paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
         out = (_capi.R128TrackResult * max(1, n))()
         alb = _capi.R128AlbumResult()
         ti = -1 if track_index is None else int(track_index)
         dyn = adyn = None
+        t0 = time.perf_counter()
         if dynamics:
             dyn = (_capi.R128Dynamics * max(1, n))()
             adyn = _capi.R128Dynamics()
-            self._check(self._lib.rg_r128_analyze_album_dynamics(self._ctx, paths, n, ti, int(true_peak), out, C.byref(alb), dyn,
-                                                                 C.byref(adyn)))
+            rc = self._lib.rg_r128_analyze_album_dynamics(self._ctx, paths, n, ti, int(true_peak), out, C.byref(alb), dyn, C.byref(adyn))
         else:
-            self._check(self._lib.rg_r128_analyze_album(self._ctx, paths, n, ti, int(true_peak), out, C.byref(alb)))
+            rc = self._lib.rg_r128_analyze_album(self._ctx, paths, n, ti, int(true_peak), out, C.byref(alb))
+        if timing is not None:
+            timing["c_call_seconds"] = time.perf_counter() - t0
+        self._check(rc)
         return _to_r128_album([_to_r128(out[i], AudioFileType.Mp3, dyn[i] if dyn is not None else None) for i in range(n)], alb, adyn)
+
+    def analyze_albums_r128(self, albums, true_peak: bool = False, dynamics: bool = False, return_blocks: bool = False,
+                            return_short_term: bool = False):
+        """analyze_album_r128 for every album of `albums` (a sequence of sequences of PcmTrack) as ONE call
+        (rg_r128_analyze_albums_pcm[_dynamics]): one pass over all tracks, every album gated on the device in the same
+        launches.  -> a list of R128AlbumResult, each bit for bit what analyze_album_r128 gives on that album's tracks;
+        return_blocks / return_short_term: also, per album, the lists analyze_album_r128 returns."""
+        if return_short_term and not dynamics:
+            raise ValueError("return_short_term needs dynamics=True")
+        tracks = [t for a in albums for t in a]
+        first = [0]
+        for a in albums:
+            first.append(first[-1] + len(a))
+        n, n_albums = len(tracks), len(albums)
+        arena, descs = pack_tracks(tracks)
+        album_first = (C.c_size_t * (n_albums + 1))(*first)
+        out = (_capi.R128TrackResult * max(1, n))()
+        alb = (_capi.R128AlbumResult * max(1, n_albums))()
+        counts, z = self._r128_blocks(tracks) if return_blocks else (None, None)
+        zp = z.ctypes.data if z is not None else None
+        dyn = adyn = None
+        if dynamics:
+            dyn = (_capi.R128Dynamics * max(1, n))()
+            adyn = (_capi.R128Dynamics * max(1, n_albums))()
+            st_counts, st = self._r128_blocks(tracks, True) if return_short_term else (None, None)
+            self._check(self._lib.rg_r128_analyze_albums_pcm_dynamics(self._ctx, descs, n, album_first, n_albums, arena.ctypes.data,
+                                                                      arena.nbytes, 0, int(true_peak), out, alb, zp, dyn, adyn,
+                                                                      st.ctypes.data if st is not None else None))
+        else:
+            self._check(self._lib.rg_r128_analyze_albums_pcm(self._ctx, descs, n, album_first, n_albums, arena.ctypes.data, arena.nbytes,
+                                                             0, int(true_peak), out, alb, zp))
+        res = [_to_r128_album([_to_r128(out[i], tracks[i].file_type, dyn[i] if dyn is not None else None)
+                               for i in range(first[a], first[a + 1])], alb[a], adyn[a] if adyn is not None else None)
+               for a in range(n_albums)]
+        extra = []
+        if return_blocks:
+            zs = _split_blocks(z, counts)
+            extra.append([zs[first[a]:first[a + 1]] for a in range(n_albums)])
+        if return_short_term:
+            ss = _split_blocks(st, st_counts)
+            extra.append([ss[first[a]:first[a + 1]] for a in range(n_albums)])
+        return (res, *extra) if extra else res
+
+    def analyze_albums_files_r128(self, albums, true_peak: bool = False, track_index: Optional[int] = None,
+                                  dynamics: bool = False, timing: Optional[dict] = None) -> list:
+        """analyze_album_files_r128 for every album of `albums` (a sequence of file sequences) as ONE call
+        (rg_r128_analyze_albums[_dynamics]).  -> per album an R128AlbumResult, or the ReplayGainError
+        analyze_album_files_r128 would have raised for it.  `timing`: as analyze_album_files."""
+        args = _albums_args_r128(albums, track_index, true_peak, dynamics)
+        fn = self._lib.rg_r128_analyze_albums_dynamics if dynamics else self._lib.rg_r128_analyze_albums
+        t0 = time.perf_counter()
+        rc = fn(self._ctx, *args[:-1])
+        if timing is not None:
+            timing["c_call_seconds"] = time.perf_counter() - t0
+        self._check(rc)
+        return _albums_results_r128(args, lambda i: self._lib.rg_tracks_error(self._ctx, i))
 
     def find_peak_amplitude(self, track: PcmTrack) -> PeakAmplitudeResult:
         """find_peak_amplitude's scan over ALL channels (src/replaygain.rs:1210-1249)."""
@@ -802,6 +862,26 @@ class Node:
                 res.append(ReplayGainError(int(status[i]), self._lib.rg_node_tracks_error(self._node, i).decode("utf-8", "replace")))
         return res
 
+    def analyze_albums_files_r128(self, albums, true_peak: bool = False, track_index: Optional[int] = None,
+                                  dynamics: bool = False) -> list:
+        """Analyzer.analyze_albums_files_r128 over all devices: whole albums dealt out by their files' bytes, one call per device."""
+        args = _albums_args_r128(albums, track_index, true_peak, dynamics)
+        rest = args[:-1] if dynamics else args[:-1] + (None, None)
+        self._check(self._lib.rg_r128_analyze_albums_node(self._node, *rest))
+        return _albums_results_r128(args, lambda i: self._lib.rg_node_tracks_error(self._node, i))
+
+    def analyze_track_files_r128(self, files, true_peak: bool = False, track_index: Optional[int] = None, dynamics: bool = False) -> list:
+        """Analyzer.analyze_track_files_r128, the files dealt out over all devices; per file a result or its error."""
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (_capi.R128TrackResult * max(1, n))()
+        status = (C.c_int32 * max(1, n))()
+        dyn = (_capi.R128Dynamics * max(1, n))() if dynamics else None
+        self._check(self._lib.rg_r128_analyze_tracks_node(self._node, paths, n, -1 if track_index is None else int(track_index),
+                                                          int(true_peak), out, status, dyn))
+        return [_to_r128(out[i], AudioFileType.Mp3, dyn[i] if dyn is not None else None) if status[i] == 0 else
+                ReplayGainError(int(status[i]), self._lib.rg_node_tracks_error(self._node, i).decode("utf-8", "replace")) for i in range(n)]
+
     def analyze_track_file(self, file_path, track_index: Optional[int] = None) -> ReplayGainResult:
         """analyze_track_with_index (src/replaygain.rs:935-941) on the node's first device."""
         ctx = self._lib.rg_node_ctx(self._node, 0)
@@ -870,6 +950,33 @@ def _albums_results(args, file_error) -> list:
             continue
         res.append(AlbumGainResult([_to_result(out[i], out[i].file_type) for i in files], alb[a].album_loudness_db,
                                    alb[a].album_gain_db, alb[a].album_peak))
+    return res
+
+
+def _albums_args_r128(albums, track_index: Optional[int], true_peak: bool, dynamics: bool):
+    """rg_r128_analyze_albums[_dynamics]' arguments after the context / node, plus the album sizes."""
+    paths, n, album_first, n_albums, ti, _, status, _, alb_status, first = _albums_args(albums, track_index)
+    out = (_capi.R128TrackResult * max(1, n))()
+    alb = (_capi.R128AlbumResult * max(1, n_albums))()
+    args = (paths, n, album_first, n_albums, ti, int(true_peak), out, status, alb, alb_status)
+    if dynamics:
+        args += ((_capi.R128Dynamics * max(1, n))(), (_capi.R128Dynamics * max(1, n_albums))())
+    return args + (first,)
+
+
+def _albums_results_r128(args, file_error) -> list:
+    n_albums, out, status, alb, alb_status, first = args[3], args[6], args[7], args[8], args[9], args[-1]
+    dyn, adyn = (args[10], args[11]) if len(args) == 13 else (None, None)
+    res = []
+    for a in range(n_albums):
+        files = range(first[a], first[a + 1])
+        if alb_status[a] != 0:
+            bad = next((i for i in files if status[i] != 0), None)
+            text = file_error(bad).decode("utf-8", "replace") if bad is not None else ""
+            res.append(ReplayGainError(int(alb_status[a]), text))
+            continue
+        res.append(_to_r128_album([_to_r128(out[i], AudioFileType.Mp3, dyn[i] if dyn is not None else None) for i in files], alb[a],
+                                  adyn[a] if adyn is not None else None))
     return res
 
 
