@@ -85,7 +85,9 @@ typedef struct rg_track_result {
     double peak;
     uint32_t sample_rate;
     int32_t gain_steps;
-    uint32_t windows; /* number of 50 ms windows that landed in the histogram */
+    uint32_t windows; /* number of 50 ms windows that landed in the histogram: the sum of its bins, which the percentile takes
+                         as a u64; this field keeps the low 32 bits (a sum of 2^32 or more needs bins that a fold of packs
+                         supplied, rg_album_reduce_gathered, or 6.8 years of audio) */
     uint32_t file_type;
     uint32_t flags;   /* RG_TRACK_FLAG_* */
     uint32_t reserved;
@@ -105,7 +107,7 @@ typedef struct rg_album_result {
     double album_gain_db;
     double album_peak;
     int32_t album_gain_steps;
-    uint32_t windows;
+    uint32_t windows; /* as rg_track_result.windows, over the album histogram: the low 32 bits of the u64 sum of its bins */
 } rg_album_result;
 
 /* PeakAmplitudeResult, src/replaygain.rs:1125-1132 */
