@@ -4,8 +4,9 @@
  * descriptors, status codes, loaders and device decoders; nothing of that path changes (RG_ABI_VERSION stays).
  *
  * The algorithm, as this library and its checker (tests/r128ref.py) both implement it:
- *  - channels 0 and 1 of a track only, each with weight 1.0 (one channel = BS.1770 mono, not "dual mono"); samples are
- *    normalised to full scale 1.0 (F32 as is, S16 / 32768, S32 / 2^31);
+ *  - channels 0 and 1 of a track only, each with weight 1.0 (one channel = BS.1770 mono, not "dual mono"), unless the
+ *    track is weighted (channel weights, below); samples are normalised to full scale 1.0 (F32 as is, S16 / 32768,
+ *    S32 / 2^31);
  *  - K-weighting: two biquads in f64 whose coefficients are derived per rate, in long double, from the analogue prototypes
  *    (rg_r128_design_info), any rate from 8000 to 384000 Hz;
  *  - hop = (rate + 5) / 10 frames; hop energy e[h] = sum over the channels of the sum of squared K-weighted samples of hop h,
@@ -43,8 +44,35 @@
  * Many albums in one call (rg_r128_analyze_albums*, below) gate every album on the device in the same launches, and the node
  * entry points deal whole albums (or files) out over the GPUs of a node.
  *
+ * Channel weights (BS.1770 multichannel loudness).  A context has a channel mode (rg_r128_set_channel_mode):
+ *  - RG_R128_CHANNELS_PAIR, the default: everything above as it stands, channels 0 and 1 with weight 1.0;
+ *  - RG_R128_CHANNELS_LAYOUT: every track is weighted by its channel layout (rg_r128_layout_weights).  The PCM calls use
+ *    rg_r128_layout_weights(channels, 0); the file calls, and the node calls through each device's context, use the
+ *    container's channel mask where it has one (WAVE_FORMAT_EXTENSIBLE, also from a decoder command's pipe; FLAC and
+ *    everything else: the default of the channel count).  MP3 never has more than two channels.
+ *  - rg_r128_analyze_pcm_weighted takes explicit weights per track; they override the mode.
+ * A weighted track (rg_r128_channel_weights):
+ *  - has 1 to 8 channels; entries of w at and beyond the channel count are ignored, every used entry must be finite and
+ *    >= 0; otherwise the call returns RG_ERR_INVALID_ARG and names the track before any output is touched (a file fails
+ *    alone: "Unsupported channel count for layout analysis: {n} (1 to 8)");
+ *  - hop energy e[h] = sum over the channels c with w[c] != 0 of w[c] * e_c[h], e_c[h] the sum of squared K-weighted samples
+ *    of hop h of channel c: in ascending channel order, starting from the first such channel, every product rounded on its
+ *    own (no fused multiply-add across the sum); all weights zero: every e[h] is 0.  From there on blocks, gates, albums,
+ *    short-term blocks, range and maxima are what is specified above for a one-channel e[h] (block_z_out and st_z_out carry
+ *    the weighted values);
+ *  - sample peak and true peak are the maximum over ALL channels of the track whatever their weight (a clipping LFE still
+ *    clips), and a sample that is not finite in any channel raises RG_TRACK_FLAG_NONFINITE;
+ *  - with at most two channels whose used weights are all exactly 1.0 it is not weighted at all: it takes the path above
+ *    and returns its bits.
+ * Weighted and plain tracks may share a batch; the plain ones run exactly as without the others.
+ * The layout rule (BS.1770-4 table 4: 1.41 for |azimuth| 60 to 120 degrees at low elevation, 1.0 elsewhere, LFE not
+ * counted): channel i is the i-th set bit of the WAVE dwChannelMask in ascending bit order.  A mask of 0, or one whose
+ * population count is not the channel count, is replaced by the default of the count, the FLAC channel order: 1: 0x4,
+ * 2: 0x3, 3: 0x7, 4: 0x33, 5: 0x37, 6: 0x3F, 7: 0x70F, 8: 0x63F.  LFE (0x8): 0.  SL and SR (0x200, 0x400): 1.41.  BL and
+ * BR (0x10, 0x20): 1.41 when the mask has neither SL nor SR, else 1.0.  Every other position: 1.0.
+ *
  * Out of scope here: one album across several GPUs (it would need an exchange of hop energies), asynchronous variants,
- * surround channel weights, writing R128_* Opus tags or range tags.
+ * writing R128_* Opus tags or range tags.
  */
 #ifndef MP3RGAIN_AMD_R128_H
 #define MP3RGAIN_AMD_R128_H
@@ -90,7 +118,16 @@ typedef struct rg_r128_dynamics {
     uint32_t st_blocks_gated;   /* those both gates of the loudness range kept (n above) */
 } rg_r128_dynamics;
 
+#define RG_R128_CHANNELS_PAIR 0
+#define RG_R128_CHANNELS_LAYOUT 1
+
+typedef struct rg_r128_channel_weights {
+    double w[8];
+} rg_r128_channel_weights;
+
 /* ---- pure helpers (host) ---------------------------------------------------------------- */
+/* the weights of a layout of 1 to 8 channels (the rule above); RG_ERR_INVALID_ARG for any other count or out == NULL */
+int rg_r128_layout_weights(uint32_t channels, uint32_t channel_mask, rg_r128_channel_weights *out);
 int rg_r128_supported_rate(uint32_t sample_rate); /* 8000 .. 384000 Hz */
 /* The K-weighting of one rate: stage 1 (shelf) b1 / a1, stage 2 (RLB high-pass) b2 / a2, three values each, a[0] = 1;
  * hop in frames, true-peak oversampling factor.  Any pointer may be NULL.  RG_ERR_UNSUPPORTED_RATE outside the range. */
@@ -117,6 +154,9 @@ size_t rg_r128_albums_wide_rounds(size_t wide_albums, size_t *state_bytes);
  * integer histogram.  Both select the same elements; the threshold's sum is rounded in another order, which shows only for
  * a block within an ulp of it. */
 int rg_r128_set_tuning(rg_ctx *ctx, int key, int64_t value);
+
+/* RG_R128_CHANNELS_PAIR (the default) or RG_R128_CHANNELS_LAYOUT; anything else: RG_ERR_INVALID_ARG */
+int rg_r128_set_channel_mode(rg_ctx *ctx, int mode);
 
 /* ---- analysis (synchronous) ----------------------------------------------------------------- */
 /* n independent tracks of a planar PCM arena (rg_track_desc, mp3rgain_amd.h: sample alignment only, any storage order,
@@ -178,6 +218,15 @@ int rg_r128_analyze_albums_pcm_dynamics(rg_ctx *ctx, const rg_track_desc *tracks
                                         int want_true_peak, rg_r128_track_result *tracks_out, rg_r128_album_result *albums_out,
                                         double *block_z_out, rg_r128_dynamics *dyn_out, rg_r128_dynamics *albums_dyn_out,
                                         double *st_z_out);
+/* The most general PCM call, with channel weights: weights[n], or NULL = by the context's channel mode.  album_first = NULL
+ * with n_albums = 0: no albums (albums_out and albums_dyn_out are not used); dyn_out = NULL (and albums_dyn_out = NULL): no
+ * dynamics.  With weights = NULL in PAIR mode it returns bit for bit what rg_r128_analyze_albums_pcm[_dynamics] returns
+ * (without albums: rg_r128_analyze_pcm_batch[_dynamics]). */
+int rg_r128_analyze_pcm_weighted(rg_ctx *ctx, const rg_track_desc *tracks, const rg_r128_channel_weights *weights, size_t n,
+                                 const size_t *album_first, size_t n_albums, const void *pcm_base, size_t pcm_bytes,
+                                 int pcm_on_device, int want_true_peak, rg_r128_track_result *tracks_out,
+                                 rg_r128_album_result *albums_out, double *block_z_out, rg_r128_dynamics *dyn_out,
+                                 rg_r128_dynamics *albums_dyn_out, double *st_z_out);
 /* Files: the groups of rg_r128_analyze_tracks over the whole list, with its per-file status and texts (rg_tracks_error; a
  * WAV of a format no de-interleave reads fails alone with "Failed to probe format").  After each group every album whose
  * last file lies in the groups taken so far is gated, all of them in one album stage; an album that goes on into the next

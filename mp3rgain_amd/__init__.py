@@ -25,6 +25,7 @@ from .replaygain import (  # noqa: F401
     analyze_track,
     find_peak_amplitude,
     is_available,
+    r128_layout_weights,
 )
 
 __version__ = "0.1.0"

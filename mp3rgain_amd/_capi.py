@@ -96,6 +96,13 @@ class R128AlbumResult(C.Structure):
     ]
 
 
+class R128ChannelWeights(C.Structure):  # rg_r128_channel_weights
+    _fields_ = [("w", C.c_double * 8)]
+
+
+R128_CHANNELS_PAIR, R128_CHANNELS_LAYOUT = 0, 1
+
+
 class R128Dynamics(C.Structure):  # rg_r128_dynamics
     _fields_ = [
         ("loudness_range_lu", C.c_double),
@@ -228,6 +235,10 @@ R128_SYMBOLS = [
                                       _P(R128AlbumResult), _P(_i32)]),
     ("rg_r128_analyze_albums_dynamics", _int, [_vp, _P(C.c_char_p), _sz, _P(_sz), _sz, _i32, _int, _P(R128TrackResult), _P(_i32),
                                                _P(R128AlbumResult), _P(_i32), _P(R128Dynamics), _P(R128Dynamics)]),
+    ("rg_r128_layout_weights", _int, [_u32, _u32, _P(R128ChannelWeights)]),
+    ("rg_r128_set_channel_mode", _int, [_vp, _int]),
+    ("rg_r128_analyze_pcm_weighted", _int, [_vp, _P(TrackDesc), _P(R128ChannelWeights), _sz, _P(_sz), _sz, _vp, _sz, _int, _int,
+                                            _P(R128TrackResult), _P(R128AlbumResult), _vp, _P(R128Dynamics), _P(R128Dynamics), _vp]),
     ("rg_r128_analyze_tracks_node", _int, [_vp, _P(C.c_char_p), _sz, _i32, _int, _P(R128TrackResult), _P(_i32), _P(R128Dynamics)]),
     ("rg_r128_analyze_albums_node", _int, [_vp, _P(C.c_char_p), _sz, _P(_sz), _sz, _i32, _int, _P(R128TrackResult), _P(_i32),
                                            _P(R128AlbumResult), _P(_i32), _P(R128Dynamics), _P(R128Dynamics)]),

@@ -63,6 +63,7 @@ class Options:  # src/main.rs:65-96
     r128: bool = False       # this façade only: EBU R 128 / ReplayGain 2.0 analysis instead of ReplayGain 1.0
     true_peak: bool = False  # with --r128: report and clip-limit on the true peak
     loudness_range: bool = False  # with --r128 (--range): loudness range, maximum momentary and short-term loudness
+    surround: bool = False   # with --r128 (--surround): BS.1770 channel weights from every file's channel layout
     files: List[Path] = field(default_factory=list)
 
 
@@ -122,6 +123,8 @@ def parse_args(args: List[str], out, err) -> Options:
             o.true_peak = True
         elif arg == "--range":
             o.loudness_range = True
+        elif arg == "--surround":
+            o.surround = True
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -214,6 +217,8 @@ def parse_args(args: List[str], out, err) -> Options:
         elif not arg.startswith("--"):
             o.files.append(Path(arg))
         i += 1
+    if o.surround and not o.r128:
+        raise CliError("--surround requires --r128")
     return o
 
 
@@ -360,6 +365,8 @@ class Cli:
             dec = self.o.decoder or os.environ.get("MP3RGAIN_AMD_DECODER")
             if dec:
                 self._an.set_decoder_command(dec)
+            if self.o.surround:
+                self._an.set_channel_mode_r128("layout")
         return self._an
 
     def analyze_track(self, file):
@@ -1088,6 +1095,7 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "--r128      Analyse after EBU R 128 / ITU-R BS.1770 (ReplayGain 2.0: gain to -18 LUFS) instead of ReplayGain 1.0",
         "--true-peak With --r128: report and clip-limit on the true peak (4x / 2x oversampled)",
         "--range     With --r128: also report loudness range (EBU Tech 3342), maximum momentary and short-term loudness",
+        "--surround  With --r128: weight every channel of a multichannel file by its layout (BS.1770: surrounds 1.41, LFE 0)",
         "-v          Show version",
         "-h          Show this help",
     ):

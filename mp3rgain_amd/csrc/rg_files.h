@@ -30,6 +30,8 @@ struct WavItem {
     uint64_t src_len;
 };
 int wav_kind(const rg_wav_info &w);  // WavKind, or -1: a sample format the de-interleave does not read
+// dwChannelMask of a RIFF/WAVE stream whose format tag is WAVE_FORMAT_EXTENSIBLE (0xFFFE); 0 for any other stream
+uint32_t wav_channel_mask(const void *data, size_t len);
 // Input `i` of a batch, a RIFF/WAVE stream: `it`, and `d` at the arena's *dst_total; both totals move past it.  An error is
 // "input <i> ..." (rg_analyze_album_begin reads the index back).
 int wav_layout(rg_ctx *c, size_t i, const void *bytes, size_t len, WavItem *it, rg_track_desc *d, size_t *src_total, size_t *dst_total);

@@ -501,6 +501,7 @@ static int r128_files_group(rg_ctx *c, const char *const *paths, size_t first, s
     int rc = load_many(c, paths, n, &in, &rcs, &errs, nullptr);
     c->file_track_index = -1;
     if (rc != RG_OK) return rc;
+    const bool layout = rg_r128_channel_mode(c) == RG_R128_CHANNELS_LAYOUT;
     std::vector<size_t> slot;
     for (size_t i = 0; i < n; ++i) {
         memset(&out[i], 0, sizeof out[i]);
@@ -509,6 +510,19 @@ static int r128_files_group(rg_ctx *c, const char *const *paths, size_t first, s
         if (frc == RG_OK && !stageable(in[i])) {
             frc = RG_ERR_FORMAT;
             msg = std::string("Failed to probe format: ") + paths[i];
+        }
+        if (frc == RG_OK && layout) {  // a layout has 1 to 8 channels
+            uint32_t channels = in[i].channels;
+            if (in[i].kind == LoadedAudio::Wav) {
+                rg_wav_info wi;
+                channels = rg_wav_parse(in[i].wav.data(), in[i].wav.size(), &wi) == RG_OK ? wi.channels : 0;
+            }
+            if (channels < 1 || channels > 8) {
+                char m[128];
+                snprintf(m, sizeof m, "Unsupported channel count for layout analysis: %u (1 to 8)", channels);
+                frc = RG_ERR_INVALID_ARG;
+                msg = m;
+            }
         }
         if (frc != RG_OK && album) return rg_set_err(c, frc, "%s", msg.c_str());
         if (status_out) {
@@ -521,8 +535,15 @@ static int r128_files_group(rg_ctx *c, const char *const *paths, size_t first, s
     std::vector<rg_r128_dynamics> dyn(dyn_out ? slot.size() : 0);
     if (kept_tr) kept_tr->resize(slot.size());
     rc = run_good_files(c, in, slot, out, [&](const rg_track_desc *descs, size_t k, size_t arena_bytes, rg_r128_track_result *res) {
+        // LAYOUT mode: every file's weights from its container's channel mask (file j of the batch is in[j] by now)
+        std::vector<rg_r128_channel_weights> weights(layout ? k : 0);
+        for (size_t j = 0; j < weights.size(); ++j) {
+            const uint32_t mask = in[j].kind == LoadedAudio::Wav ? wav_channel_mask(in[j].wav.data(), in[j].wav.size()) : 0u;
+            if (rg_r128_layout_weights(descs[j].channels, mask, &weights[j]) != RG_OK)
+                return rg_set_err(c, RG_ERR_INVALID_ARG, "Unsupported channel count for layout analysis: %u (1 to 8)", descs[j].channels);
+        }
         return rg_r128_run(c, descs, k, c->d_arena.p, arena_bytes, want_tp, album ? 1 : 0, res, nullptr, dyn_out ? dyn.data() : nullptr, nullptr,
-                           kept_tr ? kept_tr->data() : nullptr, kept_e);
+                           kept_tr ? kept_tr->data() : nullptr, kept_e, layout ? weights.data() : nullptr);
     });
     if (rc != RG_OK) {
         if (album) return rc;

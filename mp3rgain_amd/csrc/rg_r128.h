@@ -25,8 +25,8 @@ void rg_r128_tp_table(uint32_t factor, float *taps /* RG_R128_TP_TAPS */);
 // One track of a launch.  Lanes [lane_base, lane_base + nch * runs) belong to it, channel-major: lane = c * runs + r owns hops
 // [r S, min((r + 1) S, H)) of channel c.
 struct RgR128TrackDev {
-    const unsigned char *ch[2];  // ch[1] = nullptr for one channel
-    double *e;                   // hop energies [nch][H]
+    const unsigned char *ch[8];  // the planes of channels 0 .. nch-1, nullptr from there on
+    double *e;                   // hop energies [nch][H]; behind the weighted fold (rg_r128_surround.hip): nch = 1, the folded row
     uint64_t frames;
     uint64_t lane_base;
     uint64_t z_base;             // first block of the track in block_z_out
@@ -43,9 +43,31 @@ struct rg_ctx;
 // are computed too (rg_r128_range.hip) after the launches of the plain call, which do not change; st_z_out goes with them.
 // tr_out: nullptr, or the tracks' device descriptors go there (rg_r128_albums_stage reads them); their hop energies are in
 // the context's own buffer until the next call, or, with e_out, in a buffer of their own that the caller frees (hipFree).
+// weights: nullptr (every track by the context's channel mode: a pair, or rg_r128_layout_weights(channels, 0)), or one entry
+// per track.  A weighted track of at most two channels whose used weights are all 1.0 is a plain track; any other runs all
+// its channels through the main kernel into a scratch area and is folded to one row (rg_r128_surround.hip), which is what
+// everything behind sees (nch = 1 in tr_out, in the kept descriptors and in the gate kernel's).
 int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_base, size_t pcm_bytes, int want_true_peak,
                 int keep_for_album, rg_r128_track_result *out, double *block_z_out, rg_r128_dynamics *dyn_out = nullptr,
-                double *st_z_out = nullptr, RgR128TrackDev *tr_out = nullptr, double **e_out = nullptr);
+                double *st_z_out = nullptr, RgR128TrackDev *tr_out = nullptr, double **e_out = nullptr,
+                const rg_r128_channel_weights *weights = nullptr);
+int rg_r128_channel_mode(rg_ctx *c);  // RG_R128_CHANNELS_*
+// arguments of a weighted track: 1 to 8 channels, every used weight finite and >= 0; else RG_ERR_INVALID_ARG naming track t
+int rg_r128_check_weights(rg_ctx *c, size_t t, uint32_t channels, const rg_r128_channel_weights *w);
+
+// rg_r128_surround.hip: e[h] = sum over the channels with w != 0 of w_c * e_c[h], ascending c, every product and every sum
+// rounded on its own; all weights zero: 0.  One launch over n_items tracks on the HIP stream `stream`, not waited for; the
+// return value is the launch's hipError_t.
+struct RgR128FoldItem {
+    const double *src;    // [nch][H]
+    double *dst;          // [H]
+    uint64_t block_base;  // first workgroup of the track in the launch
+    uint32_t H, nch;
+    double w[8];
+};
+#define RG_R128_FOLD_BLOCK 256
+int rg_r128_fold_launch(const RgR128FoldItem *d_items, uint32_t n_items, uint64_t blocks, void *stream);
+
 void rg_r128_album_reset(rg_ctx *c);
 int rg_r128_album_end(rg_ctx *c, int want_true_peak, rg_r128_album_result *album_out, rg_r128_dynamics *dyn_out = nullptr,
                       rg_r128_dynamics *album_dyn_out = nullptr, double *st_z_out = nullptr);

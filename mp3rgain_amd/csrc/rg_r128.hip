@@ -396,6 +396,7 @@ namespace {
 struct R128State {
     uint32_t tune_S = 0;
     int tune_album_select = 0;
+    int channel_mode = RG_R128_CHANNELS_PAIR;
     void *range = nullptr;  // rg_r128_range.hip's buffers
     void *albums = nullptr;  // rg_r128_albums.hip's
     DevBuf<unsigned char> d_desc;
@@ -403,6 +404,7 @@ struct R128State {
     DevBuf<rg_r128_track_result> d_res;
     DevBuf<rg_r128_album_result> d_album;
     DevBuf<double> d_e, d_z;
+    DevBuf<double> d_ce;  // weighted tracks: the per-channel hop energies in front of the fold
     // an album in progress: every group's tracks in input order, their hop energies still on the device
     std::vector<double *> kept_e;
     std::vector<RgR128TrackDev> kept;
@@ -429,6 +431,7 @@ R128State &state(rg_ctx *c) {
             s->d_album.release();
             s->d_e.release();
             s->d_z.release();
+            s->d_ce.release();
             delete s;
         };
     }
@@ -462,13 +465,13 @@ void launch_main(const RgR128TrackDev *d_list, uint32_t n, uint64_t lanes, uint3
 }
 
 template <int FMT>
-void launch_tp(uint32_t factor, const RgR128TrackDev *d_list, uint32_t n, uint64_t tiles, uint32_t *tp, hipStream_t s) {
+void launch_tp(uint32_t factor, const RgR128TrackDev *d_list, uint32_t n, uint64_t tiles, uint32_t ny, uint32_t *tp, hipStream_t s) {
     RgR128Taps taps;
     rg_r128_tp_table(factor, taps.h);
     if (factor == 4)
-        hipLaunchKernelGGL((rg_r128_truepeak_kernel<FMT, 4>), dim3((uint32_t)tiles, 2), dim3(256), 0, s, d_list, n, taps, tp);
+        hipLaunchKernelGGL((rg_r128_truepeak_kernel<FMT, 4>), dim3((uint32_t)tiles, ny), dim3(256), 0, s, d_list, n, taps, tp);
     else
-        hipLaunchKernelGGL((rg_r128_truepeak_kernel<FMT, 2>), dim3((uint32_t)tiles, 2), dim3(256), 0, s, d_list, n, taps, tp);
+        hipLaunchKernelGGL((rg_r128_truepeak_kernel<FMT, 2>), dim3((uint32_t)tiles, ny), dim3(256), 0, s, d_list, n, taps, tp);
 }
 
 // the absolute gate, -70 LUFS as a mean square
@@ -498,6 +501,25 @@ extern "C" int rg_r128_set_tuning(rg_ctx *c, int key, int64_t value) {
     return RG_OK;
 }
 
+extern "C" int rg_r128_set_channel_mode(rg_ctx *c, int mode) {
+    if (!c) return RG_ERR_INVALID_ARG;
+    if (mode != RG_R128_CHANNELS_PAIR && mode != RG_R128_CHANNELS_LAYOUT)
+        return rg_set_err(c, RG_ERR_INVALID_ARG, "unknown R 128 channel mode %d", mode);
+    state(c).channel_mode = mode;
+    return RG_OK;
+}
+
+int rg_r128_channel_mode(rg_ctx *c) { return state(c).channel_mode; }
+
+int rg_r128_check_weights(rg_ctx *c, size_t t, uint32_t channels, const rg_r128_channel_weights *w) {
+    if (channels < 1 || channels > 8)
+        return rg_set_err(c, RG_ERR_INVALID_ARG, "track %zu: Unsupported channel count for layout analysis: %u (1 to 8)", t, channels);
+    for (uint32_t k = 0; w && k < channels; ++k)
+        if (!(w->w[k] >= 0.0) || !(w->w[k] < INFINITY))
+            return rg_set_err(c, RG_ERR_INVALID_ARG, "track %zu: channel weight %u is not a finite number >= 0", t, k);
+    return RG_OK;
+}
+
 void rg_r128_album_reset(rg_ctx *c) { state(c).drop_album(); }
 
 int rg_r128_album_select(rg_ctx *c) { return state(c).tune_album_select; }
@@ -506,12 +528,27 @@ void **rg_r128_albums_slot(rg_ctx *c) { return &state(c).albums; }
 
 int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_base, size_t pcm_bytes, int want_tp, int keep,
                 rg_r128_track_result *out, double *block_z_out, rg_r128_dynamics *dyn_out, double *st_z_out, RgR128TrackDev *tr_out,
-                double **e_out) {
+                double **e_out, const rg_r128_channel_weights *weights) {
     if (e_out) *e_out = nullptr;
     if (!c) return RG_ERR_INVALID_ARG;
     if (n && (!tracks || !out || !d_base)) return rg_set_err(c, RG_ERR_INVALID_ARG, "null argument");
     int rc = r128_validate(c, tracks, n, pcm_bytes);
     if (rc != RG_OK) return rc;
+    // the weights of every track: the caller's, or the layout rule's in LAYOUT mode; neither: the pair of channels 0 and 1
+    std::vector<rg_r128_channel_weights> layout_w;
+    if (!weights && n && state(c).channel_mode == RG_R128_CHANNELS_LAYOUT) {
+        layout_w.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            rc = rg_r128_check_weights(c, i, tracks[i].channels, nullptr);
+            if (rc != RG_OK) return rc;
+            (void)rg_r128_layout_weights(tracks[i].channels, 0, &layout_w[i]);
+        }
+        weights = layout_w.data();
+    }
+    for (size_t i = 0; weights && i < n; ++i) {
+        rc = rg_r128_check_weights(c, i, tracks[i].channels, &weights[i]);
+        if (rc != RG_OK) return rc;
+    }
     if (n == 0) return RG_OK;
     rc = rg_bind_device(c);
     if (rc != RG_OK) return rc;
@@ -521,7 +558,11 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
     R128State &st = state(c);
 
     std::vector<RgR128TrackDev> tr(n);
-    uint64_t total_e = 0, total_z = 0, channel_hops = 0;
+    uint64_t total_e = 0, total_z = 0, channel_hops = 0, total_ce = 0;
+    // a weighted track: every channel goes through the main kernel into d_ce (main_nch rows from ce_off on) and is folded
+    // into the track's one row of d_e; 0: a plain track
+    std::vector<uint32_t> main_nch(n, 0);
+    std::vector<uint64_t> ce_off(n, 0);
     for (size_t i = 0; i < n; ++i) {
         const rg_track_desc &d = tracks[i];
         RgR128Design ds;
@@ -530,8 +571,14 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
         memset(&o, 0, sizeof o);
         const size_t bps = rg_bytes_per_sample(d.format);
         o.nch = d.channels >= 2 ? 2 : 1;
-        o.ch[0] = (const unsigned char *)d_base + d.offset_bytes;
-        o.ch[1] = o.nch == 2 ? o.ch[0] + d.frames * bps : nullptr;
+        if (weights) {
+            bool plain = d.channels <= 2;
+            for (uint32_t k = 0; plain && k < d.channels; ++k) plain = weights[i].w[k] == 1.0;
+            if (!plain) main_nch[i] = d.channels;
+        }
+        const uint32_t planes = main_nch[i] ? main_nch[i] : o.nch;
+        for (uint32_t k = 0; k < planes; ++k) o.ch[k] = (const unsigned char *)d_base + d.offset_bytes + (uint64_t)k * d.frames * bps;
+        if (main_nch[i]) o.nch = 1;
         o.frames = d.frames;
         o.hop = ds.hop;
         o.H = (uint32_t)(d.frames / ds.hop);
@@ -547,7 +594,11 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
         total_z += o.H > 3 ? o.H - 3 : 0;
         o.e = (double *)(uintptr_t)(total_e * sizeof(double));  // offset for now
         total_e += (uint64_t)o.nch * o.H;
-        channel_hops += (uint64_t)o.nch * o.H;
+        channel_hops += (uint64_t)planes * o.H;
+        if (main_nch[i]) {
+            ce_off[i] = total_ce;
+            total_ce += (uint64_t)planes * o.H;
+        }
     }
     const uint32_t S = choose_S(st, channel_hops);
     double *d_e = nullptr;
@@ -561,6 +612,7 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
         RG_HIP(c, st.d_e.reserve(total_e ? total_e : 1));
         d_e = st.d_e.p;
     }
+    if (total_ce) RG_HIP(c, st.d_ce.reserve(total_ce));
     for (size_t i = 0; i < n; ++i) {
         RgR128TrackDev &o = tr[i];
         o.e = d_e + (uintptr_t)o.e / sizeof(double);
@@ -569,13 +621,17 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
     }
     // launch lists: the loudness kernel per sample format, the true-peak kernel per (format, factor)
     std::vector<RgR128TrackDev> blob(tr);
-    struct List { size_t first = 0, count = 0; uint64_t units = 0; };
+    struct List { size_t first = 0, count = 0; uint64_t units = 0; uint32_t ny = 2; };
     List main_l[3], tp_l[3][2];
     for (int f = 0; f < 3; ++f) {
         main_l[f].first = blob.size();
         for (size_t i = 0; i < n; ++i)
             if ((int)tr[i].format == f && tr[i].runs) {
                 RgR128TrackDev o = tr[i];
+                if (main_nch[i]) {
+                    o.nch = main_nch[i];
+                    o.e = st.d_ce.p + ce_off[i];
+                }
                 o.lane_base = main_l[f].units;
                 main_l[f].units += (uint64_t)o.nch * o.runs;
                 blob.push_back(o);
@@ -590,6 +646,8 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
                 for (size_t i = 0; i < n; ++i)
                     if ((int)tr[i].format == f && tr[i].tp_factor == factor && tr[i].frames) {
                         RgR128TrackDev o = tr[i];
+                        if (main_nch[i]) o.nch = main_nch[i];  // peaks are over every channel, whatever its weight
+                        tp_l[f][k].ny = std::max(tp_l[f][k].ny, o.nch);
                         o.tile_base = tp_l[f][k].units;
                         const uint64_t chunk = (uint64_t)RG_R128_TP_CHUNK * RG_R128_TP_TILE;
                         tp_l[f][k].units += (o.frames + 48 / factor + chunk - 1) / chunk;
@@ -601,13 +659,32 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
     for (int f = 0; f < 3; ++f)
         if (main_l[f].units > 0x7FFFFFFFull * RG_R128_BLOCK) return rg_set_err(c, RG_ERR_INVALID_ARG, "batch too long for one launch");
 
-    RG_HIP(c, st.d_desc.reserve(blob.size() * sizeof(RgR128TrackDev)));
+    std::vector<RgR128FoldItem> fold;
+    uint64_t fold_blocks = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (main_nch[i] && tr[i].H) {
+            RgR128FoldItem it;
+            memset(&it, 0, sizeof it);
+            it.src = st.d_ce.p + ce_off[i];
+            it.dst = tr[i].e;
+            it.block_base = fold_blocks;
+            it.H = tr[i].H;
+            it.nch = main_nch[i];
+            for (uint32_t k = 0; k < it.nch; ++k) it.w[k] = weights[i].w[k];
+            fold_blocks += (it.H + RG_R128_FOLD_BLOCK - 1) / RG_R128_FOLD_BLOCK;
+            fold.push_back(it);
+        }
+    if (fold_blocks > 0x7FFFFFFFull) return rg_set_err(c, RG_ERR_INVALID_ARG, "batch too long for one launch");
+    const size_t desc_bytes = blob.size() * sizeof(RgR128TrackDev);  // (a multiple of 8: the fold's items follow)
+    RG_HIP(c, st.d_desc.reserve(desc_bytes + fold.size() * sizeof(RgR128FoldItem)));
     RG_HIP(c, st.d_words.reserve(3 * n));
     RG_HIP(c, st.d_res.reserve(n));
     if (block_z_out) RG_HIP(c, st.d_z.reserve(total_z ? total_z : 1));
     const RgR128TrackDev *d_tr = reinterpret_cast<const RgR128TrackDev *>(st.d_desc.p);
     uint32_t *d_peak = st.d_words.p, *d_tp = st.d_words.p + n, *d_flags = st.d_words.p + 2 * n;
-    RG_HIP(c, hipMemcpyAsync(st.d_desc.p, blob.data(), blob.size() * sizeof(RgR128TrackDev), hipMemcpyHostToDevice, s));
+    RG_HIP(c, hipMemcpyAsync(st.d_desc.p, blob.data(), desc_bytes, hipMemcpyHostToDevice, s));
+    if (!fold.empty())
+        RG_HIP(c, hipMemcpyAsync(st.d_desc.p + desc_bytes, fold.data(), fold.size() * sizeof(RgR128FoldItem), hipMemcpyHostToDevice, s));
     RG_HIP(c, hipMemsetAsync(st.d_words.p, 0, 3 * n * sizeof(uint32_t), s));
     for (int f = 0; f < 3; ++f) {
         if (!main_l[f].count) continue;
@@ -617,15 +694,18 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
         else launch_main<RG_FMT_S32_PLANAR>(l, (uint32_t)main_l[f].count, main_l[f].units, d_peak, d_flags, s);
         RG_HIP(c, hipGetLastError());
     }
+    if (!fold.empty())
+        RG_HIP(c, (hipError_t)rg_r128_fold_launch(reinterpret_cast<const RgR128FoldItem *>(st.d_desc.p + desc_bytes), (uint32_t)fold.size(),
+                                                  fold_blocks, s));
     if (want_tp)
         for (int f = 0; f < 3; ++f)
             for (int k = 0; k < 2; ++k) {
                 if (!tp_l[f][k].count) continue;
                 const RgR128TrackDev *l = d_tr + tp_l[f][k].first;
                 const uint32_t factor = k ? 2 : 4, cnt = (uint32_t)tp_l[f][k].count;
-                if (f == RG_FMT_F32_PLANAR) launch_tp<RG_FMT_F32_PLANAR>(factor, l, cnt, tp_l[f][k].units, d_tp, s);
-                else if (f == RG_FMT_S16_PLANAR) launch_tp<RG_FMT_S16_PLANAR>(factor, l, cnt, tp_l[f][k].units, d_tp, s);
-                else launch_tp<RG_FMT_S32_PLANAR>(factor, l, cnt, tp_l[f][k].units, d_tp, s);
+                if (f == RG_FMT_F32_PLANAR) launch_tp<RG_FMT_F32_PLANAR>(factor, l, cnt, tp_l[f][k].units, tp_l[f][k].ny, d_tp, s);
+                else if (f == RG_FMT_S16_PLANAR) launch_tp<RG_FMT_S16_PLANAR>(factor, l, cnt, tp_l[f][k].units, tp_l[f][k].ny, d_tp, s);
+                else launch_tp<RG_FMT_S32_PLANAR>(factor, l, cnt, tp_l[f][k].units, tp_l[f][k].ny, d_tp, s);
                 RG_HIP(c, hipGetLastError());
             }
     hipLaunchKernelGGL(rg_r128_gate_kernel, dim3((uint32_t)n), dim3(256), 0, s, d_tr, (uint32_t)n, (const uint32_t *)nullptr, 0u,

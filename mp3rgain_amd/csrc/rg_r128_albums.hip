@@ -397,7 +397,7 @@ namespace {
 int albums_pcm(rg_ctx *c, const char *fn, const rg_track_desc *tracks, size_t n, const size_t *album_first, size_t n_albums,
                const void *pcm_base, size_t pcm_bytes, int on_device, int want_tp, rg_r128_track_result *tracks_out,
                rg_r128_album_result *albums_out, double *block_z_out, bool dynamics, rg_r128_dynamics *dyn_out,
-               rg_r128_dynamics *albums_dyn_out, double *st_z_out) {
+               rg_r128_dynamics *albums_dyn_out, double *st_z_out, const rg_r128_channel_weights *weights = nullptr) {
     if (!c) return RG_ERR_INVALID_ARG;
     if ((n && (!tracks || !pcm_base || !tracks_out || (dynamics && !dyn_out))) || (n_albums && (!albums_out || (dynamics && !albums_dyn_out))))
         return rg_set_err(c, RG_ERR_INVALID_ARG, "%s: null input or output array", fn);
@@ -408,7 +408,7 @@ int albums_pcm(rg_ctx *c, const char *fn, const rg_track_desc *tracks, size_t n,
     if (rc != RG_OK) return rc;
     // one pass over all n tracks (S from the whole batch), their hop energies stay in the context's buffer for the album stage
     std::vector<RgR128TrackDev> tr(n);
-    rc = rg_r128_run(c, tracks, n, d_base, pcm_bytes, want_tp, 0, tracks_out, block_z_out, nullptr, nullptr, tr.data());
+    rc = rg_r128_run(c, tracks, n, d_base, pcm_bytes, want_tp, 0, tracks_out, block_z_out, nullptr, nullptr, tr.data(), nullptr, weights);
     if (rc != RG_OK) return rc;
     rg_r128_dynamics none;  // (n_albums == 0 with dynamics: the stage still wants to know that they were asked for)
     return rg_r128_albums_stage(c, tr.data(), tracks_out, n, album_first, n_albums, want_tp, albums_out, dyn_out,
@@ -431,4 +431,23 @@ extern "C" int rg_r128_analyze_albums_pcm_dynamics(rg_ctx *c, const rg_track_des
                                                    rg_r128_dynamics *albums_dyn_out, double *st_z_out) {
     return albums_pcm(c, "rg_r128_analyze_albums_pcm_dynamics", tracks, n, album_first, n_albums, pcm_base, pcm_bytes, pcm_on_device,
                       want_true_peak, tracks_out, albums_out, block_z_out, true, dyn_out, albums_dyn_out, st_z_out);
+}
+
+// The most general PCM call: per-track channel weights (nullptr: by the context's channel mode), albums or none, dynamics
+// or none.
+extern "C" int rg_r128_analyze_pcm_weighted(rg_ctx *c, const rg_track_desc *tracks, const rg_r128_channel_weights *weights, size_t n,
+                                            const size_t *album_first, size_t n_albums, const void *pcm_base, size_t pcm_bytes,
+                                            int pcm_on_device, int want_true_peak, rg_r128_track_result *tracks_out,
+                                            rg_r128_album_result *albums_out, double *block_z_out, rg_r128_dynamics *dyn_out,
+                                            rg_r128_dynamics *albums_dyn_out, double *st_z_out) {
+    const char *fn = "rg_r128_analyze_pcm_weighted";
+    if (!c) return RG_ERR_INVALID_ARG;
+    if (album_first || n_albums)
+        return albums_pcm(c, fn, tracks, n, album_first, n_albums, pcm_base, pcm_bytes, pcm_on_device, want_true_peak, tracks_out, albums_out,
+                          block_z_out, dyn_out != nullptr || albums_dyn_out != nullptr, dyn_out, albums_dyn_out, st_z_out, weights);
+    if (n && (!tracks || !pcm_base || !tracks_out)) return rg_set_err(c, RG_ERR_INVALID_ARG, "%s: null input or output array", fn);
+    const void *d_base = nullptr;
+    const int rc = rg_stage_pcm(c, pcm_base, pcm_bytes, pcm_on_device, &d_base);
+    if (rc != RG_OK) return rc;
+    return rg_r128_run(c, tracks, n, d_base, pcm_bytes, want_true_peak, 0, tracks_out, block_z_out, dyn_out, st_z_out, nullptr, nullptr, weights);
 }

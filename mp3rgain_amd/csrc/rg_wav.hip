@@ -68,6 +68,23 @@ extern "C" int rg_wav_parse(const void *data, size_t len, rg_wav_info *out) {
     return RG_ERR_INVALID_ARG;
 }
 
+uint32_t rgf::wav_channel_mask(const void *data, size_t len) {
+    const uint8_t *d = (const uint8_t *)data;
+    if (!d || len < 12 || memcmp(d, "RIFF", 4) != 0 || memcmp(d + 8, "WAVE", 4) != 0) return 0;
+    size_t pos = 12;
+    while (pos + 8 <= len) {
+        const uint32_t size = le32(d + pos + 4);
+        const size_t body = pos + 8;
+        if (memcmp(d + pos, "fmt ", 4) == 0)
+            return size >= 40 && body + 40 <= len && le16(d + body) == 0xFFFE ? le32(d + body + 20) : 0u;
+        if (memcmp(d + pos, "data", 4) == 0) return 0;
+        const uint64_t next = (uint64_t)body + size + (size & 1u);
+        if (next > len) break;
+        pos = (size_t)next;
+    }
+    return 0;
+}
+
 // =================================================================================================
 // interleaved bytes -> planar arena (device).  One thread per frame in the general kernel; stereo f32 and
 // stereo s16 (what decoders emit) move 16 bytes per lane per access when the planes are 16-byte aligned.

@@ -162,11 +162,16 @@ class PcmTrack:
     channels: Sequence[np.ndarray]
     sample_rate: int
     file_type: AudioFileType = AudioFileType.Mp3
+    channel_weights: Optional[Sequence[float]] = None  # EBU R 128 only: up to 8 weights, one per channel (missing ones: 0)
     _fmt: int = field(init=False, default=0)
 
     def __post_init__(self):
         if len(self.channels) == 0:
             raise ValueError("No audio track found")  # src/replaygain.rs:834-836
+        if self.channel_weights is not None:
+            self.channel_weights = [float(w) for w in self.channel_weights]
+            if len(self.channel_weights) > 8:
+                raise ValueError("at most 8 channel weights")
         chans = [np.ascontiguousarray(c) for c in self.channels]
         dt = chans[0].dtype
         if dt not in _NP_FMT:
@@ -180,6 +185,27 @@ class PcmTrack:
     @property
     def frames(self) -> int:
         return int(self.channels[0].shape[0])
+
+
+_R128_MODES = {"pair": _capi.R128_CHANNELS_PAIR, "layout": _capi.R128_CHANNELS_LAYOUT}
+
+
+def _r128_mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in _R128_MODES:
+            raise ValueError(f"unknown R 128 channel mode {mode!r} (pair, layout)")
+        return _R128_MODES[mode]
+    return int(mode)
+
+
+def r128_layout_weights(channels: int, mask: int = 0) -> List[float]:
+    """The BS.1770 weights of a layout of 1 to 8 channels (rg_r128_layout_weights; host only): channel i is the i-th set bit
+    of the WAVE channel mask `mask`, 0 = the default layout of that many channels (the FLAC channel order)."""
+    w = _capi.R128ChannelWeights()
+    rc = _capi.load().rg_r128_layout_weights(int(channels), int(mask), C.byref(w))
+    if rc != _capi.RG_OK:
+        raise ReplayGainError(rc, f"Unsupported channel count for layout analysis: {channels} (1 to 8)")
+    return [float(w.w[i]) for i in range(int(channels))]
 
 
 def _to_dynamics(d) -> Optional[R128Dynamics]:
@@ -352,6 +378,44 @@ class Analyzer:
         0 = chosen by the library, 1 = one workgroup, 2 = wide counting passes."""
         self._check(self._lib.rg_r128_set_tuning(self._ctx, key, value))
 
+    def set_channel_mode_r128(self, mode):
+        """"pair" (the default): channels 0 and 1 of every track, weight 1.0.  "layout": every track weighted by its channel
+        layout (r128_layout_weights; files: by their container's channel mask)."""
+        self._check(self._lib.rg_r128_set_channel_mode(self._ctx, _r128_mode(mode)))
+        self._r128_layout = _r128_mode(mode) == _capi.R128_CHANNELS_LAYOUT
+
+    def _r128_weighted(self, tracks, first, true_peak, return_blocks, dynamics, return_short_term):
+        """rg_r128_analyze_pcm_weighted: tracks that carry channel_weights use them, the others the weights the context's
+        channel mode gives them.  first: None (no albums) or the albums' first tracks.  -> out, alb, dyn, adyn, extra"""
+        n = len(tracks)
+        arena, descs = pack_tracks(tracks)
+        weights = (_capi.R128ChannelWeights * max(1, n))()
+        layout = getattr(self, "_r128_layout", False)
+        for i, t in enumerate(tracks):
+            cw = t.channel_weights
+            if cw is None:  # what the context's mode gives this track ({1, 1} on at most two channels: the plain path)
+                if not layout and len(t.channels) > 2:
+                    raise ValueError("in pair mode a track of more than two channels cannot share a call with weighted tracks")
+                cw = r128_layout_weights(len(t.channels)) if layout else [1.0] * len(t.channels)
+            for k, v in enumerate(cw):
+                weights[i].w[k] = v
+        n_albums = len(first) - 1 if first is not None else 0
+        album_first = (C.c_size_t * (n_albums + 1))(*first) if first is not None else None
+        out = (_capi.R128TrackResult * max(1, n))()
+        alb = (_capi.R128AlbumResult * max(1, n_albums))()
+        counts, z = self._r128_blocks(tracks) if return_blocks else (None, None)
+        dyn = adyn = st = st_counts = None
+        if dynamics:
+            dyn = (_capi.R128Dynamics * max(1, n))()
+            adyn = (_capi.R128Dynamics * max(1, n_albums))()
+            st_counts, st = self._r128_blocks(tracks, True) if return_short_term else (None, None)
+        self._check(self._lib.rg_r128_analyze_pcm_weighted(
+            self._ctx, descs, weights, n, album_first, n_albums, arena.ctypes.data, arena.nbytes, 0, int(true_peak), out, alb,
+            z.ctypes.data if z is not None else None, dyn, adyn if first is not None else None,
+            st.ctypes.data if st is not None else None))
+        extra = ([_split_blocks(z, counts)] if return_blocks else []) + ([_split_blocks(st, st_counts)] if return_short_term else [])
+        return out, alb, dyn, adyn, extra
+
     def _r128_blocks(self, tracks, short_term=False):
         count = self._lib.rg_r128_short_term_count if short_term else self._lib.rg_r128_block_count
         counts = [int(count(t.sample_rate, t.frames)) for t in tracks]
@@ -367,6 +431,10 @@ class Analyzer:
         if return_short_term and not dynamics:
             raise ValueError("return_short_term needs dynamics=True")
         n = len(tracks)
+        if any(t.channel_weights is not None for t in tracks):
+            out, _, dyn, _, extra = self._r128_weighted(tracks, None, true_peak, return_blocks, dynamics, return_short_term)
+            res = [_to_r128(out[i], tracks[i].file_type, dyn[i] if dyn is not None else None) for i in range(n)]
+            return (res, *extra) if extra else res
         arena, descs = pack_tracks(tracks)
         out = (_capi.R128TrackResult * max(1, n))()
         counts, z = self._r128_blocks(tracks) if return_blocks else (None, None)
@@ -390,6 +458,11 @@ class Analyzer:
         if return_short_term and not dynamics:
             raise ValueError("return_short_term needs dynamics=True")
         n = len(tracks)
+        if any(t.channel_weights is not None for t in tracks):
+            out, alb, dyn, adyn, extra = self._r128_weighted(tracks, [0, n], true_peak, return_blocks, dynamics, return_short_term)
+            res = _to_r128_album([_to_r128(out[i], tracks[i].file_type, dyn[i] if dyn is not None else None) for i in range(n)],
+                                 alb[0], adyn[0] if adyn is not None else None)
+            return (res, *extra) if extra else res
         arena, descs = pack_tracks(tracks)
         out = (_capi.R128TrackResult * max(1, n))()
         alb = _capi.R128AlbumResult()
@@ -460,14 +533,24 @@ class Analyzer:
         for a in albums:
             first.append(first[-1] + len(a))
         n, n_albums = len(tracks), len(albums)
-        arena, descs = pack_tracks(tracks)
-        album_first = (C.c_size_t * (n_albums + 1))(*first)
-        out = (_capi.R128TrackResult * max(1, n))()
-        alb = (_capi.R128AlbumResult * max(1, n_albums))()
-        counts, z = self._r128_blocks(tracks) if return_blocks else (None, None)
-        zp = z.ctypes.data if z is not None else None
-        dyn = adyn = None
-        if dynamics:
+        weighted = any(t.channel_weights is not None for t in tracks)
+        if weighted:
+            out, alb, dyn, adyn, wextra = self._r128_weighted(tracks, first, true_peak, return_blocks, dynamics, return_short_term)
+            if return_blocks:
+                z_split = wextra.pop(0)
+            if return_short_term:
+                st_split = wextra.pop(0)
+        else:
+            arena, descs = pack_tracks(tracks)
+            album_first = (C.c_size_t * (n_albums + 1))(*first)
+            out = (_capi.R128TrackResult * max(1, n))()
+            alb = (_capi.R128AlbumResult * max(1, n_albums))()
+            counts, z = self._r128_blocks(tracks) if return_blocks else (None, None)
+            zp = z.ctypes.data if z is not None else None
+            dyn = adyn = None
+        if weighted:
+            pass
+        elif dynamics:
             dyn = (_capi.R128Dynamics * max(1, n))()
             adyn = (_capi.R128Dynamics * max(1, n_albums))()
             st_counts, st = self._r128_blocks(tracks, True) if return_short_term else (None, None)
@@ -482,10 +565,10 @@ class Analyzer:
                for a in range(n_albums)]
         extra = []
         if return_blocks:
-            zs = _split_blocks(z, counts)
+            zs = z_split if weighted else _split_blocks(z, counts)
             extra.append([zs[first[a]:first[a + 1]] for a in range(n_albums)])
         if return_short_term:
-            ss = _split_blocks(st, st_counts)
+            ss = st_split if weighted else _split_blocks(st, st_counts)
             extra.append([ss[first[a]:first[a + 1]] for a in range(n_albums)])
         return (res, *extra) if extra else res
 
@@ -816,6 +899,7 @@ class Node:
         a._ctx = ctx
         a._borrowed = True
         a.device = int(i)
+        a._r128_layout = getattr(self, "_r128_layout", False)
         return a
 
     def set_tuning(self, key: int, value: int):
@@ -824,6 +908,14 @@ class Node:
             ctx = self._lib.rg_node_ctx(self._node, i)
             if ctx and self._lib.rg_set_tuning(ctx, int(key), int(value)) != 0:
                 raise ReplayGainError(-1, self._lib.rg_last_error(ctx).decode("utf-8", "replace"))
+
+    def set_channel_mode_r128(self, mode):
+        """Analyzer.set_channel_mode_r128 on every device's context."""
+        for i in range(self.devices):
+            ctx = self._lib.rg_node_ctx(self._node, i)
+            if ctx and self._lib.rg_r128_set_channel_mode(ctx, _r128_mode(mode)) != 0:
+                raise ReplayGainError(-1, self._lib.rg_last_error(ctx).decode("utf-8", "replace"))
+        self._r128_layout = _r128_mode(mode) == _capi.R128_CHANNELS_LAYOUT
 
     def set_decoder_command(self, command_template: Optional[str]):
         for i in range(self.devices):
