@@ -16,13 +16,15 @@
  * reference decodes FLAC with symphonia, whose source is not in the reference tree; its handling of damaged FLAC could not
  * be compared, and this rule is the project's own.
  *
- * Host code (apart from rg_flac_decode_device), plain C types, no exceptions or aborts across the ABI.
+ * Host code (apart from rg_flac_decode_device and rg_flac_stage_device_batch), plain C types, no exceptions or aborts across the ABI.
  */
 #ifndef MP3RGAIN_AMD_FLAC_H
 #define MP3RGAIN_AMD_FLAC_H
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "mp3rgain_amd.h" /* rg_track_desc (rg_flac_stage_device_batch) */
 
 #ifdef __cplusplus
 extern "C" {
@@ -84,6 +86,26 @@ const char *rg_flac_last_error(void);
 /* Test seam of the device decoder: the stream through the file route's device kernels (frame check, layout, decode),
  * PCM back to `planes` as rg_flac_decode_s32 returns it (bit for bit, tests/test_gpu_flac.py).  `ctx` is an rg_ctx. */
 int rg_flac_decode_device(void *ctx, const void *data, size_t len, int32_t *const *planes, uint64_t capacity, rg_flac_info *out);
+
+/* Test seam of the file route's FLAC staging: `n` streams in memory are loaded (the frame walk; with tuning key 14 = 0 the
+ * host decoder and its repacking) and staged by the very code a file call runs -- one launch of the device decoder for
+ * all of them, each stream at its own 16-byte-aligned arena offset, <= 16 bits per sample in 16-bit planes (<< 16 - bps),
+ * 17-24 bits in 32-bit planes (<< 32 - bps), plane c of stream i at offset_bytes + c * frames * element size -- and the
+ * first *arena_bytes bytes of the analysis arena are copied to `arena_out` (tests/test_gpu_flac_batch.py).
+ * descs[i]: what the analysis kernels would be given for stream i (offset, decoded PCM frames, rate, channels, format).
+ * infos[i]: STREAMINFO, and frames = decoded PCM frames per channel, audio_frames = FLAC frames decoded, dropped_frames
+ * = FLAC frames dropped (walked = audio_frames + dropped_frames).  RG_ERR_INVALID_ARG with *arena_bytes set when
+ * `arena_capacity` is too small.  `ctx` is an rg_ctx. */
+int rg_flac_stage_device_batch(void *ctx, size_t n, const void *const *data, const size_t *len, rg_track_desc *descs,
+                               rg_flac_info *infos, void *arena_out, size_t arena_capacity, size_t *arena_bytes);
+
+/* Test seam, host code: the CPU twin of the device decoder's output stage.  Decodes the stream as rg_flac_decode_s32
+ * does, but writes -- and, for the stereo decorrelations, reads back -- every sample through the arena sink of the device
+ * kernel (rg_flac_frame.h: RgFlacArenaOut) into `out`, in the arena's format: planes of *elem_bytes-byte elements (2 for
+ * <= 16 bits per sample, else 4), plane c at out + c * info->frames * *elem_bytes.  RG_FLAC_ERR_CAPACITY (info->frames
+ * set) when capacity_bytes < channels * frames * elem_bytes; RG_FLAC_ERR_ARG if a frame's verdict through this sink
+ * differs from the host decoder's (it must not). */
+int rg_flac_decode_arena(const void *data, size_t len, void *out, size_t capacity_bytes, uint32_t *elem_bytes, rg_flac_info *info);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,8 @@
 // rg_file_hooks.hip -- measurement and parity hooks of the file layer's device decoders: one stream in memory through the
-// decode chain, timed (rg_mp3_decode_bench) or with the PCM brought back (rg_mp3_decode_device, rg_flac_decode_device).
+// decode chain, timed (rg_mp3_decode_bench) or with the PCM brought back (rg_mp3_decode_device, rg_flac_decode_device), and
+// a batch of FLAC streams through the file route's staging with the arena brought back (rg_flac_stage_device_batch).
+#include <new>
+#include <string>
 #include <vector>
 
 #include "rg_files.h"
@@ -234,4 +237,43 @@ extern "C" int rg_flac_decode_device(void *ctx, const void *data, size_t len, in
         RG_HIP(c, hipMemcpy(planes[ch], c->d_arena.p + (size_t)ch * st.samples * sizeof(int32_t), (size_t)st.samples * sizeof(int32_t), hipMemcpyDeviceToHost));
     c->user_dirty = true;
     return RG_OK;
+}
+
+// `n` FLAC streams in memory through the file route's own loading and staging (load_flac with the context's tuning key 14,
+// then stage_loaded: one rg_flacdev_decode for all of them, or the host decoder's repacked PCM), and the arena brought
+// back with the track descriptors the analysis kernels would be given: the parity hook of tests/test_gpu_flac_batch.py.
+extern "C" int rg_flac_stage_device_batch(void *ctx, size_t n, const void *const *data, const size_t *len, rg_track_desc *descs,
+                                          rg_flac_info *infos, void *arena_out, size_t arena_capacity, size_t *arena_bytes) {
+    rg_ctx *c = static_cast<rg_ctx *>(ctx);
+    if (!c || !n || !data || !len || !descs || !infos || !arena_bytes || (arena_capacity && !arena_out)) return RG_ERR_INVALID_ARG;
+    try {
+        std::vector<LoadedAudio> &pool = file_pool(c, n);
+        for (size_t i = 0; i < n; ++i) {
+            if (!data[i]) return rg_set_err(c, RG_ERR_INVALID_ARG, "stream %zu: null data", i);
+            if (rg_flac_scan(data[i], len[i], &infos[i]) != RG_FLAC_OK) return rg_set_err(c, RG_ERR_FORMAT, "stream %zu: %s", i, rg_flac_last_error());
+            const uint8_t *p = static_cast<const uint8_t *>(data[i]);
+            pool[i].file_bytes.assign(p, p + len[i]);
+            std::string err;
+            const std::string name = "stream " + std::to_string(i);
+            const int lrc = load_flac(c->gpu_flac_decode, name.c_str(), &pool[i], &err);
+            if (lrc != RG_OK) return rg_set_err(c, lrc == kFlacNotHere ? RG_ERR_FORMAT : lrc, "%s", err.c_str());
+        }
+        std::vector<rg_track_desc> d;
+        std::vector<FlacCounts> counts;
+        size_t bytes = 0;
+        const int rc = stage_loaded(c, pool, n, &d, &bytes, &counts);
+        if (rc != RG_OK) return rc;
+        *arena_bytes = bytes;
+        for (size_t i = 0; i < n; ++i) {
+            descs[i] = d[i];
+            infos[i].frames = d[i].frames;
+            infos[i].audio_frames = counts[i].decoded;
+            infos[i].dropped_frames = counts[i].dropped;
+        }
+        if (bytes > arena_capacity) return rg_set_err(c, RG_ERR_INVALID_ARG, "arena capacity %zu < %zu bytes", arena_capacity, bytes);
+        if (bytes) RG_HIP(c, hipMemcpy(arena_out, c->d_arena.p, bytes, hipMemcpyDeviceToHost));
+        return RG_OK;
+    } catch (const std::bad_alloc &) {
+        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
+    }
 }

@@ -59,6 +59,8 @@ int load_flac(int route, const char *path, LoadedAudio *out, std::string *err) {
     }
     const uint32_t eb = flac_elem_bytes(si.bits_per_sample), sh = flac_shift(si.bits_per_sample);
     out->frames = di.frames;
+    out->flac_decoded = di.audio_frames;
+    out->flac_dropped = di.dropped_frames;
     out->flac_pcm.resize((size_t)di.frames * si.channels * eb);
     for (uint32_t ch = 0; ch < si.channels; ++ch) {
         const int32_t *src = planes[ch];

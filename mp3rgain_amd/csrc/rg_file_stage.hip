@@ -29,8 +29,10 @@ int arena_reserve_keep(rg_ctx *c, size_t need, size_t keep) {
 
 // the same for loaded files: WAV items take the de-interleave route, decoded MP3 items are planar f32 already and go
 // straight into the arena
-int stage_loaded(rg_ctx *c, const std::vector<LoadedAudio> &in, size_t n, std::vector<rg_track_desc> *descs, size_t *arena_bytes) {
+int stage_loaded(rg_ctx *c, const std::vector<LoadedAudio> &in, size_t n, std::vector<rg_track_desc> *descs, size_t *arena_bytes,
+                 std::vector<FlacCounts> *flac_counts) {
     std::vector<WavItem> items(n);
+    if (flac_counts) flac_counts->assign(n ? n : 1, FlacCounts{0, 0});
     // streams the loader pipeline has decoded already sit in [0, keep) of the arena; everything else goes behind them
     size_t keep = 0;
     for (size_t i = 0; i < n; ++i)
@@ -73,6 +75,7 @@ int stage_loaded(rg_ctx *c, const std::vector<LoadedAudio> &in, size_t n, std::v
             if (in[i].flac_frames.empty()) {  // the host decoder's PCM (or an empty stream)
                 if (!in[i].flac_pcm.empty()) RG_HIP(c, hipMemcpyAsync(dst, in[i].flac_pcm.data(), in[i].flac_pcm.size(), hipMemcpyHostToDevice, fs));
                 if (in[i].flac_pcm.empty()) (*descs)[i].frames = 0;
+                if (flac_counts) (*flac_counts)[i] = FlacCounts{in[i].flac_decoded, in[i].flac_dropped};
                 continue;
             }
             RgFlacDevStream st{};
@@ -122,7 +125,10 @@ int stage_loaded(rg_ctx *c, const std::vector<LoadedAudio> &in, size_t n, std::v
     if (!flac.empty()) {  // the device FLAC decoder writes PCM straight into the arena; the decoded lengths come back
         rc = rg_flacdev_decode(c, flac.data(), flac.size(), fs);
         if (rc != RG_OK) return rc;
-        for (size_t k = 0; k < flac.size(); ++k) (*descs)[flac_of[k]].frames = flac[k].samples;
+        for (size_t k = 0; k < flac.size(); ++k) {
+            (*descs)[flac_of[k]].frames = flac[k].samples;
+            if (flac_counts) (*flac_counts)[flac_of[k]] = FlacCounts{flac[k].decoded_frames, flac[k].dropped_frames};
+        }
     }
     // the host buffers are the caller's locals: the copies must have left them before this returns
     RG_HIP(c, hipStreamSynchronize(fs));

@@ -75,20 +75,18 @@ struct LoadedAudio {
     std::vector<rg_flac_frame> flac_frames;
     std::vector<uint8_t> flac_pcm;
     uint32_t flac_bps = 0;
+    uint32_t flac_decoded = 0, flac_dropped = 0;  // key 14 = 0: FLAC frames the host decoder decoded / dropped
     // ready for the next file; the vectors keep their capacity
     void reset() {
         wav.clear(); planar.clear(); is.clear(); units.clear(); main_stream.clear(); recs.clear(); file_bytes.clear();
-        flac_frames.clear(); flac_pcm.clear(); flac_bps = 0;
+        flac_frames.clear(); flac_pcm.clear(); flac_bps = 0; flac_decoded = flac_dropped = 0;
         sample_rate = channels = 0; frames = 0; n_units = 0; lsf = 0;
         kind = Wav; is_mp4 = false;
         arena_off = 0; walked_frames = 0; result_index = 0; n_audio_tracks = 1;
     }
 };
 
-// The arena format of FLAC PCM, the WAV route's convention: up to 16 bits S16 planar (<< 16 - bps), 17-24 bits S32 planar
-// (<< 32 - bps).  Both are exact powers of two, so the analysis sees the same normalised samples either way.
-inline uint32_t flac_elem_bytes(uint32_t bps) { return bps <= 16 ? 2u : 4u; }
-inline uint32_t flac_shift(uint32_t bps) { return bps <= 16 ? 16u - bps : 32u - bps; }
+// the arena format of FLAC PCM (rg_flac.h: flac_elem_bytes, flac_shift) as a track descriptor's
 inline uint16_t flac_format(uint32_t bps) { return bps <= 16 ? RG_FMT_S16_PLANAR : RG_FMT_S32_PLANAR; }
 
 constexpr int kFlacNotHere = 1;  // load_flac: a FLAC stream this library does not decode (the decoder command's to try)
@@ -117,7 +115,13 @@ inline int load_one(rg_ctx *c, const char *path, std::vector<LoadedAudio> *pool)
 
 // ---- rg_file_stage.hip --------------------------------------------------------------------------------------------------
 int arena_reserve_keep(rg_ctx *c, size_t need, size_t keep);
-int stage_loaded(rg_ctx *c, const std::vector<LoadedAudio> &in, size_t n, std::vector<rg_track_desc> *descs, size_t *arena_bytes);
+// FLAC frames of one input that decoded / were dropped (zero for an input that is not a FLAC stream)
+struct FlacCounts {
+    uint32_t decoded, dropped;
+};
+// `flac_counts`: null, or entry i <- the counts of input i (the parity hook rg_flac_stage_device_batch reports them)
+int stage_loaded(rg_ctx *c, const std::vector<LoadedAudio> &in, size_t n, std::vector<rg_track_desc> *descs, size_t *arena_bytes,
+                 std::vector<FlacCounts> *flac_counts = nullptr);
 
 // ---- rg_mp3_pipe.hip ----------------------------------------------------------------------------------------------------
 // The loader pipeline of tuning key 6 = 3 (the default).

@@ -16,6 +16,13 @@ int rg_flac_index_vec(const uint8_t *d, size_t len, std::vector<rg_flac_frame> *
 int rg_flac_decode_vec(const uint8_t *d, size_t len, const std::vector<rg_flac_frame> &frames, const rg_flac_info &si,
                        int32_t *const *planes, uint64_t capacity, rg_flac_info *out, std::vector<uint8_t> *good);
 
+namespace rgf {
+// The arena format of FLAC PCM, the WAV route's convention: up to 16 bits S16 planar (<< 16 - bps), 17-24 bits S32 planar
+// (<< 32 - bps).  Both are exact powers of two, so the analysis sees the same normalised samples either way.
+inline uint32_t flac_elem_bytes(uint32_t bps) { return bps <= 16 ? 2u : 4u; }
+inline uint32_t flac_shift(uint32_t bps) { return bps <= 16 ? 16u - bps : 32u - bps; }
+}  // namespace rgf
+
 #ifdef __HIP__
 #include <hip/hip_runtime.h>
 

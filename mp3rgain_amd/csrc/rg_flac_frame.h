@@ -157,6 +157,28 @@ struct RgFlacSink {
     }
 };
 
+// The Out of the analysis arena: planar elements of 2 or 4 bytes, each sample shifted left into its element (rg_flac.h:
+// flac_elem_bytes, flac_shift), plane `ch` of the stream `stride` elements behind plane ch - 1, this frame's first sample at
+// element `at`.  get() undoes put() exactly for every value of the stream's width -- the decorrelations read the first
+// channel back through it, for a CD rip through a 16-bit plane.  The device decode kernel (rg_flacdev.hip) writes through
+// it, and so does the host twin rg_flac_decode_arena (rg_flacdec.cpp).
+struct RgFlacArenaOut {
+    unsigned char *base;
+    uint64_t stride;
+    uint64_t at;
+    uint32_t elem, shift;
+    RG_FLAC_HD void put(uint32_t ch, uint32_t i, int32_t v) {
+        const uint64_t idx = (uint64_t)ch * stride + at + i;
+        if (elem == 2) reinterpret_cast<int16_t *>(base)[idx] = (int16_t)((uint32_t)v << shift);
+        else reinterpret_cast<int32_t *>(base)[idx] = (int32_t)((uint32_t)v << shift);
+    }
+    RG_FLAC_HD int32_t get(uint32_t ch, uint32_t i) const {
+        const uint64_t idx = (uint64_t)ch * stride + at + i;
+        if (elem == 2) return (int32_t)reinterpret_cast<const int16_t *>(base)[idx] >> shift;
+        return reinterpret_cast<const int32_t *>(base)[idx] >> shift;
+    }
+};
+
 // The residual of a predicted subframe, with the prediction applied as it is decoded.  ORDER > 0: history and
 // coefficients live in registers (compile-time indices only); ORDER < 0: the runtime order `order` (13..32) keeps them
 // in `ring` (32 history words, then 32 coefficients, `stride` apart: an LDS column per lane on the device).

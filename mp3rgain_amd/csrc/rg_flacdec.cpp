@@ -329,6 +329,42 @@ extern "C" int rg_flac_decode_s32(const void *data, size_t len, int32_t *const *
     }
 }
 
+extern "C" int rg_flac_decode_arena(const void *data, size_t len, void *out, size_t capacity_bytes, uint32_t *elem_bytes, rg_flac_info *info) {
+    if (!data || !info || !elem_bytes || (capacity_bytes && !out)) return fail(RG_FLAC_ERR_ARG, "null argument");
+    g_err[0] = 0;
+    try {
+        const uint8_t *d = (const uint8_t *)data;
+        std::vector<rg_flac_frame> v;
+        rg_flac_info si;
+        int rc = rg_flac_index_vec(d, len, &v, &si);
+        if (rc != RG_FLAC_OK) {
+            memset(info, 0, sizeof *info);
+            return rc;
+        }
+        // as on the device: which frames decode first (the plane stride is the decoded length), then the good ones into place
+        std::vector<uint8_t> good;
+        rc = rg_flac_decode_vec(d, len, v, si, nullptr, 0, info, &good);
+        if (rc != RG_FLAC_OK) return rc;
+        const uint32_t eb = rgf::flac_elem_bytes(si.bits_per_sample), sh = rgf::flac_shift(si.bits_per_sample);
+        *elem_bytes = eb;
+        if ((uint64_t)capacity_bytes < info->frames * si.channels * eb) return fail(RG_FLAC_ERR_CAPACITY, "output capacity too small");
+        std::vector<int32_t> ring(64);
+        uint64_t at = 0;
+        for (size_t k = 0; k < v.size(); ++k) {
+            if (!good[k]) continue;
+            const rg_flac_frame &f = v[k];
+            RgFlacArenaOut sink{static_cast<unsigned char *>(out), info->frames, at, eb, sh};
+            if (!rg_flac_decode_frame(d, len, f.offset, f.length, f.header_length, f.block_size, f.channel_assignment, si.channels,
+                                      si.bits_per_sample, ring.data(), 1, sink))
+                return fail(RG_FLAC_ERR_ARG, "a frame decodes into int32 planes but not through the arena sink");
+            at += f.block_size;
+        }
+        return RG_FLAC_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(RG_FLAC_ERR_ARG, "out of memory");
+    }
+}
+
 extern "C" int rg_flac_index_selfcheck(const void *data, size_t len) {
     if (!data) return fail(RG_FLAC_ERR_ARG, "null argument");
     try {

@@ -116,23 +116,6 @@ rg_flac_layout_kernel(const FlacDevFrame *__restrict__ frames, const FlacDevStre
     }
 }
 
-struct DevOut {
-    unsigned char *base;
-    uint64_t stride;
-    uint64_t at;
-    uint32_t elem, shift;
-    __device__ void put(uint32_t ch, uint32_t i, int32_t v) {
-        const uint64_t idx = (uint64_t)ch * stride + at + i;
-        if (elem == 2) reinterpret_cast<int16_t *>(base)[idx] = (int16_t)((uint32_t)v << shift);
-        else reinterpret_cast<int32_t *>(base)[idx] = (int32_t)((uint32_t)v << shift);
-    }
-    __device__ int32_t get(uint32_t ch, uint32_t i) const {
-        const uint64_t idx = (uint64_t)ch * stride + at + i;
-        if (elem == 2) return (int32_t)reinterpret_cast<const int16_t *>(base)[idx] >> shift;
-        return reinterpret_cast<const int32_t *>(base)[idx] >> shift;
-    }
-};
-
 __global__ void __launch_bounds__(kDecodeBlock)
 rg_flac_decode_kernel(const uint8_t *__restrict__ blob, uint64_t blob_len, const FlacDevFrame *__restrict__ frames, uint32_t n_frames,
                       const FlacDevStreamD *__restrict__ streams, const uint8_t *__restrict__ good, const uint64_t *__restrict__ out_off,
@@ -142,7 +125,7 @@ rg_flac_decode_kernel(const uint8_t *__restrict__ blob, uint64_t blob_len, const
     if (f >= n_frames || !good[f]) return;
     const FlacDevFrame fr = frames[f];
     const FlacDevStreamD st = streams[fr.stream];
-    DevOut out{reinterpret_cast<unsigned char *>(st.dst), results[fr.stream].samples, out_off[f], st.elem, st.shift};
+    RgFlacArenaOut out{reinterpret_cast<unsigned char *>(st.dst), results[fr.stream].samples, out_off[f], st.elem, st.shift};
     if (!rg_flac_decode_frame(blob, blob_len, fr.off, fr.len, fr.hlen, fr.bs, fr.assign, st.channels, st.bps, ring + threadIdx.x,
                               kDecodeBlock, out)) {
         dropped[f] = 1;

@@ -53,6 +53,9 @@ SYMBOLS = [
     ("rg_flac_index_selfcheck", C.c_int, [C.c_void_p, C.c_size_t]),
     ("rg_flac_last_error", C.c_char_p, []),
     ("rg_flac_decode_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(FlacInfo)]),
+    ("rg_flac_stage_device_batch", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(_capi.TrackDesc),
+                                             C.POINTER(FlacInfo), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("rg_flac_decode_arena", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(FlacInfo)]),
 ]
 
 
@@ -118,6 +121,25 @@ def decode(data: bytes) -> Tuple[int, int, np.ndarray, FlacInfo]:
     if rc != OK:
         raise FlacError(rc, L.rg_flac_last_error().decode())
     return int(di.sample_rate), int(di.bits_per_sample), out[:, :int(di.frames)], di
+
+
+def decode_arena(data: bytes) -> Tuple[List[np.ndarray], FlacInfo]:
+    """rg_flac_decode_arena, the host twin of the device decoder's output stage: the stream decoded through the arena sink
+    -> ([plane per channel: int16 (<= 16 bits per sample, << 16 - bps) or int32 (<< 32 - bps)], info)."""
+    L = _lib()
+    _, info = index(data)
+    ch = int(info.channels)
+    eb = 2 if info.bits_per_sample <= 16 else 4
+    arena = np.zeros(max(1, int(info.frames) * ch * eb), dtype=np.uint8)
+    di = FlacInfo()
+    got_eb = C.c_uint32()
+    rc = L.rg_flac_decode_arena(_buf(data), len(data), arena.ctypes.data, arena.size, C.byref(got_eb), C.byref(di))
+    if rc != OK:
+        raise FlacError(rc, L.rg_flac_last_error().decode())
+    assert got_eb.value == eb
+    n = int(di.frames)
+    dt = np.int16 if eb == 2 else np.int32
+    return [arena[c * n * eb:(c + 1) * n * eb].view(dt) for c in range(ch)], di
 
 
 def selfcheck(data: bytes) -> int:

@@ -687,6 +687,28 @@ class Analyzer:
         self._check(L.rg_flac_decode_device(self._ctx, flacdec._buf(data), len(data), planes, cap, C.byref(di)))
         return out[:, :int(di.frames)], di
 
+    def stage_flac_device(self, streams: Sequence[bytes]):
+        """FLAC streams in memory through the file route's loading and staging (rg_flac_stage_device_batch: tuning key 14
+        picks the device or the host decoder) -> (the arena as a uint8 array, [TrackDesc], [FlacInfo]): plane c of stream
+        i is arena[descs[i].offset_bytes + c * descs[i].frames * element size ...], int16 for S16 planar, int32 for S32."""
+        from . import flacdec
+
+        L = flacdec._lib()
+        n = len(streams)
+        bufs = [flacdec._buf(s) for s in streams]
+        ptrs = (C.c_void_p * max(1, n))(*[C.addressof(b) for b in bufs])
+        lens = (C.c_size_t * max(1, n))(*[len(s) for s in streams])
+        cap = 16
+        for s in streams:  # what the arena is laid out for: every walked frame, each stream rounded up to 16 bytes
+            info = flacdec.index(s)[1]
+            cap += (int(info.frames) * int(info.channels) * (2 if info.bits_per_sample <= 16 else 4) + 15) // 16 * 16
+        arena = np.zeros(cap, dtype=np.uint8)
+        descs = (_capi.TrackDesc * max(1, n))()
+        infos = (flacdec.FlacInfo * max(1, n))()
+        used = C.c_size_t()
+        self._check(L.rg_flac_stage_device_batch(self._ctx, n, ptrs, lens, descs, infos, arena.ctypes.data, arena.size, C.byref(used)))
+        return arena[:used.value], list(descs[:n]), list(infos[:n])
+
     def decode_mp3_bench(self, data: bytes, copies: int, reps: int = 5) -> dict:
         """rg_mp3_decode_bench: per-kernel HIP-event times of the device decode chain on `copies` copies of one stream."""
         ms = (C.c_double * 5)()
