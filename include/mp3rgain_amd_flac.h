@@ -16,7 +16,17 @@
  * reference decodes FLAC with symphonia, whose source is not in the reference tree; its handling of damaged FLAC could not
  * be compared, and this rule is the project's own.
  *
- * Host code (apart from rg_flac_decode_device and rg_flac_stage_device_batch), plain C types, no exceptions or aborts across the ABI.
+ * What is hashed (rg_flac_verify, rg_flac_md5_s32, rg_flac_md5_arena).  STREAMINFO carries the MD5 signature of the
+ * unencoded audio: RFC 1321 MD5, with its padding and 64-bit bit length, over the frames in order and within a frame the
+ * channels in order, each sample a signed two's-complement integer of B = (bps + 7) / 8 bytes, little-endian, sign-extended
+ * from bps bits (B is 1, 2 or 3 for the 4-24 bits this decoder takes).  A stream of `frames` frames hashes
+ * frames * channels * B bytes; zero frames give the MD5 of the empty message; a STREAMINFO field of sixteen zero bytes means
+ * "no signature".  In the analysis arena a FLAC sample lies left-justified in its element (16-bit planes for bps <= 16,
+ * << 16 - bps; 32-bit planes above, << 32 - bps; rg_flac_stage_device_batch); the sample value is the element shifted back
+ * arithmetically.
+ *
+ * Host code (apart from rg_flac_decode_device, rg_flac_stage_device_batch, route 1 of rg_flac_md5_arena and rg_flac_verify),
+ * plain C types, no exceptions or aborts across the ABI.
  */
 #ifndef MP3RGAIN_AMD_FLAC_H
 #define MP3RGAIN_AMD_FLAC_H
@@ -106,6 +116,50 @@ int rg_flac_stage_device_batch(void *ctx, size_t n, const void *const *data, con
  * set) when capacity_bytes < channels * frames * elem_bytes; RG_FLAC_ERR_ARG if a frame's verdict through this sink
  * differs from the host decoder's (it must not). */
 int rg_flac_decode_arena(const void *data, size_t len, void *out, size_t capacity_bytes, uint32_t *elem_bytes, rg_flac_info *info);
+
+/* STREAMINFO's MD5 signature into out[16] (behind an ID3v2 tag as rg_flac_scan skips it): 1 = a signature is set, 0 = the
+ * field is all zero (no signature), < 0 = an rg_flac_status (not a FLAC stream). */
+int rg_flac_stream_md5(const void *data, size_t len, uint8_t out[16]);
+
+/* The signature of right-justified planes as rg_flac_decode_s32 returns them ("What is hashed" above): RG_FLAC_OK, or
+ * RG_FLAC_ERR_ARG (1-8 channels, 4-24 bits per sample). */
+int rg_flac_md5_s32(const int32_t *const *planes, uint32_t channels, uint64_t frames, uint32_t bps, uint8_t out[16]);
+
+/* Test seam of the hash: the `n` streams that descs[i] (format S16 or S32 planar, the arena's left-justified form: the
+ * sample is the element >> (8 * element size - bps[i])) describe in the host arena `arena`, each hashed into
+ * digests[16 * i ..].  route 0: the host twin reads that form where it lies (`ctx` may be NULL); route 1: the arena is
+ * copied to the device and the kernel of the file route hashes it, one lane per stream (`ctx` is an rg_ctx).  A stream
+ * needs only sample alignment; RG_ERR_INVALID_ARG for one whose planes are not wholly inside the arena. */
+int rg_flac_md5_arena(void *ctx, int route, size_t n, const rg_track_desc *descs, const uint32_t *bps, const void *arena,
+                      size_t arena_bytes, uint8_t *digests /* [n][16] */);
+
+/* Measurement hook (tools/flac_md5_rate.py): `n` streams of `frames` frames of `channels` channels of 16-bit PCM, filled on
+ * the device, each at its own offset of one device arena.  After a warm-up, `reps` rounds of: the kernel over all n streams
+ * (dev_ms[r], HIP events around the launch), then the host twin over a host copy of the first `host_streams` (<= n) streams
+ * on `threads` host threads (host_ms[r]).  *mismatches: host digests that differ from the kernel's (it must be 0).  `ctx` is
+ * an rg_ctx. */
+int rg_flac_md5_rate(void *ctx, size_t n, uint64_t frames, uint32_t channels, size_t host_streams, uint32_t threads, uint32_t reps,
+                     double *dev_ms, double *host_ms, size_t *mismatches);
+
+/* rg_flac_verify: what `flac -t` gives.  The files are decoded by the very route the analysis uses -- the same loaders, the
+ * same groups (tuning key 13) for lists larger than the device, the device decoder (tuning key 14 = 1) or the host decoder
+ * (key 14 = 0) -- and the decoded PCM is hashed where it lies: in the analysis arena by a device kernel, one lane per
+ * stream, only the digests coming back (key 14 = 1), or on the host (key 14 = 0).  Both give the same bytes in `out`. */
+#define RG_FLAC_VERIFY_HAS_SIGNATURE 1u  /* STREAMINFO's MD5 is not all zero                          */
+#define RG_FLAC_VERIFY_MD5_MATCH     2u  /* set only with HAS_SIGNATURE: md5_decoded == md5_stream    */
+#define RG_FLAC_VERIFY_LENGTH_MATCH  4u  /* total_samples == 0 (unknown) or == frames                 */
+#define RG_FLAC_VERIFY_COMPLETE      8u  /* dropped_frames == 0                                       */
+typedef struct rg_flac_verify_result {
+    int32_t status;          /* RG_OK, or why there is no decode (text: rg_tracks_error(ctx, i))      */
+    uint32_t flags;
+    uint64_t frames;         /* PCM frames per channel that were decoded and hashed                   */
+    uint64_t total_samples;  /* STREAMINFO                                                            */
+    uint32_t audio_frames, dropped_frames;
+    uint8_t md5_stream[16], md5_decoded[16];
+} rg_flac_verify_result;     /* 64 bytes */
+/* A failing file fails alone: RG_ERR_IO (it cannot be opened), RG_ERR_FORMAT (not a native FLAC stream, or one of 25-32
+ * bits per sample; no decoder command is run), its record otherwise zero.  RG_OK whenever the call itself worked. */
+int rg_flac_verify(rg_ctx *ctx, const char *const *paths, size_t n, rg_flac_verify_result *out);
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,7 @@ class Options:  # src/main.rs:65-96
     true_peak: bool = False  # with --r128: report and clip-limit on the true peak
     loudness_range: bool = False  # with --r128 (--range): loudness range, maximum momentary and short-term loudness
     surround: bool = False   # with --r128 (--surround): BS.1770 channel weights from every file's channel layout
+    verify: bool = False     # this façade only (--verify): FLAC files against the MD5 signature of their STREAMINFO
     files: List[Path] = field(default_factory=list)
 
 
@@ -125,6 +126,8 @@ def parse_args(args: List[str], out, err) -> Options:
             o.loudness_range = True
         elif arg == "--surround":
             o.surround = True
+        elif arg == "--verify":  # not in the reference: a command of its own, like -s c
+            o.verify = True
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -445,6 +448,8 @@ class Cli:
                 return 1
         if o.assume_mpeg2 and self.talk:
             self.e("note: -f (assume MPEG2) is accepted for compatibility but has no effect")
+        if o.verify:
+            return self.cmd_verify()
         if o.max_amplitude_only:
             return self.cmd_max_amplitude()
         if o.stored_tag_mode == "delete":
@@ -462,6 +467,51 @@ class Cli:
         if o.gain_steps is not None:
             return self.cmd_apply(o.gain_steps)
         return self.cmd_info()
+
+    # ---- --verify (not in the reference): what `flac -t` gives, on the GPU -----------------------------------------
+    def cmd_verify(self) -> int:
+        """Every file decoded by the route the analysis uses (rg_flac_verify, on the first GPU) and the MD5 of its PCM compared
+        with the signature in its STREAMINFO.  Exit status 0 only when no file has a mismatch, dropped frames or an error; a
+        file without a signature does not fail."""
+        o = self.o
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            res = an.verify_flac(o.files)
+        if self.talk:
+            self.p(f"mp3rgain Verifying {len(o.files)} FLAC file(s)")
+            self.p()
+        results, failed = [], 0
+        for file, r in zip(o.files, res):
+            if r.error is not None:
+                verdict = str(r.error)
+            elif r.dropped_frames:
+                verdict = f"{r.dropped_frames} frames dropped"
+            elif r.has_signature and not r.md5_match:
+                verdict = "MD5 mismatch"
+            elif not r.length_match:
+                verdict = "length mismatch"
+            elif not r.has_signature:
+                verdict = "no signature"
+            else:
+                verdict = "verified"
+            bad = verdict not in ("verified", "no signature")
+            failed += bad
+            if o.output_format == "json":
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                else:
+                    d.update(verdict=verdict, verified=r.verified, has_signature=r.has_signature, md5_match=r.md5_match,
+                             length_match=r.length_match, complete=r.complete, frames=r.frames, total_samples=r.total_samples,
+                             dropped_frames=r.dropped_frames, md5_stream=r.md5_stream.hex(), md5_decoded=r.md5_decoded.hex())
+                results.append(d)
+            elif o.output_format == "tsv":
+                self.p(f"{_name(file)}\t{verdict}\t{r.frames}\t{r.total_samples}\t{r.dropped_frames}\t{r.md5_stream.hex()}\t{r.md5_decoded.hex()}")
+            elif bad or not o.quiet:
+                (self.e if r.error is not None else self.p)(f"{_name(file)} - {verdict}")
+        if o.output_format == "json":
+            _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+        return 1 if failed else 0
 
     # ---- find_max_amplitude, src/lib.rs:1174-1199 ------------------------------------------------------------
     def find_max_amplitude(self, file: Path):
@@ -1096,6 +1146,7 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "--true-peak With --r128: report and clip-limit on the true peak (4x / 2x oversampled)",
         "--range     With --r128: also report loudness range (EBU Tech 3342), maximum momentary and short-term loudness",
         "--surround  With --r128: weight every channel of a multichannel file by its layout (BS.1770: surrounds 1.41, LFE 0)",
+        "--verify    Verify FLAC files: decode on the GPU and compare the PCM's MD5 with the signature in STREAMINFO",
         "-v          Show version",
         "-h          Show this help",
     ):

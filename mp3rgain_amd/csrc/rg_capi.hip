@@ -318,6 +318,7 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_flac_blob.release();
     c->d_flac_work.release();
     c->h_flac_stage.release();
+    c->d_flac_md5.release();
     if (c->file_pool && c->file_pool_free) c->file_pool_free(c->file_pool);
     c->file_pool = nullptr;
     c->d_mp3_tab.release();

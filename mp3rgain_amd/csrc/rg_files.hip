@@ -22,6 +22,7 @@
 
 #include "rg_albums.h"
 #include "rg_files.h"
+#include "rg_flac_md5.h"
 #include "rg_r128.h"
 
 using namespace rgf;
@@ -466,6 +467,116 @@ extern "C" int rg_analyze_albums(rg_ctx *c, const char *const *paths, size_t n, 
         c->err = text;
     }
     return rc;
+}
+
+// ---- rg_flac_verify (include/mp3rgain_amd_flac.h) ---------------------------------------------------------------------------
+// one group of the call: files [first, first + n).  The route is the analysis's: load_many, stage_loaded, then the hash of
+// what lies in the arena (device decoder) or of the host decoder's PCM (tuning key 14 = 0), then the per-file records.
+static int flac_verify_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, rg_flac_verify_result *out) {
+    paths += first;
+    out += first;
+    std::vector<LoadedAudio> &in = file_pool(c, n);
+    std::vector<int> rcs;
+    std::vector<std::string> errs;
+    // no decoder command here: what this library does not decode itself is not a FLAC stream it could verify
+    std::string cmd;
+    cmd.swap(c->decoder_cmd);
+    int rc = load_many(c, paths, n, &in, &rcs, &errs, nullptr);
+    cmd.swap(c->decoder_cmd);
+    if (rc != RG_OK) return rc;
+    // everything that loaded and is not a WAV stream goes through the staging, as in an analysis call (what the loader
+    // pipeline has put into the arena already stays accounted for); only the FLAC streams are hashed
+    std::vector<size_t> slot;
+    for (size_t i = 0; i < n; ++i) {
+        out[i].status = rcs[i];
+        c->file_errors[first + i] = errs[i];
+        if (rcs[i] != RG_OK) continue;
+        if (in[i].kind == LoadedAudio::Wav) {
+            out[i].status = RG_ERR_FORMAT;
+            c->file_errors[first + i] = std::string("Not a native FLAC stream: ") + paths[i];
+            continue;
+        }
+        slot.push_back(i);
+    }
+    if (slot.empty()) return RG_OK;
+    for (size_t k = 0; k < slot.size(); ++k)
+        if (slot[k] != k) std::swap(in[k], in[slot[k]]);
+    auto fail_all = [&](int code) {
+        for (size_t k = 0; k < slot.size(); ++k) {
+            memset(&out[slot[k]], 0, sizeof out[slot[k]]);
+            out[slot[k]].status = code;
+            c->file_errors[first + slot[k]] = c->err;
+        }
+        return RG_OK;
+    };
+    std::vector<rg_track_desc> descs;
+    std::vector<FlacCounts> counts;
+    size_t arena_bytes = 0;
+    rc = stage_loaded(c, in, slot.size(), &descs, &arena_bytes, &counts);
+    if (rc != RG_OK) return fail_all(rc);
+    std::vector<RgFlacMd5Rec> recs;
+    std::vector<size_t> rec_of;  // record -> position in the batch
+    for (size_t k = 0; k < slot.size(); ++k) {
+        rg_flac_verify_result &r = out[slot[k]];
+        if (in[k].kind != LoadedAudio::Flac) {
+            r.status = RG_ERR_FORMAT;
+            c->file_errors[first + slot[k]] = std::string("Not a native FLAC stream: ") + paths[slot[k]];
+            continue;
+        }
+        rg_flac_info si;
+        (void)rg_flac_scan(in[k].file_bytes.data(), in[k].file_bytes.size(), &si);  // (load_flac has walked this stream)
+        if (rg_flac_stream_md5(in[k].file_bytes.data(), in[k].file_bytes.size(), r.md5_stream) == 1) r.flags |= RG_FLAC_VERIFY_HAS_SIGNATURE;
+        r.frames = descs[k].frames;
+        r.total_samples = si.total_samples;
+        r.audio_frames = counts[k].decoded;
+        r.dropped_frames = counts[k].dropped;
+        RgFlacMd5Rec rec;
+        if (in[k].flac_frames.empty()) {  // the host decoder's PCM, in the arena's format (or a stream without frames)
+            rg_track_desc d = descs[k];
+            d.offset_bytes = 0;
+            rc = rg_flac_md5_record(c, slot[k], d, in[k].flac_bps, in[k].flac_pcm.data(), in[k].flac_pcm.size(), &rec);
+            if (rc != RG_OK) return fail_all(rc);
+            rg_flac_md5_host(rec, r.md5_decoded);
+            continue;
+        }
+        rc = rg_flac_md5_record(c, slot[k], descs[k], in[k].flac_bps, c->d_arena.p, arena_bytes, &rec);
+        if (rc != RG_OK) return fail_all(rc);
+        recs.push_back(rec);
+        rec_of.push_back(k);
+    }
+    if (!recs.empty()) {  // on the stream the decode ran on
+        std::vector<uint8_t> dig(recs.size() * 16);
+        rc = rg_flac_md5_device(c, recs.data(), recs.size(), dig.data(), c->user_attached ? c->user_stream : c->slot().stream);
+        if (rc != RG_OK) return fail_all(rc);
+        for (size_t j = 0; j < recs.size(); ++j) memcpy(out[slot[rec_of[j]]].md5_decoded, &dig[16 * j], 16);
+    }
+    for (size_t k = 0; k < slot.size(); ++k) {
+        rg_flac_verify_result &r = out[slot[k]];
+        if (r.status != RG_OK) continue;
+        if ((r.flags & RG_FLAC_VERIFY_HAS_SIGNATURE) && memcmp(r.md5_stream, r.md5_decoded, 16) == 0) r.flags |= RG_FLAC_VERIFY_MD5_MATCH;
+        if (r.total_samples == 0 || r.total_samples == r.frames) r.flags |= RG_FLAC_VERIFY_LENGTH_MATCH;
+        if (r.dropped_frames == 0) r.flags |= RG_FLAC_VERIFY_COMPLETE;
+    }
+    return RG_OK;
+}
+
+extern "C" int rg_flac_verify(rg_ctx *c, const char *const *paths, size_t n, rg_flac_verify_result *out) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    c->file_errors.assign(n, std::string());
+    if (n) memset(out, 0, n * sizeof *out);
+    int rc = rg_bind_device(c);
+    if (rc != RG_OK) return rc;
+    try {
+        std::vector<std::pair<size_t, size_t>> groups;
+        file_groups(c, paths, n, &groups);
+        for (const auto &g : groups) {
+            rc = flac_verify_group(c, paths, g.first, g.second, out);
+            if (rc != RG_OK) return rc;
+        }
+    } catch (const std::bad_alloc &) {
+        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
+    }
+    return RG_OK;
 }
 
 // find_peak_amplitude (src/replaygain.rs:1140-1249): max |x| over ALL channels, no loudness analysis

@@ -45,6 +45,22 @@ class FlacFrame(C.Structure):
     ]
 
 
+class FlacVerifyRecord(C.Structure):
+    """rg_flac_verify_result."""
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("total_samples", C.c_uint64),
+        ("audio_frames", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("md5_stream", C.c_uint8 * 16),
+        ("md5_decoded", C.c_uint8 * 16),
+    ]
+
+
+VERIFY_HAS_SIGNATURE, VERIFY_MD5_MATCH, VERIFY_LENGTH_MATCH, VERIFY_COMPLETE = 1, 2, 4, 8
+
 SYMBOLS = [
     ("rg_flac_is_flac", C.c_int, [C.c_void_p, C.c_size_t]),
     ("rg_flac_scan", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(FlacInfo)]),
@@ -56,6 +72,13 @@ SYMBOLS = [
     ("rg_flac_stage_device_batch", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(_capi.TrackDesc),
                                              C.POINTER(FlacInfo), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("rg_flac_decode_arena", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(FlacInfo)]),
+    ("rg_flac_stream_md5", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("rg_flac_md5_s32", C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]),
+    ("rg_flac_md5_arena", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(_capi.TrackDesc), C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
+    ("rg_flac_md5_rate", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), C.POINTER(C.c_size_t)]),
+    ("rg_flac_verify", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(FlacVerifyRecord)]),
 ]
 
 
@@ -145,3 +168,44 @@ def decode_arena(data: bytes) -> Tuple[List[np.ndarray], FlacInfo]:
 def selfcheck(data: bytes) -> int:
     """rg_flac_index_selfcheck: 0 = the index and the decoder agree, 1 = they do not, < 0 = not decodable."""
     return int(_lib().rg_flac_index_selfcheck(_buf(data), len(data)))
+
+
+def stream_md5(data: bytes):
+    """STREAMINFO's MD5 signature (rg_flac_stream_md5): the 16 bytes, or None when the field is all zero (no signature)."""
+    L = _lib()
+    out = (C.c_uint8 * 16)()
+    rc = L.rg_flac_stream_md5(_buf(data), len(data), out)
+    if rc < 0:
+        raise FlacError(rc, L.rg_flac_last_error().decode())
+    return bytes(out) if rc == 1 else None
+
+
+def md5_planes(planes, bps: int) -> bytes:
+    """rg_flac_md5_s32: the signature of right-justified PCM, `planes` = [channels][frames] integers of `bps` bits."""
+    L = _lib()
+    arr = np.ascontiguousarray(planes, dtype=np.int32)
+    if arr.ndim != 2:
+        raise ValueError("planes must be [channels][frames]")
+    ch, n = arr.shape
+    ptrs = (C.c_void_p * max(1, ch))(*[arr[c].ctypes.data for c in range(ch)])
+    out = (C.c_uint8 * 16)()
+    rc = L.rg_flac_md5_s32(ptrs, ch, n, int(bps), out)
+    if rc != OK:
+        raise FlacError(rc, f"rg_flac_md5_s32: {ch} channels of {bps} bits per sample")
+    return bytes(out)
+
+
+def md5_arena(ctx, route: int, descs, bps, arena: np.ndarray):
+    """rg_flac_md5_arena: the streams `descs` ([TrackDesc], format S16 or S32 planar, left-justified) of `bps` ([int]) in the
+    host arena `arena` (uint8) -> [16 digest bytes per stream].  route 0: the host twin (`ctx` may be None), route 1: the kernel."""
+    L = _lib()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    b = (C.c_uint32 * max(1, n))(*[int(x) for x in bps])
+    out = (C.c_uint8 * (16 * max(1, n)))()
+    rc = L.rg_flac_md5_arena(ctx, int(route), n, d, b, arena.ctypes.data if arena.size else None, arena.size, out)
+    if rc != OK:
+        raise FlacError(rc, _capi.load().rg_last_error(ctx).decode())
+    raw = bytes(out)
+    return [raw[16 * i:16 * i + 16] for i in range(n)]

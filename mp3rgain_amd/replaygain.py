@@ -156,6 +156,26 @@ _NP_FMT = {
 
 
 @dataclass
+class FlacVerifyResult:
+    """One file of Analyzer.verify_flac (rg_flac_verify_result): the decoded PCM's MD5 against STREAMINFO's signature."""
+    has_signature: bool      # STREAMINFO's MD5 is not all zero
+    md5_match: bool          # only with has_signature: md5_decoded == md5_stream
+    length_match: bool       # total_samples is 0 (unknown) or equals frames
+    complete: bool           # no frame was dropped
+    frames: int              # PCM frames per channel that were decoded and hashed
+    total_samples: int       # STREAMINFO
+    audio_frames: int
+    dropped_frames: int
+    md5_stream: bytes
+    md5_decoded: bytes
+    error: Optional["ReplayGainError"] = None  # why there is no decode; every other field is then zero
+
+    @property
+    def verified(self) -> bool:
+        return self.error is None and self.has_signature and self.md5_match and self.length_match and self.complete
+
+
+@dataclass
 class PcmTrack:
     """Decoded audio of one file: planar channels (float32 in [-1,1], int16 or int32)."""
 
@@ -708,6 +728,48 @@ class Analyzer:
         used = C.c_size_t()
         self._check(L.rg_flac_stage_device_batch(self._ctx, n, ptrs, lens, descs, infos, arena.ctypes.data, arena.size, C.byref(used)))
         return arena[:used.value], list(descs[:n]), list(infos[:n])
+
+    def flac_md5_arena(self, route: int, descs, bps, arena):
+        """rg_flac_md5_arena, the seam of the FLAC MD5 kernel: the streams `descs` describe in the host arena `arena` ->
+        [digest bytes]; route 0 = the host twin, route 1 = the arena copied to this GPU and hashed by the kernel."""
+        from . import flacdec
+
+        try:
+            return flacdec.md5_arena(self._ctx, route, descs, bps, arena)
+        except flacdec.FlacError as e:
+            raise ReplayGainError(e.code, self._lib.rg_last_error(self._ctx).decode()) from None
+
+    def verify_flac(self, files) -> list:
+        """rg_flac_verify: every file decoded by the route the analysis uses and its PCM's MD5 compared with STREAMINFO's
+        signature -> [FlacVerifyResult]; a file that cannot be decoded carries its ReplayGainError in `.error`."""
+        from . import flacdec
+
+        L = flacdec._lib()
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (flacdec.FlacVerifyRecord * max(1, n))()
+        self._check(L.rg_flac_verify(self._ctx, paths, n, out))
+        res = []
+        for i in range(n):
+            r = out[i]
+            err = None
+            if r.status != 0:
+                err = ReplayGainError(int(r.status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
+            res.append(FlacVerifyResult(bool(r.flags & flacdec.VERIFY_HAS_SIGNATURE), bool(r.flags & flacdec.VERIFY_MD5_MATCH),
+                                        bool(r.flags & flacdec.VERIFY_LENGTH_MATCH), bool(r.flags & flacdec.VERIFY_COMPLETE),
+                                        int(r.frames), int(r.total_samples), int(r.audio_frames), int(r.dropped_frames),
+                                        bytes(r.md5_stream), bytes(r.md5_decoded), err))
+        return res
+
+    def verify_flac_raw(self, files) -> bytes:
+        """verify_flac's rg_flac_verify_result array as the C call left it (tests compare routes byte for byte)."""
+        from . import flacdec
+
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (flacdec.FlacVerifyRecord * max(1, n))()
+        self._check(flacdec._lib().rg_flac_verify(self._ctx, paths, n, out))
+        return bytes(out)[:n * C.sizeof(flacdec.FlacVerifyRecord)]
 
     def decode_mp3_bench(self, data: bytes, copies: int, reps: int = 5) -> dict:
         """rg_mp3_decode_bench: per-kernel HIP-event times of the device decode chain on `copies` copies of one stream."""
