@@ -8,6 +8,7 @@ undo tags), `mp4meta` (src/mp4meta.rs: ReplayGain tags in M4A files) and `cli` (
 `python -m mp3rgain_amd`).
 """
 from . import _capi, replaygain  # noqa: F401
+from .mp3verify import Mp3VerifyResult  # noqa: F401
 from .replaygain import (  # noqa: F401
     REPLAYGAIN_REFERENCE_DB,
     AlbumGainResult,

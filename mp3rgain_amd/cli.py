@@ -469,19 +469,65 @@ class Cli:
         return self.cmd_info()
 
     # ---- --verify (not in the reference): what `flac -t` gives, on the GPU -----------------------------------------
+    @staticmethod
+    def _is_mpeg(file) -> bool:
+        """What --verify sends to rg_mp3_verify: a bare MPEG Layer III stream, judged from the file's head (an ID3v2 tag and
+        64 KiB behind it).  Anything else, unreadable files included, goes to rg_flac_verify as before."""
+        from . import mp3verify
+
+        try:
+            with open(file, "rb") as f:
+                head = f.read(10)
+                want = 1 << 16
+                if len(head) == 10 and head[:3] == b"ID3" and not any(b & 0x80 for b in head[6:10]):
+                    want += (head[6] << 21) | (head[7] << 14) | (head[8] << 7) | head[9]
+                head += f.read(want)
+        except OSError:
+            return False
+        return mp3verify.is_mpeg(head)
+
     def cmd_verify(self) -> int:
-        """Every file decoded by the route the analysis uses (rg_flac_verify, on the first GPU) and the MD5 of its PCM compared
-        with the signature in its STREAMINFO.  Exit status 0 only when no file has a mismatch, dropped frames or an error; a
-        file without a signature does not fail."""
+        """Every file decoded by the route the analysis uses, on the first GPU.  FLAC (rg_flac_verify): the MD5 of its PCM
+        compared with the signature in its STREAMINFO.  MPEG Layer III (rg_mp3_verify): dropped frames, frame CRCs, and the
+        LAME extension's music length, music CRC and tag CRC.  Exit status 0 only when no file fails; a file without a
+        signature or checksum does not fail.  TSV, one row per file and no header: a FLAC row is `file, verdict, frames,
+        total samples, dropped frames, stored MD5, decoded MD5`; an MP3 row is `file, verdict, "mp3", audio frames, Xing frames,
+        dropped frames, failed frame CRCs, stored music CRC, computed music CRC`, told apart by the word in its third field."""
         o = self.o
         devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        is_mp3 = [self._is_mpeg(f) for f in o.files]
+        res = [None] * len(o.files)
         with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
-            res = an.verify_flac(o.files)
+            flac_at = [i for i, m in enumerate(is_mp3) if not m]
+            mp3_at = [i for i, m in enumerate(is_mp3) if m]
+            if flac_at or not mp3_at:
+                for i, r in zip(flac_at, an.verify_flac([o.files[i] for i in flac_at])):
+                    res[i] = r
+            if mp3_at:
+                for i, r in zip(mp3_at, an.verify_mp3([o.files[i] for i in mp3_at])):
+                    res[i] = r
         if self.talk:
-            self.p(f"mp3rgain Verifying {len(o.files)} FLAC file(s)")
+            self.p(f"mp3rgain Verifying {len(o.files)} {'' if any(is_mp3) else 'FLAC '}file(s)")
             self.p()
         results, failed = [], 0
-        for file, r in zip(o.files, res):
+        for file, r, mp3 in zip(o.files, res, is_mp3):
+            if mp3:
+                verdict, bad = r.verdict, r.failed
+                failed += bad
+                if o.output_format == "json":
+                    d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                    if r.error is not None:
+                        d["error"] = str(r.error)
+                    else:
+                        d.update(verdict=verdict, verified=r.verified, **r.as_dict())
+                    results.append(d)
+                elif o.output_format == "tsv":
+                    # the third field names the kind: a FLAC row (below, unchanged) has a frame count there, never a word
+                    self.p(f"{_name(file)}\t{verdict}\tmp3\t{r.audio_frames}\t{r.xing_frames}\t{r.dropped_frames}\t{r.frame_crc_failed}\t"
+                           f"{r.music_crc_stored:04x}\t{r.music_crc_computed:04x}")
+                elif bad or not o.quiet:
+                    (self.e if r.error is not None else self.p)(f"{_name(file)} - {verdict}")
+                continue
             if r.error is not None:
                 verdict = str(r.error)
             elif r.dropped_frames:
@@ -1147,6 +1193,7 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "--range     With --r128: also report loudness range (EBU Tech 3342), maximum momentary and short-term loudness",
         "--surround  With --r128: weight every channel of a multichannel file by its layout (BS.1770: surrounds 1.41, LFE 0)",
         "--verify    Verify FLAC files: decode on the GPU and compare the PCM's MD5 with the signature in STREAMINFO",
+        "            MP3 files: dropped frames, frame CRCs, and the LAME tag's music length, music CRC and tag CRC",
         "-v          Show version",
         "-h          Show this help",
     ):

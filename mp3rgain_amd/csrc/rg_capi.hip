@@ -319,6 +319,8 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_flac_work.release();
     c->h_flac_stage.release();
     c->d_flac_md5.release();
+    c->d_mp3_crc.release();
+    c->h_mp3_crc.release();
     if (c->file_pool && c->file_pool_free) c->file_pool_free(c->file_pool);
     c->file_pool = nullptr;
     c->d_mp3_tab.release();

@@ -188,6 +188,9 @@ struct rg_ctx {
     DevBuf<unsigned char> d_flac_work;       // per frame: good / dropped flags and output offsets; per stream: results
     PinnedBuf<unsigned char> h_flac_stage;   // pinned staging of d_flac_blob, and the results coming back
     DevBuf<unsigned char> d_flac_md5;        // rg_flac_md5.hip: [per-stream records | digests] of one launch
+    DevBuf<unsigned char> d_mp3_crc;         // rg_mp3_crc.hip: [bytes | range records | frame offsets | tile CRCs | results] of one launch
+    PinnedBuf<unsigned char> h_mp3_crc;      // pinned staging of d_mp3_crc's upload, and the results coming back
+    bool keep_mpeg_bytes = false;            // only while rg_mp3_verify runs: the loader pipeline keeps an MPEG stream's bytes as read
     int32_t file_track_index = -1;           // Some(idx) of the file-level call in progress (src/replaygain.rs:838-851); -1 = None
     unsigned loader_threads = 0;             // tuning key 7: host threads of the file loaders; 0 = every core this process may use
     // Routing knobs of the file layer.  The environment is read ONCE, at rg_create (rg_capi.hip: read_env_defaults; getenv is

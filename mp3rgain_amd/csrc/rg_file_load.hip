@@ -151,6 +151,7 @@ int decode_mpeg_host(int gpu_decode, const std::vector<uint8_t> &bytes, const rg
     out->sample_rate = di.sample_rate;
     out->channels = di.channels;
     out->frames = di.frames;
+    out->mp3_skipped = di.skipped_frames;
     if (gpu_decode) out->lsf = di.mpeg_version == 1 ? 0u : 1u;
     out->kind = gpu_decode ? LoadedAudio::Split : LoadedAudio::Planar;
     return rc;
@@ -258,6 +259,7 @@ int load_audio_for_impl(const std::string &decoder_cmd, int gpu_decode, const ch
                 for (size_t i = 0; i < got && i < n_au; ++i) es.insert(es.end(), bytes.begin() + (ptrdiff_t)off[i], bytes.begin() + (ptrdiff_t)(off[i] + sz[i]));
                 bytes.swap(es);
                 mp4_mpeg_audio = true;
+                out->mpeg_in_mp4 = true;
             }
         }
     }

@@ -76,6 +76,8 @@ struct LoadedAudio {
     std::vector<uint8_t> flac_pcm;
     uint32_t flac_bps = 0;
     uint32_t flac_decoded = 0, flac_dropped = 0;  // key 14 = 0: FLAC frames the host decoder decoded / dropped
+    uint32_t mp3_skipped = 0;    // Planar / Split: frames the host's decoder or frame walk dropped (rg_mp3_stream_info::skipped_frames)
+    bool mpeg_in_mp4 = false;    // the MPEG stream is the selected track of an MP4 file, not the file itself
     // ready for the next file; the vectors keep their capacity
     void reset() {
         wav.clear(); planar.clear(); is.clear(); units.clear(); main_stream.clear(); recs.clear(); file_bytes.clear();
@@ -83,6 +85,7 @@ struct LoadedAudio {
         sample_rate = channels = 0; frames = 0; n_units = 0; lsf = 0;
         kind = Wav; is_mp4 = false;
         arena_off = 0; walked_frames = 0; result_index = 0; n_audio_tracks = 1;
+        mp3_skipped = 0; mpeg_in_mp4 = false;
     }
 };
 

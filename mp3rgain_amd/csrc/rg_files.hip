@@ -23,6 +23,7 @@
 #include "rg_albums.h"
 #include "rg_files.h"
 #include "rg_flac_md5.h"
+#include "rg_mp3verify.h"
 #include "rg_r128.h"
 
 using namespace rgf;
@@ -571,6 +572,141 @@ extern "C" int rg_flac_verify(rg_ctx *c, const char *const *paths, size_t n, rg_
         file_groups(c, paths, n, &groups);
         for (const auto &g : groups) {
             rc = flac_verify_group(c, paths, g.first, g.second, out);
+            if (rc != RG_OK) return rc;
+        }
+    } catch (const std::bad_alloc &) {
+        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
+    }
+    return RG_OK;
+}
+
+// ---- rg_mp3_verify (include/mp3rgain_amd_mp3verify.h) ---------------------------------------------------------------------
+// one group of the call.  The decode side is the analysis's (load_many without a decoder command, stage_loaded), so how many
+// frames were dropped is the route's own verdict; the loader keeps the bytes of MPEG streams as read while this runs.  The
+// checksums: one upload of the group's bytes with their range and frame tables and the kernels of rg_mp3_crc.hip, on the
+// stream the decode ran on; with tuning key 6 = 0 (the host decoder) the host twin.
+static int mp3_verify_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, rg_mp3_verify_result *out) {
+    paths += first;
+    out += first;
+    std::vector<LoadedAudio> &in = file_pool(c, n);
+    std::vector<int> rcs;
+    std::vector<std::string> errs;
+    struct Quiet {  // no decoder command; MPEG bytes kept
+        rg_ctx *c;
+        std::string cmd;
+        explicit Quiet(rg_ctx *c) : c(c) { cmd.swap(c->decoder_cmd); c->keep_mpeg_bytes = true; }
+        ~Quiet() { cmd.swap(c->decoder_cmd); c->keep_mpeg_bytes = false; }
+    };
+    int rc;
+    {
+        Quiet q(c);
+        rc = load_many(c, paths, n, &in, &rcs, &errs, nullptr);
+    }
+    if (rc != RG_OK) return rc;
+    std::vector<size_t> slot;
+    for (size_t i = 0; i < n; ++i) {
+        out[i].status = rcs[i];
+        c->file_errors[first + i] = errs[i];
+        if (rcs[i] != RG_OK) continue;
+        const bool mpeg = in[i].kind == LoadedAudio::Planar || in[i].kind == LoadedAudio::Split || in[i].kind == LoadedAudio::Staged;
+        if (!mpeg || in[i].mpeg_in_mp4) {
+            out[i].status = RG_ERR_FORMAT;
+            c->file_errors[first + i] = std::string("Not a bare MPEG Layer III stream: ") + paths[i];
+            continue;
+        }
+        slot.push_back(i);
+    }
+    if (slot.empty()) return RG_OK;
+    for (size_t k = 0; k < slot.size(); ++k)
+        if (slot[k] != k) std::swap(in[k], in[slot[k]]);
+    const size_t m = slot.size();
+    auto fail_all = [&](int code) {
+        for (size_t k = 0; k < m; ++k) {
+            memset(&out[slot[k]], 0, sizeof out[slot[k]]);
+            out[slot[k]].status = code;
+            c->file_errors[first + slot[k]] = c->err;
+        }
+        return RG_OK;
+    };
+    std::vector<rg_track_desc> descs;
+    size_t arena_bytes = 0;
+    rc = stage_loaded(c, in, m, &descs, &arena_bytes);
+    if (rc != RG_OK) return fail_all(rc);
+    std::vector<RgMp3VerifyPlan> plans(m);
+    std::vector<uint32_t> dropped(m, 0);
+    std::vector<char> live(m, 0);
+    for (size_t k = 0; k < m; ++k) {
+        const LoadedAudio &la = in[k];
+        if (rg_mp3_verify_plan(la.file_bytes.data(), la.file_bytes.size(), &plans[k]) != RG_OK) {
+            out[slot[k]].status = RG_ERR_FORMAT;
+            c->file_errors[first + slot[k]] = std::string("Not a bare MPEG Layer III stream: ") + paths[slot[k]];
+            continue;
+        }
+        live[k] = 1;
+        const uint32_t spf = plans[k].si.samples_per_frame ? plans[k].si.samples_per_frame : 1152;
+        dropped[k] = la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
+    }
+    std::vector<uint16_t> music(m, 0);
+    std::vector<uint32_t> failed(m, 0);
+    if (c->gpu_mp3_decode == 0) {  // the host twin
+        for (size_t k = 0; k < m; ++k) {
+            if (!live[k]) continue;
+            const uint8_t *d = in[k].file_bytes.data();
+            music[k] = rg_mp3_crc_range_host(d, plans[k].music_off, plans[k].music_len);
+            for (uint64_t o : plans[k].prot) failed[k] += rg_mp3_frame_crc_host(d, in[k].file_bytes.size(), o) ? 0u : 1u;
+        }
+    } else {
+        std::vector<const uint8_t *> parts(m);
+        std::vector<uint64_t> part_off(m), part_len(m), r_off(m), r_len(m), f_off;
+        std::vector<size_t> f_of;
+        uint64_t total = 0;
+        for (size_t k = 0; k < m; ++k) {
+            parts[k] = in[k].file_bytes.data();
+            part_off[k] = total;
+            part_len[k] = live[k] ? in[k].file_bytes.size() : 0;
+            r_off[k] = total + (live[k] ? plans[k].music_off : 0);
+            r_len[k] = live[k] ? plans[k].music_len : 0;
+            if (live[k])
+                for (uint64_t o : plans[k].prot) {
+                    f_off.push_back(total + o);
+                    f_of.push_back(k);
+                }
+            total = (total + part_len[k] + 15) & ~(uint64_t)15;
+        }
+        std::vector<uint8_t> ok(f_off.size() ? f_off.size() : 1);
+        RgMp3CrcJob job;
+        job.parts = parts.data();
+        job.part_off = part_off.data();
+        job.part_len = part_len.data();
+        job.n_parts = m;
+        job.nbytes = total;
+        job.range_off = r_off.data();
+        job.range_len = r_len.data();
+        job.n_ranges = m;
+        job.frame_off = f_off.data();
+        job.n_frames = f_off.size();
+        job.crc_out = music.data();
+        job.ok_out = ok.data();
+        rc = rg_mp3_crc_device(c, job, c->user_attached ? c->user_stream : c->slot().stream);
+        if (rc != RG_OK) return fail_all(rc);
+        for (size_t j = 0; j < f_off.size(); ++j) failed[f_of[j]] += ok[j] ? 0u : 1u;
+    }
+    for (size_t k = 0; k < m; ++k)
+        if (live[k]) rg_mp3_verify_fill(in[k].file_bytes.data(), in[k].file_bytes.size(), plans[k], dropped[k], music[k], failed[k], &out[slot[k]]);
+    return RG_OK;
+}
+
+extern "C" int rg_mp3_verify(rg_ctx *c, const char *const *paths, size_t n, rg_mp3_verify_result *out) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    c->file_errors.assign(n, std::string());
+    if (n) memset(out, 0, n * sizeof *out);
+    int rc = rg_bind_device(c);
+    if (rc != RG_OK) return rc;
+    try {
+        std::vector<std::pair<size_t, size_t>> groups;
+        file_groups(c, paths, n, &groups);
+        for (const auto &g : groups) {
+            rc = mp3_verify_group(c, paths, g.first, g.second, out);
             if (rc != RG_OK) return rc;
         }
     } catch (const std::bad_alloc &) {

@@ -268,6 +268,7 @@ bool PipeCall::classify(size_t i, Mp3Scratch &sc, uint64_t *units, double *tl) {
     rg_mp3_stream_info si;
     uint64_t main_len = 0;
     tl[1] = trace ? now() : 0.0;
+    if (c->keep_mpeg_bytes && !mp4) la.file_bytes.assign(sc.p, sc.p + len);  // rg_mp3_verify: the compaction below works in place
     if (mp4 || rg_mp3_compact_stream(sc.p, len, &sc.slots, &sc.tiles, &main_len, &si) != RG_MP3DEC_OK || si.audio_frames == 0) {
         (*rcs)[i] = load_audio_for(cmd, 2, path, &la, &err, track_index, flac_route);  // the decoder command, or the reference's probe error
         return false;

@@ -935,6 +935,29 @@ extern "C" int rg_mp3_scan(const void *data, size_t len, rg_mp3_stream_info *out
     return RG_MP3DEC_OK;
 }
 
+// rg_mp3verify.h: the walk of rg_mp3_scan with the places it visits.  offsets[k] (k < cap): where audio frame k starts;
+// *n_frames: how many there are; *last_end: where the last one ends (first_frame_offset when there is none).
+extern "C" int rg_mp3_walk_offsets(const void *data, size_t len, uint64_t *offsets, size_t cap, size_t *n_frames, uint64_t *last_end,
+                                   rg_mp3_stream_info *out) {
+    RG_NEED_FMA();
+    if (!data || !out || !n_frames || !last_end || (cap && !offsets)) return fail(RG_MP3DEC_ERR_ARG, "null argument");
+    g_err[0] = 0;
+    const uint8_t *d = (const uint8_t *)data;
+    size_t n = 0;
+    uint64_t end = 0;
+    const int rc = walk_frames(d, len, out, [&](const uint8_t *f, const Header &h) {
+        if (n < cap) offsets[n] = (uint64_t)(f - d);
+        ++n;
+        end = (uint64_t)(f - d) + (uint64_t)h.frame_bytes;
+    });
+    if (rc != RG_MP3DEC_OK) return rc;
+    out->audio_frames = (uint32_t)n;
+    out->frames = (uint64_t)n * out->samples_per_frame;
+    *n_frames = n;
+    *last_end = n ? end : out->first_frame_offset;
+    return RG_MP3DEC_OK;
+}
+
 extern "C" int rg_mp3_decode_f32(const void *data, size_t len, float *ch0, float *ch1, uint64_t capacity,
                                  rg_mp3_stream_info *out) {
     RG_NEED_FMA();

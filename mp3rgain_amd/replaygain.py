@@ -771,6 +771,52 @@ class Analyzer:
         self._check(flacdec._lib().rg_flac_verify(self._ctx, paths, n, out))
         return bytes(out)[:n * C.sizeof(flacdec.FlacVerifyRecord)]
 
+    def verify_mp3(self, files) -> list:
+        """rg_mp3_verify: every file decoded by the route the analysis uses, its dropped frames counted, and the LAME music
+        CRC, the info tag's CRC and the frame CRCs computed on this GPU -> [mp3verify.Mp3VerifyResult]; a file that is not a
+        bare MPEG Layer III stream or cannot be opened carries its ReplayGainError in `.error`."""
+        from . import mp3verify
+
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (mp3verify.Mp3VerifyRecord * max(1, n))()
+        self._check(mp3verify._lib().rg_mp3_verify(self._ctx, paths, n, out))
+        res = []
+        for i in range(n):
+            err = None
+            if out[i].status != 0:
+                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
+            res.append(mp3verify.result_of(out[i], err))
+        return res
+
+    def verify_mp3_raw(self, files) -> bytes:
+        """verify_mp3's rg_mp3_verify_result array as the C call left it (tests compare routes byte for byte)."""
+        from . import mp3verify
+
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (mp3verify.Mp3VerifyRecord * max(1, n))()
+        self._check(mp3verify._lib().rg_mp3_verify(self._ctx, paths, n, out))
+        return bytes(out)[:n * C.sizeof(mp3verify.Mp3VerifyRecord)]
+
+    def mp3_crc_ranges(self, route: int, offsets, lengths, data):
+        """rg_mp3_crc_ranges, the seam of the CRC-16/ARC chunk and fold kernels (route 1) and their host twin (route 0)."""
+        from . import mp3verify
+
+        try:
+            return mp3verify.crc_ranges(self._ctx, route, offsets, lengths, data)
+        except mp3verify.Mp3VerifyError as e:
+            raise ReplayGainError(e.code, self._lib.rg_last_error(self._ctx).decode()) from None
+
+    def mp3_frame_crc_check(self, route: int, frame_offsets, data):
+        """rg_mp3_frame_crc_check, the seam of the frame-CRC kernel (route 1) and its host twin (route 0)."""
+        from . import mp3verify
+
+        try:
+            return mp3verify.frame_crc_check(self._ctx, route, frame_offsets, data)
+        except mp3verify.Mp3VerifyError as e:
+            raise ReplayGainError(e.code, self._lib.rg_last_error(self._ctx).decode()) from None
+
     def decode_mp3_bench(self, data: bytes, copies: int, reps: int = 5) -> dict:
         """rg_mp3_decode_bench: per-kernel HIP-event times of the device decode chain on `copies` copies of one stream."""
         ms = (C.c_double * 5)()
