@@ -38,9 +38,10 @@ struct RgR128TrackDev {
 
 struct rg_ctx;
 // Loudness (and true peak) of n tracks whose PCM is on the device.  keep_for_album: the tracks' hop energies stay on the
-// device until rg_r128_album_end gates their union (call rg_r128_album_reset first).  dyn_out (without keep_for_album) and
-// dyn_out / album_dyn_out of rg_r128_album_end (every kept track, in input order): nullptr, or loudness range and maxima
-// are computed too (rg_r128_range.hip) after the launches of the plain call, which do not change; st_z_out goes with them.
+// device until rg_r128_album_end runs the album stage over them (rg_r128_albums_stage with one album; call
+// rg_r128_album_reset first).  dyn_out (without keep_for_album) and dyn_out / album_dyn_out of rg_r128_album_end (every
+// kept track, in input order): nullptr, or loudness range and maxima are computed too (rg_r128_range.hip) after the
+// launches of the plain call, which do not change; st_z_out goes with them.
 // tr_out: nullptr, or the tracks' device descriptors go there (rg_r128_albums_stage reads them); their hop energies are in
 // the context's own buffer until the next call, or, with e_out, in a buffer of their own that the caller frees (hipFree).
 // weights: nullptr (every track by the context's channel mode: a pair, or rg_r128_layout_weights(channels, 0)), or one entry
@@ -72,11 +73,14 @@ void rg_r128_album_reset(rg_ctx *c);
 int rg_r128_album_end(rg_ctx *c, int want_true_peak, rg_r128_album_result *album_out, rg_r128_dynamics *dyn_out = nullptr,
                       rg_r128_dynamics *album_dyn_out = nullptr, double *st_z_out = nullptr);
 
+// the absolute gate of both measures, -70 LUFS as a mean square (rg_r128.hip)
+double rg_r128_abs_gate();
+
 // rg_r128_range.hip: loudness range and momentary / short-term maxima of n tracks whose hop energies (tr[i].e) are on the
-// device; res[i].flags marks the tracks that are not finite.  album_out: nullptr, or the n tracks are one album too.
-// *slot holds the stage's device buffers between calls (rg_r128_range_free).  album_select: tuning key 2.
-int rg_r128_dynamics_run(rg_ctx *c, void **slot, int album_select, const RgR128TrackDev *tr, const rg_r128_track_result *res,
-                         size_t n, rg_r128_dynamics *out, rg_r128_dynamics *album_out, double *st_z_out);
+// device, waited for; res[i].flags marks the tracks that are not finite.  *slot holds the stage's device buffers between
+// calls (rg_r128_range_free).  Albums are rg_r128_albums_stage's.
+int rg_r128_dynamics_run(rg_ctx *c, void **slot, const RgR128TrackDev *tr, const rg_r128_track_result *res, size_t n,
+                         rg_r128_dynamics *out, double *st_z_out);
 void rg_r128_dynamics_none(rg_r128_dynamics *d);  // the values of a track or an album without blocks
 void rg_r128_range_free(void *slot);
 void rg_r128_dynamics_nan(rg_r128_dynamics *d);   // the values of a track or an album that is not finite
@@ -92,7 +96,7 @@ struct RgR128RangeDev {
 };
 int rg_r128_range_tracks(rg_ctx *c, void **slot, const RgR128TrackDev *tr, size_t n, RgR128RangeDev *dev);
 
-// rg_r128_albums.hip: the album stage of many albums at once.  tr / res: n tracks whose hop energies are on the device;
+// rg_r128_albums.hip: the album stage of one album or of many at once.  tr / res: n tracks whose hop energies are on the device;
 // album a is tracks [first[a], first[a + 1]), first[n_albums] <= n (tracks past it belong to no album and get their own
 // dynamics only).  albums_dyn_out: nullptr, or loudness range and maxima of every track (dyn_out, may be nullptr) and every
 // album are computed too.  Empty albums get the record of rg_r128_analyze_album for n = 0.

@@ -317,38 +317,29 @@ rg_r128_truepeak_kernel(const RgR128TrackDev *__restrict__ tracks, const uint32_
 }
 
 // =================================================================================================
-// Gate kernel: one workgroup per track (blocks 0 .. track_blocks-1) and one for the album (the union of the blocks of the
-// tracks listed in album_list, in list order).  Block values from hop energies in a fixed order, both gates, the logarithm.
-// Every thread sums its blocks in ascending order and the workgroup folds the 256 partial sums in a fixed tree: the same
-// input gives the same bits on every run.
+// Gate kernel: one workgroup per track.  Block values from hop energies in a fixed order, both gates, the logarithm.  Every
+// thread sums its blocks in ascending order and the workgroup folds the 256 partial sums in a fixed tree: the same input
+// gives the same bits on every run.  (An album's union of blocks is rg_r128a_gate_kernel's, rg_r128_albums.hip.)
 __global__ void __launch_bounds__(256)
-rg_r128_gate_kernel(const RgR128TrackDev *__restrict__ tracks, const uint32_t track_blocks, const uint32_t *__restrict__ album_list,
-                    const uint32_t n_album, const double abs_gate, const uint32_t *__restrict__ peak_bits,
+rg_r128_gate_kernel(const RgR128TrackDev *__restrict__ tracks, const double abs_gate, const uint32_t *__restrict__ peak_bits,
                     const uint32_t *__restrict__ tp_bits /* nullptr: true peak not asked for */, const uint32_t *__restrict__ flags,
-                    rg_r128_track_result *__restrict__ out, rg_r128_album_result *__restrict__ album_out,
-                    double *__restrict__ block_z /* nullptr, or every track's blocks */) {
+                    rg_r128_track_result *__restrict__ out, double *__restrict__ block_z /* nullptr, or every track's blocks */) {
     __shared__ double sh_sum[256];
     __shared__ uint32_t sh_cnt[256];
-    const bool album = blockIdx.x >= track_blocks;
-    const uint32_t n_list = album ? n_album : 1u;
+    const RgR128TrackDev &T = tracks[blockIdx.x];
+    const uint32_t nb = T.H > 3u ? T.H - 3u : 0u;
     double thr = abs_gate;
     double sum = 0.0;
-    uint32_t cnt = 0, total = 0;
+    uint32_t cnt = 0;
     for (int pass = 0; pass < 2; ++pass) {
         sum = 0.0;
         cnt = 0;
-        total = 0;
-        for (uint32_t k = 0; k < n_list; ++k) {
-            const RgR128TrackDev &T = tracks[album ? album_list[k] : blockIdx.x];
-            const uint32_t nb = T.H > 3u ? T.H - 3u : 0u;
-            total += nb;
-            for (uint32_t b = threadIdx.x; b < nb; b += 256) {
-                const double z = r128_block_z(T, b);
-                if (pass == 0 && !album && block_z) block_z[T.z_base + b] = z;
-                if (z >= abs_gate && z >= thr) {
-                    sum += z;
-                    ++cnt;
-                }
+        for (uint32_t b = threadIdx.x; b < nb; b += 256) {
+            const double z = r128_block_z(T, b);
+            if (pass == 0 && block_z) block_z[T.z_base + b] = z;
+            if (z >= abs_gate && z >= thr) {
+                sum += z;
+                ++cnt;
             }
         }
         r128_fold(sh_sum, sh_cnt, sum, cnt);
@@ -361,18 +352,6 @@ rg_r128_gate_kernel(const RgR128TrackDev *__restrict__ tracks, const uint32_t tr
         lufs = -0.691 + 10.0 * log10(sum / (double)cnt);
         gain = RG_R128_REFERENCE_LUFS - lufs;
     }
-    if (album) {  // peaks, and the NaN of an album with a track that is not finite, are the host's (it has the tracks' results)
-        rg_r128_album_result a;
-        a.loudness_lufs = lufs;
-        a.gain_db = gain;
-        a.sample_peak = 0.0;
-        a.true_peak = nan;
-        a.blocks = total;
-        a.blocks_gated = cnt;
-        *album_out = a;
-        return;
-    }
-    const RgR128TrackDev &T = tracks[blockIdx.x];
     rg_r128_track_result r;
     const uint32_t fl = flags[T.index];
     r.loudness_lufs = fl ? nan : lufs;
@@ -383,7 +362,7 @@ rg_r128_gate_kernel(const RgR128TrackDev *__restrict__ tracks, const uint32_t tr
                                                     : R128Fmt<RG_FMT_S32_PLANAR>::peak_value(pb);
     r.true_peak = !tp_bits ? nan : T.tp_factor == 1 ? r.sample_peak : (double)__uint_as_float(tp_bits[T.index]);
     r.sample_rate = T.sample_rate;
-    r.blocks = total;
+    r.blocks = nb;
     r.blocks_gated = cnt;
     r.flags = fl;
     out[T.index] = r;
@@ -402,7 +381,6 @@ struct R128State {
     DevBuf<unsigned char> d_desc;
     DevBuf<uint32_t> d_words;  // [sample peak | true peak | flags] x n
     DevBuf<rg_r128_track_result> d_res;
-    DevBuf<rg_r128_album_result> d_album;
     DevBuf<double> d_e, d_z;
     DevBuf<double> d_ce;  // weighted tracks: the per-channel hop energies in front of the fold
     // an album in progress: every group's tracks in input order, their hop energies still on the device
@@ -428,7 +406,6 @@ R128State &state(rg_ctx *c) {
             s->d_desc.release();
             s->d_words.release();
             s->d_res.release();
-            s->d_album.release();
             s->d_e.release();
             s->d_z.release();
             s->d_ce.release();
@@ -474,9 +451,6 @@ void launch_tp(uint32_t factor, const RgR128TrackDev *d_list, uint32_t n, uint64
         hipLaunchKernelGGL((rg_r128_truepeak_kernel<FMT, 2>), dim3((uint32_t)tiles, ny), dim3(256), 0, s, d_list, n, taps, tp);
 }
 
-// the absolute gate, -70 LUFS as a mean square
-double r128_abs_gate() { return pow(10.0, (-70.0 + 0.691) / 10.0); }
-
 // hops per lane: enough lanes for about three waves on every SIMD of the chip, few enough that the three warm-up hops of a
 // lane stay a small share of what it reads
 uint32_t choose_S(const R128State &st, uint64_t channel_hops) {
@@ -487,6 +461,8 @@ uint32_t choose_S(const R128State &st, uint64_t channel_hops) {
 }
 
 }  // namespace
+
+double rg_r128_abs_gate() { return pow(10.0, (-70.0 + 0.691) / 10.0); }
 
 extern "C" int rg_r128_set_tuning(rg_ctx *c, int key, int64_t value) {
     if (!c) return RG_ERR_INVALID_ARG;
@@ -708,9 +684,9 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
                 else launch_tp<RG_FMT_S32_PLANAR>(factor, l, cnt, tp_l[f][k].units, tp_l[f][k].ny, d_tp, s);
                 RG_HIP(c, hipGetLastError());
             }
-    hipLaunchKernelGGL(rg_r128_gate_kernel, dim3((uint32_t)n), dim3(256), 0, s, d_tr, (uint32_t)n, (const uint32_t *)nullptr, 0u,
-                       r128_abs_gate(), (const uint32_t *)d_peak, (const uint32_t *)(want_tp ? d_tp : nullptr), (const uint32_t *)d_flags,
-                       st.d_res.p, (rg_r128_album_result *)nullptr, block_z_out ? st.d_z.p : (double *)nullptr);
+    hipLaunchKernelGGL(rg_r128_gate_kernel, dim3((uint32_t)n), dim3(256), 0, s, d_tr, rg_r128_abs_gate(), (const uint32_t *)d_peak,
+                       (const uint32_t *)(want_tp ? d_tp : nullptr), (const uint32_t *)d_flags, st.d_res.p,
+                       block_z_out ? st.d_z.p : (double *)nullptr);
     RG_HIP(c, hipGetLastError());
     RG_HIP(c, hipMemcpyAsync(out, st.d_res.p, n * sizeof(rg_r128_track_result), hipMemcpyDeviceToHost, s));
     if (block_z_out && total_z) RG_HIP(c, hipMemcpyAsync(block_z_out, st.d_z.p, total_z * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -722,58 +698,22 @@ int rg_r128_run(rg_ctx *c, const rg_track_desc *tracks, size_t n, const void *d_
             st.kept_res.push_back(out[i]);
         }
     else if (dyn_out)
-        return rg_r128_dynamics_run(c, &st.range, st.tune_album_select, tr.data(), out, n, dyn_out, nullptr, st_z_out);
+        return rg_r128_dynamics_run(c, &st.range, tr.data(), out, n, dyn_out, st_z_out);
     return RG_OK;
 }
 
+// One album is the many-albums stage with n_albums == 1: the empty album's record, the gates over the union, the peaks, the
+// NaN rule and the dynamics are all rg_r128_albums_stage's.
 int rg_r128_album_end(rg_ctx *c, int want_tp, rg_r128_album_result *album_out, rg_r128_dynamics *dyn_out,
                       rg_r128_dynamics *album_dyn_out, double *st_z_out) {
     if (!c || !album_out) return RG_ERR_INVALID_ARG;
     R128State &st = state(c);
-    memset(album_out, 0, sizeof *album_out);
-    album_out->loudness_lufs = -INFINITY;
-    album_out->true_peak = want_tp ? 0.0 : NAN;
-    if (album_dyn_out) rg_r128_dynamics_none(album_dyn_out);
-    const size_t n = st.kept.size();
-    if (n) {
-        int rc = rg_bind_device(c);
-        if (rc != RG_OK) return rc;
-        hipStream_t s = c->slot().stream;
-        std::vector<uint32_t> list(n);
-        for (size_t i = 0; i < n; ++i) list[i] = (uint32_t)i;
-        const size_t desc_bytes = n * sizeof(RgR128TrackDev);
-        RG_HIP(c, st.d_desc.reserve(desc_bytes + n * sizeof(uint32_t)));
-        RG_HIP(c, st.d_album.reserve(1));
-        RG_HIP(c, hipMemcpyAsync(st.d_desc.p, st.kept.data(), desc_bytes, hipMemcpyHostToDevice, s));
-        RG_HIP(c, hipMemcpyAsync(st.d_desc.p + desc_bytes, list.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(rg_r128_gate_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<const RgR128TrackDev *>(st.d_desc.p), 0u,
-                           reinterpret_cast<const uint32_t *>(st.d_desc.p + desc_bytes), (uint32_t)n, r128_abs_gate(),
-                           (const uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                           (rg_r128_track_result *)nullptr, st.d_album.p, (double *)nullptr);
-        RG_HIP(c, hipGetLastError());
-        RG_HIP(c, hipMemcpyAsync(album_out, st.d_album.p, sizeof *album_out, hipMemcpyDeviceToHost, s));
-        RG_HIP(c, hipStreamSynchronize(s));
-        bool bad = false;
-        double sp = 0.0, tp = 0.0;
-        for (const rg_r128_track_result &r : st.kept_res) {
-            bad = bad || (r.flags & RG_TRACK_FLAG_NONFINITE);
-            sp = std::max(sp, r.sample_peak);
-            if (want_tp) tp = std::max(tp, r.true_peak);
-        }
-        album_out->sample_peak = sp;
-        album_out->true_peak = want_tp ? tp : NAN;
-        if (bad) album_out->loudness_lufs = album_out->gain_db = NAN;
-        if (album_dyn_out) {
-            rc = rg_r128_dynamics_run(c, &st.range, st.tune_album_select, st.kept.data(), st.kept_res.data(), n, dyn_out, album_dyn_out,
-                                      st_z_out);
-            if (rc != RG_OK) {
-                st.drop_album();
-                return rc;
-            }
-        }
-    }
+    const size_t n = st.kept.size(), first[2] = {0, n};
+    int rc = n ? rg_bind_device(c) : RG_OK;
+    if (rc == RG_OK)
+        rc = rg_r128_albums_stage(c, st.kept.data(), st.kept_res.data(), n, first, 1, want_tp, album_out, dyn_out, album_dyn_out, st_z_out);
     st.drop_album();
-    return RG_OK;
+    return rc;
 }
 
 namespace {

@@ -1,15 +1,16 @@
-// rg_r128_albums.hip -- the album stage of the EBU R 128 path for many albums at once: every album of a call (of a group
-// of files) in the same launches, segmented over the arrays the track stage leaves on the device.  The loops, the slices
-// and the fold trees are those of the single-album kernels (rg_r128.hip, rg_r128_range.hip; the shared pieces are in
-// rg_r128_inl.h), so an album's record is bit for bit what the single-album call gives.  DESIGN.md section 14.2.
+// rg_r128_albums.hip -- the album stage of the EBU R 128 path: every album of a call (of a group of files) in the same
+// launches, segmented over the arrays the track stage leaves on the device.  The single-album entry points come here too
+// (rg_r128.hip: rg_r128_album_end, one album over every kept track), so there is one album stage and an album's record
+// does not depend on how many albums share its call.  The pieces shared with the track kernels (a block's value, the fold
+// tree, the radix select's steps) are in rg_r128_inl.h.  DESIGN.md section 14.2.
 //
 //  rg_r128a_gate_kernel         integrated loudness: one workgroup per album walks the album's tracks.
 //  rg_r128a_select_kernel       loudness range of the small albums: one workgroup per album over its range of the
 //                               short-term block array (tracks lie one after another there, so an album is contiguous).
 //  rg_r128a_wide_gate_kernel    loudness range of the wide albums (from RG_R128R_WIDE_FROM blocks on): grid = (slices, album).
-//  rg_r128a_wide_count_kernel   The threshold's sum keeps the single-album form's RG_R128R_WIDE fixed slices of the album's
-//  rg_r128a_wide_finish_kernel  own block list (a workgroup takes several, one after another, never merged); the counting
-//                               passes are integer counts and take at least RG_R128A_COUNT_MIN values per workgroup.
+//  rg_r128a_wide_count_kernel   The threshold's sum is over RG_R128R_WIDE fixed slices of the album's own block list (a
+//  rg_r128a_wide_finish_kernel  workgroup takes one, or several one after another, never merged), whatever the grid; the
+//                               counting passes are integer counts and take at least RG_R128A_COUNT_MIN values per workgroup.
 // Integer atomics only; every launch reads what the launch before it left in global memory and no launch reads what it writes.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -23,7 +24,7 @@
 #include "rg_r128.h"
 #include "rg_r128_inl.h"
 
-#define RG_R128A_GATE_SLICES 4      // slices of the threshold's sum one workgroup takes
+#define RG_R128A_GATE_SLICES 4      // slices of the threshold's sum one workgroup takes, from that many albums in a round on
 #define RG_R128A_COUNT_MIN 4096u    // values of a counting workgroup, at least (two 4096-bin histograms are cleared and flushed)
 
 struct RgR128AlbumDev {
@@ -36,8 +37,9 @@ struct RgR128AlbumDev {
 };
 
 // =================================================================================================
-// Integrated loudness: the album branch of rg_r128_gate_kernel, one workgroup per album.  Peaks, and the NaN of an album
-// with a track that is not finite, are the host's (it has the tracks' results).
+// Integrated loudness: one workgroup per album over the union of its tracks' gating blocks, in track order; the passes, the
+// per-thread order and the fold are rg_r128_gate_kernel's.  Peaks, and the NaN of an album with a track that is not finite,
+// are the host's (it has the tracks' results).
 __global__ void __launch_bounds__(256)
 rg_r128a_gate_kernel(const RgR128TrackDev *__restrict__ tracks, const RgR128AlbumDev *__restrict__ albums, const double abs_gate,
                      rg_r128_album_result *__restrict__ out) {
@@ -83,7 +85,8 @@ rg_r128a_gate_kernel(const RgR128TrackDev *__restrict__ tracks, const RgR128Albu
 }
 
 // =================================================================================================
-// Loudness range, small albums: the album workgroup of rg_r128r_select_kernel over the album's range of the block array.
+// Loudness range, small albums: rg_r128r_select_kernel's gates and radix select, one workgroup per album over the album's
+// range of the block array; the maxima are the integer max over its tracks' words.
 __global__ void __launch_bounds__(256)
 rg_r128a_select_kernel(const RgR128AlbumDev *__restrict__ albums, const double *__restrict__ st, const double abs_gate,
                        const unsigned long long *__restrict__ max_bits, rg_r128_dynamics *__restrict__ out) {
@@ -105,7 +108,7 @@ rg_r128a_select_kernel(const RgR128AlbumDev *__restrict__ albums, const double *
             ++cnt;
         }
     }
-    r128r_fold(sh_sum, sh_cnt, sum, cnt);
+    r128_fold(sh_sum, sh_cnt, sum, cnt);
     const double thr = cnt ? 0.01 * (sum / (double)cnt) : abs_gate;
     sum = 0.0;
     cnt = 0;
@@ -113,7 +116,7 @@ rg_r128a_select_kernel(const RgR128AlbumDev *__restrict__ albums, const double *
         const double x = v[i];
         if (x >= abs_gate && x >= thr) ++cnt;
     }
-    r128r_fold(sh_sum, sh_cnt, sum, cnt);
+    r128_fold(sh_sum, sh_cnt, sum, cnt);
     RgR128RangeSel sel;
     r128r_start(sel, thr, cnt);
     if (sel.n)  // uniform over the workgroup
@@ -133,11 +136,16 @@ rg_r128a_select_kernel(const RgR128AlbumDev *__restrict__ albums, const double *
 }
 
 // =================================================================================================
-// Loudness range, wide albums: rg_r128r_album_*_kernel with the album as the grid's second dimension.  Album y of the round
-// has its selection state at wide + y * kWideBytes.
+// Loudness range, wide albums: every pass of the selection is a launch, the album is the grid's second dimension, and album y
+// of the round has its selection state at wide + y * kWideBytes.  Slice g of the threshold's sum is the fixed range
+// [g * slice, (g + 1) * slice) of the album's blocks; a counting workgroup takes the fixed range its index gives.  Every
+// launch first brings the selection's state up to date from what the launch before it left in global memory (the partial
+// sums, the histogram) -- every workgroup for itself, all with the same result -- and workgroup 0 stores that state for the
+// next launch: sel[0] holds the threshold, sel[p + 1] the state before counting pass p.
 __global__ void __launch_bounds__(256)
 rg_r128a_wide_gate_kernel(const RgR128AlbumDev *__restrict__ albums, const double *__restrict__ st, const double abs_gate,
-                          const int pass, unsigned char *__restrict__ wide) {
+                          const int pass, const uint32_t slices /* a workgroup walks: gridDim.x * slices == RG_R128R_WIDE */,
+                          unsigned char *__restrict__ wide) {
     __shared__ double sh_sum[256];
     __shared__ uint32_t sh_cnt[256];
     const RgR128AlbumDev A = albums[blockIdx.y];
@@ -151,12 +159,12 @@ rg_r128a_wide_gate_kernel(const RgR128AlbumDev *__restrict__ albums, const doubl
     if (pass) {
         double sum = psum[threadIdx.x];  // RG_R128R_WIDE == the workgroup's size
         uint32_t cnt = pcnt[threadIdx.x];
-        r128r_fold(sh_sum, sh_cnt, sum, cnt);
+        r128_fold(sh_sum, sh_cnt, sum, cnt);
         thr = cnt ? 0.01 * (sum / (double)cnt) : abs_gate;
         if (blockIdx.x == 0 && threadIdx.x == 0) sel[0].thr = thr;
     }
     const uint32_t slice = (N + RG_R128R_WIDE - 1) / RG_R128R_WIDE;
-    for (uint32_t g = blockIdx.x * RG_R128A_GATE_SLICES; g < (blockIdx.x + 1) * RG_R128A_GATE_SLICES; ++g) {
+    for (uint32_t g = blockIdx.x * slices; g < (blockIdx.x + 1) * slices; ++g) {
         const uint64_t i0 = (uint64_t)g * slice;
         const uint64_t i1 = i0 + slice < N ? i0 + slice : N;
         double sum = 0.0;
@@ -168,7 +176,7 @@ rg_r128a_wide_gate_kernel(const RgR128AlbumDev *__restrict__ albums, const doubl
                 ++cnt;
             }
         }
-        r128r_fold(sh_sum, sh_cnt, sum, cnt);
+        r128_fold(sh_sum, sh_cnt, sum, cnt);
         if (threadIdx.x == 0) {
             psum[pass * RG_R128R_WIDE + g] = sum;
             pcnt[pass * RG_R128R_WIDE + g] = cnt;
@@ -193,7 +201,7 @@ rg_r128a_wide_count_kernel(const RgR128AlbumDev *__restrict__ albums, const doub
     if (pass == 0) {
         double sum = 0.0;
         uint32_t cnt = pcnt[RG_R128R_WIDE + tid];
-        r128r_fold(sh_sum, sh_cnt, sum, cnt);
+        r128_fold(sh_sum, sh_cnt, sum, cnt);
         r128r_start(s, sel[0].thr, cnt);
     } else {
         s = sel[pass];
@@ -254,8 +262,6 @@ struct AlbumsState {
     DevBuf<unsigned char> d_wide;     // RG_R128A_ROUND selection states at most
 };
 
-double r128a_abs_gate() { return pow(10.0, (-70.0 + 0.691) / 10.0); }
-
 }  // namespace
 
 void rg_r128_albums_free(void *p) {
@@ -294,7 +300,7 @@ int rg_r128_albums_stage(rg_ctx *c, const RgR128TrackDev *tr, const rg_r128_trac
     if (!*slot) *slot = new AlbumsState();
     AlbumsState &st = *static_cast<AlbumsState *>(*slot);
     hipStream_t s = c->slot().stream;
-    const double gate = r128a_abs_gate();
+    const double gate = rg_r128_abs_gate();
 
     RgR128RangeDev dev;
     if (albums_dyn_out) {  // stage 1 and the per-track selection over all n tracks, as the track call launches them
@@ -343,10 +349,13 @@ int rg_r128_albums_stage(rg_ctx *c, const RgR128TrackDev *tr, const rg_r128_trac
         const RgR128AlbumDev *d_round = st.d_albums.p + n_all + n_small + r0;
         uint32_t wgs = 1;
         for (uint32_t k = 0; k < nr; ++k) wgs = std::max(wgs, wide[r0 + k].count_wgs);
+        // a few albums: a workgroup per slice, so that the launch still fills the chip (measured: one album of 1.77 M blocks,
+        // 8.6 us a pass by 256 workgroups, 27 us by 64); the slices themselves do not change, nor do the bits
+        const uint32_t slices = nr < RG_R128A_GATE_SLICES ? 1u : RG_R128A_GATE_SLICES;
         RG_HIP(c, hipMemsetAsync(st.d_wide.p, 0, (size_t)nr * kWideBytes, s));
         for (int pass = 0; pass < 2; ++pass)
-            hipLaunchKernelGGL(rg_r128a_wide_gate_kernel, dim3(RG_R128R_WIDE / RG_R128A_GATE_SLICES, nr), dim3(256), 0, s, d_round, dev.st,
-                               gate, pass, st.d_wide.p);
+            hipLaunchKernelGGL(rg_r128a_wide_gate_kernel, dim3(RG_R128R_WIDE / slices, nr), dim3(256), 0, s, d_round, dev.st, gate, pass,
+                               slices, st.d_wide.p);
         RG_HIP(c, hipGetLastError());
         for (int pass = 0; pass < RG_R128R_PASSES; ++pass)
             hipLaunchKernelGGL(rg_r128a_wide_count_kernel, dim3(wgs, nr), dim3(256), 0, s, d_round, dev.st, gate, pass, st.d_wide.p);

@@ -1,6 +1,6 @@
 // rg_r128_inl.h -- the device helpers the kernels of the EBU R 128 path share (rg_r128.hip, rg_r128_range.hip,
 // rg_r128_albums.hip): a block's value, the fixed fold tree, the radix select's steps.  Every summation order has its one
-// definition here, so that a kernel of one translation unit gives the bits of its counterpart in another.
+// definition here, so that a track's kernels and an album's, in different translation units, agree to the bit.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,7 +8,7 @@
 
 #include "rg_r128.h"
 
-// ---- integrated loudness (rg_r128_gate_kernel, rg_r128a_gate_kernel) ------------------------------------------------------
+// ---- a gating block's value (rg_r128_gate_kernel, rg_r128a_gate_kernel), and the fold of every gate pass ------------------
 namespace {
 
 __device__ __forceinline__ double r128_block_z(const RgR128TrackDev &T, const uint32_t b) {
@@ -23,6 +23,7 @@ __device__ __forceinline__ double r128_block_z(const RgR128TrackDev &T, const ui
     return s / (4.0 * (double)T.hop);
 }
 
+// sum and count over the workgroup (256 threads), in a fixed tree
 __device__ __forceinline__ void r128_fold(double *sh_sum, uint32_t *sh_cnt, double &sum, uint32_t &cnt) {
     const int tid = threadIdx.x;
     __syncthreads();
@@ -46,7 +47,7 @@ __device__ __forceinline__ void r128_fold(double *sh_sum, uint32_t *sh_cnt, doub
 #define RG_R128R_ST_HOPS 30
 #define RG_R128R_BINS 4096      // 12-bit digit: two histograms are 32 KiB of LDS
 #define RG_R128R_PASSES 6       // 5 x 12 bits + 4 bits
-#define RG_R128R_WIDE 256       // workgroups of a wide album pass
+#define RG_R128R_WIDE 256       // slices of a wide album's threshold sum; its counting workgroups at most
 #define RG_R128R_WIDE_FROM 16384u  // measured: one workgroup is ahead at 7 k blocks, level at 18 k, 0.4 ms behind at 66 k
 
 struct RgR128RangeTrack {
@@ -75,24 +76,6 @@ __device__ __forceinline__ unsigned long long r128r_umax(unsigned long long a, u
 
 __device__ __forceinline__ int r128r_shift(const int pass) { return pass < RG_R128R_PASSES - 1 ? 52 - 12 * pass : 0; }
 __device__ __forceinline__ int r128r_width(const int pass) { return pass < RG_R128R_PASSES - 1 ? 12 : 4; }
-
-// sum and count over the workgroup, in a fixed tree
-__device__ __forceinline__ void r128r_fold(double *sh_sum, uint32_t *sh_cnt, double &sum, uint32_t &cnt) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh_sum[tid] = sum;
-    sh_cnt[tid] = cnt;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            sh_sum[tid] += sh_sum[tid + s];
-            sh_cnt[tid] += sh_cnt[tid + s];
-        }
-        __syncthreads();
-    }
-    sum = sh_sum[0];
-    cnt = sh_cnt[0];
-}
 
 // hist: RG_R128R_BINS counters in LDS.  The bin that holds the element of rank `rank` (0-based, below the counters' sum) and
 // its rank within that bin go to pick[0], pick[1]; every thread may read them after the call.

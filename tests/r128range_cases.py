@@ -88,6 +88,27 @@ def large_album_ids():
     return list(LARGE_ALBUM)
 
 
+# Short-term block counts of an album's union at which the wide selection's partition changes shape: one block (255 of the
+# 256 slices of the threshold's sum are empty), one fewer and one more than there are slices (slices of 1 with an empty last
+# one; slices of 2, half of them empty), one fewer than a counting workgroup's least share of 4096 (one workgroup), and one
+# more than twice that (two workgroups of 4097 and 4096).
+EDGE_ALBUM_BLOCKS = (1, 255, 257, 4095, 8193)
+
+
+def edge_album_tracks(n_blocks):
+    """[(channels, rate)]: an album of two mono F32 tracks of stepped noise at 8 kHz, n_blocks // 2 short-term blocks in the
+    first and the rest in the second (n_blocks = 1: the first has 29 hops and no block), each with a partial last hop.  The
+    short tracks have two level steps instead of eight, so that a segment is longer than a block and the -20 LU gate has
+    whole blocks to drop at every size."""
+    rate, h = 8000, r128cases.hop(8000)
+    out = []
+    for k, blocks in enumerate((n_blocks // 2, n_blocks - n_blocks // 2)):
+        frames = (blocks + ref.ST_HOPS - 1) * h + 3 + 2 * k
+        steps = STEPS if blocks >= 1024 else [-6.0, -40.0]
+        out.append((_quantise(_stepped("noise", rate, frames, 1, 700 + 10 * EDGE_ALBUM_BLOCKS.index(n_blocks) + k, steps), "f32"), rate))
+    return out
+
+
 def conformance_tracks():
     """[(case, rate, format, channels, expected LRA)]: the EBU Tech 3342 signals as the GPU conformance test runs them."""
     out = []

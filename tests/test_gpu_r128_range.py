@@ -226,6 +226,24 @@ def test_large_album_by_one_workgroup_and_by_wide_passes(an):
         _check_dynamics(cs[i][0], t.dynamics, refs[i])
 
 
+def _edge_album(n_blocks):
+    if ("edge", n_blocks) not in _CACHE:
+        tr = cases.edge_album_tracks(n_blocks)
+        _CACHE["edge", n_blocks] = (tr, ref.analyze_album(tr)[1])
+    return _CACHE["edge", n_blocks]
+
+
+@pytest.mark.parametrize("n_blocks,mode", [(n, 2) for n in cases.EDGE_ALBUM_BLOCKS] + [(257, 1)], ids=lambda v: str(v))
+def test_album_sizes_at_the_partition_edges(an, n_blocks, mode):
+    """The union sizes at which the wide passes' 256 slices and their counting workgroups change shape (1, 255, 257, 4095,
+    8193 blocks: tests/r128range_cases.py), forced wide, and 257 by one workgroup too, against the checker's union."""
+    tr, ref_album = _edge_album(n_blocks)
+    an.set_tuning_r128(2, mode)
+    a, st = an.analyze_album_r128([_track(ch, rate) for ch, rate in tr], dynamics=True, return_short_term=True)
+    assert a.dynamics.st_blocks == n_blocks
+    _check_dynamics(f"edge-album-{n_blocks}-mode{mode}", a.dynamics, ref_album, np.concatenate(st))
+
+
 def _write_album(tmp_path):
     tr, _ = _album()
     files = []

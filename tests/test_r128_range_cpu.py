@@ -119,6 +119,17 @@ def test_precondition_no_block_near_a_gate():
     assert all(abs(alb["loudness_range_lu"] - r["loudness_range_lu"]) > 0.1 for r in res)
 
 
+@pytest.mark.parametrize("n_blocks", cases.EDGE_ALBUM_BLOCKS)
+def test_precondition_edge_albums(n_blocks):
+    """The albums at the sizes where the wide selection's partition changes shape (tests/test_gpu_r128_range.py:
+    test_album_sizes_at_the_partition_edges): the union has exactly that many short-term blocks, and none of them lies within
+    10 x tol of the absolute gate or of the album's -20 LU threshold, on the checker alone."""
+    _, alb = ref.analyze_album(cases.edge_album_tracks(n_blocks))
+    assert alb["st_blocks"] == n_blocks and alb["st_blocks_gated"] > 0
+    closest = min(_no_block_near(f"edge-album-{n_blocks}", alb["st"], (ref.ABS_GATE, alb["thr"]), TOL))
+    print(f"{n_blocks} blocks, {alb['st_blocks_gated']} kept: closest block to a gate {closest:.3e} relative (tolerance {TOL:.2e})")
+
+
 # ---- command line -------------------------------------------------------------------------------------------------------
 def test_cli_parses_range():
     from mp3rgain_amd import cli
