@@ -23,6 +23,7 @@ from .replaygain import (  # noqa: F401
     R128Result,
     ReplayGainError,
     ReplayGainResult,
+    RipChecksums,
     analyze_album,
     analyze_track,
     find_peak_amplitude,

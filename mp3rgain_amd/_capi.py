@@ -244,6 +244,34 @@ R128_SYMBOLS = [
                                            _P(R128AlbumResult), _P(_i32), _P(R128Dynamics), _P(R128Dynamics)]),
 ]
 
+# include/mp3rgain_amd_rip.h (rip checksums: CRC-32 and AccurateRip v1 / v2 per track)
+RIP_FIRST_TRACK, RIP_LAST_TRACK = 1, 2
+RIP_CD_RATE, RIP_CD_FRAMES, RIP_COMPLETE = 1, 2, 4
+
+
+class RipRecord(C.Structure):  # rg_rip_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("null_samples", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("crc32", C.c_uint32),
+        ("crc32_nonnull", C.c_uint32),
+        ("arv1", C.c_uint32),
+        ("arv2", C.c_uint32),
+    ]
+
+
+RIP_SYMBOLS = [
+    ("rg_rip_checksums", _int, [_vp, _P(C.c_char_p), _sz, _P(_u32), _P(RipRecord)]),
+    ("rg_rip_checksums_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _P(_u32), _vp, _sz, _P(RipRecord)]),
+    ("rg_rip_kernel_shape", _int, [_P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_rip_crc32_algebra", _int, [_u32, _u32, _u64, _P(_u32), _P(_u32)]),
+    ("rg_rip_rate", _int, [_vp, _sz, _u64, _int, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_sz)]),
+]
+
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions
 NODE_OPEN = C.CFUNCTYPE(_vp, _int, _vp)
 NODE_CLOSE = C.CFUNCTYPE(None, _vp, _vp)
@@ -284,7 +312,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

@@ -65,6 +65,8 @@ class Options:  # src/main.rs:65-96
     loudness_range: bool = False  # with --r128 (--range): loudness range, maximum momentary and short-term loudness
     surround: bool = False   # with --r128 (--surround): BS.1770 channel weights from every file's channel layout
     verify: bool = False     # this façade only (--verify): FLAC files against the MD5 signature of their STREAMINFO
+    rip: bool = False        # this façade only (--rip): the files are the tracks of one disc; CRC-32 and AccurateRip checksums
+    rip_log: Optional[str] = None  # with --rip (--rip-log LOG): a ripper's log to compare the checksums with
     files: List[Path] = field(default_factory=list)
 
 
@@ -128,6 +130,10 @@ def parse_args(args: List[str], out, err) -> Options:
             o.surround = True
         elif arg == "--verify":  # not in the reference: a command of its own, like -s c
             o.verify = True
+        elif arg == "--rip":  # not in the reference: a command of its own, like --verify
+            o.rip = True
+        elif arg == "--rip-log":
+            o.rip_log = need("--rip-log", "--rip-log requires an argument")
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -222,6 +228,8 @@ def parse_args(args: List[str], out, err) -> Options:
         i += 1
     if o.surround and not o.r128:
         raise CliError("--surround requires --r128")
+    if o.rip_log is not None and not o.rip:
+        raise CliError("--rip-log requires --rip")
     return o
 
 
@@ -450,6 +458,8 @@ class Cli:
             self.e("note: -f (assume MPEG2) is accepted for compatibility but has no effect")
         if o.verify:
             return self.cmd_verify()
+        if o.rip:
+            return self.cmd_rip()
         if o.max_amplitude_only:
             return self.cmd_max_amplitude()
         if o.stored_tag_mode == "delete":
@@ -558,6 +568,75 @@ class Cli:
         if o.output_format == "json":
             _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
         return 1 if failed else 0
+
+    # ---- --rip (not in the reference): the checksums a CD ripper's log holds, on the GPU -------------------------------
+    def cmd_rip(self) -> int:
+        """The files are the tracks of one disc, in order (rg_rip_checksums, the first flagged first and the last last): per
+        file the CRC-32 of its PCM, the CRC-32 without null samples and the AccurateRip v1 / v2 signatures, from one decode on
+        the first GPU.  With --rip-log the log's track sections are compared with the files in order.  Exit status 1 when a
+        file fails, a log value mismatches, or the number of sections differs from the number of files.  TSV, one row per file
+        and no header: `file, status, frames, null samples, CRC32, CRC32 without nulls, ARv1, ARv2` and, with a log, its
+        verdict."""
+        from . import riplog
+
+        o = self.o
+        sections = None
+        if o.rip_log is not None:
+            try:
+                sections = riplog.parse(Path(o.rip_log).read_bytes())
+            except OSError as ex:
+                self.e(f"error: cannot read {o.rip_log}: {ex.strerror or ex}")
+                return 1
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            res = an.rip_checksums(o.files, disc=True)
+        if self.talk:
+            self.p(f"mp3rgain Rip checksums of {len(o.files)} file(s), taken as one disc")
+            self.p()
+        results, failed = [], 0
+        count_differs = sections is not None and len(sections) != len(o.files)
+        for i, (file, r) in enumerate(zip(o.files, res)):
+            verdict = None
+            if sections is not None and r.error is None:
+                verdict = riplog.compare(sections[i], r) if i < len(sections) else None
+            bad = r.error is not None or (verdict is not None and not verdict.ok) or (sections is not None and r.error is None and verdict is None)
+            failed += bad
+            vtext = None if sections is None or r.error is not None else (verdict.text if verdict is not None else "no log section")
+            if o.output_format == "json":
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                else:
+                    d.update(frames=r.frames, sample_rate=r.sample_rate, null_samples=r.null_samples, dropped_frames=r.dropped_frames,
+                             first_track=r.first_track, last_track=r.last_track, cd_rate=r.cd_rate, cd_frames=r.cd_frames,
+                             complete=r.complete, crc32=f"{r.crc32:08X}", crc32_nonnull=f"{r.crc32_nonnull:08X}",
+                             arv1=f"{r.arv1:08X}", arv2=f"{r.arv2:08X}")
+                    if vtext is not None:
+                        d["log"] = vtext
+                        if verdict is not None:
+                            d["log_checks"] = [{"name": n, "logged": f"{v:08X}", "ok": ok} for n, v, _, ok in verdict.checks]
+                results.append(d)
+            elif o.output_format == "tsv":
+                if r.error is not None:
+                    self.p(f"{_name(file)}\t{r.error}")
+                else:
+                    row = f"{_name(file)}\tok\t{r.frames}\t{r.null_samples}\t{r.crc32:08X}\t{r.crc32_nonnull:08X}\t{r.arv1:08X}\t{r.arv2:08X}"
+                    self.p(row + (f"\t{vtext}" if vtext is not None else ""))
+            elif r.error is not None:
+                self.e(f"{_name(file)} - {r.error}")
+            else:
+                notes = [] if r.complete else [f"{r.dropped_frames} frames dropped"]
+                if not r.cd_rate:
+                    notes.append(f"{r.sample_rate} Hz")
+                if not r.cd_frames:
+                    notes.append("not a whole number of sectors")
+                self.p(f"{_name(file)} - CRC32 {r.crc32:08X}  w/o null {r.crc32_nonnull:08X}  ARv1 {r.arv1:08X}  ARv2 {r.arv2:08X}"
+                       + (f"  [{', '.join(notes)}]" if notes else "") + (f"  log: {vtext}" if vtext is not None else ""))
+        if count_differs:
+            self.e(f"error: {o.rip_log} has {len(sections)} track section(s) for {len(o.files)} file(s)")
+        if o.output_format == "json":
+            _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+        return 1 if failed or count_differs else 0
 
     # ---- find_max_amplitude, src/lib.rs:1174-1199 ------------------------------------------------------------
     def find_max_amplitude(self, file: Path):
@@ -1194,6 +1273,9 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "--surround  With --r128: weight every channel of a multichannel file by its layout (BS.1770: surrounds 1.41, LFE 0)",
         "--verify    Verify FLAC files: decode on the GPU and compare the PCM's MD5 with the signature in STREAMINFO",
         "            MP3 files: dropped frames, frame CRCs, and the LAME tag's music length, music CRC and tag CRC",
+        "--rip       The files are the tracks of one ripped disc (16-bit stereo WAV or FLAC), in order: CRC-32, CRC-32 without",
+        "            null samples and AccurateRip v1 / v2 signatures per track, computed on the GPU",
+        "--rip-log <log>  With --rip: compare with the track sections of a ripper's log (EAC, XLD), in order",
         "-v          Show version",
         "-h          Show this help",
     ):

@@ -190,6 +190,7 @@ struct rg_ctx {
     DevBuf<unsigned char> d_flac_md5;        // rg_flac_md5.hip: [per-stream records | digests] of one launch
     DevBuf<unsigned char> d_mp3_crc;         // rg_mp3_crc.hip: [bytes | range records | frame offsets | tile CRCs | results] of one launch
     PinnedBuf<unsigned char> h_mp3_crc;      // pinned staging of d_mp3_crc's upload, and the results coming back
+    DevBuf<unsigned char> d_rip;             // rg_rip_crc.hip: [track records | tile records | sums] of one launch
     bool keep_mpeg_bytes = false;            // only while rg_mp3_verify runs: the loader pipeline keeps an MPEG stream's bytes as read
     int32_t file_track_index = -1;           // Some(idx) of the file-level call in progress (src/replaygain.rs:838-851); -1 = None
     unsigned loader_threads = 0;             // tuning key 7: host threads of the file loaders; 0 = every core this process may use

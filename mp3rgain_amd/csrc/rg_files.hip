@@ -25,6 +25,7 @@
 #include "rg_flac_md5.h"
 #include "rg_mp3verify.h"
 #include "rg_r128.h"
+#include "rg_rip.h"
 
 using namespace rgf;
 
@@ -716,6 +717,118 @@ extern "C" int rg_mp3_verify(rg_ctx *c, const char *const *paths, size_t n, rg_m
 }
 
 // find_peak_amplitude (src/replaygain.rs:1140-1249): max |x| over ALL channels, no loudness analysis
+// ---- rg_rip_checksums (include/mp3rgain_amd_rip.h) --------------------------------------------------------------------------
+// one group of the call: files [first, first + n).  The route is rg_flac_verify's -- load_many without a decoder command,
+// stage_loaded -- except that 16-bit stereo WAV streams are kept.  Whatever route put a track's PCM into the arena (device
+// FLAC decoder, the host decoder's planes by copy, the WAV de-interleave), the two kernels of rg_rip_crc.hip read it there, on
+// the stream the decode ran on, so tuning key 14 cannot show in the records.
+static int rip_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const uint32_t *track_flags, rg_rip_result *out) {
+    paths += first;
+    out += first;
+    if (track_flags) track_flags += first;
+    std::vector<LoadedAudio> &in = file_pool(c, n);
+    std::vector<int> rcs;
+    std::vector<std::string> errs;
+    std::string cmd;
+    cmd.swap(c->decoder_cmd);
+    int rc = load_many(c, paths, n, &in, &rcs, &errs, nullptr);
+    cmd.swap(c->decoder_cmd);
+    if (rc != RG_OK) return rc;
+    auto refuse = [&](size_t i, const std::string &why) {
+        out[i].status = RG_ERR_FORMAT;
+        c->file_errors[first + i] = "No rip checksums (" + why + "): " + paths[i];
+    };
+    // everything that loaded goes through the staging, as in an analysis call (what the loader pipeline has put into the arena
+    // already stays accounted for), except WAV streams that take no part: the staging cannot lay out every kind of them
+    std::vector<size_t> slot;
+    for (size_t i = 0; i < n; ++i) {
+        out[i].status = rcs[i];
+        c->file_errors[first + i] = errs[i];
+        if (rcs[i] != RG_OK) continue;
+        if (in[i].kind == LoadedAudio::Wav) {
+            rg_wav_info w;
+            if (rg_wav_parse(in[i].wav.data(), in[i].wav.size(), &w) != RG_OK) {
+                out[i].status = RG_ERR_FORMAT;
+                c->file_errors[first + i] = std::string("Failed to probe format: ") + paths[i];
+                continue;
+            }
+            if (w.sample_format != 1 || w.bits_per_sample != 16 || w.channels != 2) {
+                refuse(i, std::to_string(w.channels) + " channel(s) of " + std::to_string(w.bits_per_sample) + "-bit " +
+                              (w.sample_format == 3 ? "float" : "integer") + " PCM, not 2 of 16-bit integer");
+                continue;
+            }
+        }
+        slot.push_back(i);
+    }
+    if (slot.empty()) return RG_OK;
+    for (size_t k = 0; k < slot.size(); ++k)
+        if (slot[k] != k) std::swap(in[k], in[slot[k]]);
+    auto fail_all = [&](int code) {
+        for (size_t k = 0; k < slot.size(); ++k) {
+            memset(&out[slot[k]], 0, sizeof out[slot[k]]);
+            out[slot[k]].status = code;
+            c->file_errors[first + slot[k]] = c->err;
+        }
+        return RG_OK;
+    };
+    std::vector<rg_track_desc> descs;
+    std::vector<FlacCounts> counts;
+    size_t arena_bytes = 0;
+    rc = stage_loaded(c, in, slot.size(), &descs, &arena_bytes, &counts);
+    if (rc != RG_OK) return fail_all(rc);
+    std::vector<RgRipTrack> recs;
+    std::vector<size_t> rec_of;  // record -> position in the batch
+    for (size_t k = 0; k < slot.size(); ++k) {
+        const size_t i = slot[k];
+        if (in[k].kind != LoadedAudio::Wav && in[k].kind != LoadedAudio::Flac) {
+            refuse(i, "an MPEG stream, not a WAV or native FLAC stream");
+            continue;
+        }
+        if (in[k].kind == LoadedAudio::Flac && (in[k].flac_bps != 16 || in[k].channels != 2)) {
+            refuse(i, std::to_string(in[k].channels) + " channel(s) of " + std::to_string(in[k].flac_bps) + " bits per sample, not 2 of 16");
+            continue;
+        }
+        RgRipTrack rec;
+        char err[256] = "";
+        rc = rg_rip_track_record(i, descs[k], track_flags ? track_flags[i] : 0u, arena_bytes, &rec, err, sizeof err);
+        if (rc == RG_ERR_FORMAT) {
+            refuse(i, err);
+            continue;
+        }
+        if (rc != RG_OK) return fail_all(rg_set_err(c, rc, "%s", err));
+        recs.push_back(rec);
+        rec_of.push_back(k);
+    }
+    if (recs.empty()) return RG_OK;
+    std::vector<RgRipSums> sums(recs.size());
+    rc = rg_rip_device(c, c->d_arena.p, recs.data(), recs.size(), sums.data(), c->user_attached ? c->user_stream : c->slot().stream);
+    if (rc != RG_OK) return fail_all(rc);
+    for (size_t j = 0; j < recs.size(); ++j) {
+        const size_t k = rec_of[j];
+        rg_rip_fill(sums[j], descs[k].frames, descs[k].sample_rate, counts[k].dropped, &out[slot[k]]);
+    }
+    return RG_OK;
+}
+
+extern "C" int rg_rip_checksums(rg_ctx *c, const char *const *paths, size_t n, const uint32_t *track_flags, rg_rip_result *out) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    c->file_errors.assign(n, std::string());
+    if (n) memset(out, 0, n * sizeof *out);
+    int rc = rg_bind_device(c);
+    if (rc != RG_OK) return rc;
+    try {
+        std::vector<std::pair<size_t, size_t>> groups;
+        file_groups(c, paths, n, &groups);
+        for (const auto &g : groups) {
+            rc = rip_group(c, paths, g.first, g.second, track_flags, out);
+            if (rc != RG_OK) return rc;
+        }
+    } catch (const std::bad_alloc &) {
+        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
+    }
+    return RG_OK;
+}
+
 extern "C" int rg_find_peak_amplitude(rg_ctx *c, const char *path, rg_peak_result *out) {
     if (!c || !out) return RG_ERR_INVALID_ARG;
     rg_track_desc desc;

@@ -155,6 +155,27 @@ _NP_FMT = {
 }
 
 
+def rip_checksums_arena(ctx, route: int, descs, flags, arena):
+    """rg_rip_checksums_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> [RipRecord]."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    fl = None if flags is None else (C.c_uint32 * max(1, n))(*[int(f) for f in flags])
+    out = (_capi.RipRecord * max(1, n))()
+    rc = L.rg_rip_checksums_arena(ctx, int(route), n, d, fl, arena.ctypes.data if arena.size else None, arena.size, out)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return list(out[:n])
+
+
+def rip_kernel_shape():
+    """rg_rip_kernel_shape -> (chunk_frames, tile_frames, fold_lanes)."""
+    c, t, f = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _capi.load().rg_rip_kernel_shape(C.byref(c), C.byref(t), C.byref(f))
+    return c.value, t.value, f.value
+
+
 @dataclass
 class FlacVerifyResult:
     """One file of Analyzer.verify_flac (rg_flac_verify_result): the decoded PCM's MD5 against STREAMINFO's signature."""
@@ -173,6 +194,25 @@ class FlacVerifyResult:
     @property
     def verified(self) -> bool:
         return self.error is None and self.has_signature and self.md5_match and self.length_match and self.complete
+
+
+@dataclass
+class RipChecksums:
+    """One file of Analyzer.rip_checksums (rg_rip_result, include/mp3rgain_amd_rip.h): the numbers a ripper's log holds."""
+    crc32: int               # CRC-32 of the PCM's interleaved bytes (EAC's "Copy CRC")
+    crc32_nonnull: int       # the same with null samples left out
+    arv1: int                # AccurateRip v1 / v2 signatures
+    arv2: int
+    frames: int              # PCM frames per channel that were hashed
+    null_samples: int
+    sample_rate: int
+    dropped_frames: int      # FLAC frames the decode route dropped
+    cd_rate: bool            # 44100 Hz
+    cd_frames: bool          # frames is a whole number of CD sectors (588 frames)
+    complete: bool           # no frame was dropped
+    first_track: bool = False  # what the call was told about the file's place on its disc
+    last_track: bool = False
+    error: Optional["ReplayGainError"] = None  # why there are no checksums; every other field is then zero
 
 
 @dataclass
@@ -770,6 +810,57 @@ class Analyzer:
         out = (flacdec.FlacVerifyRecord * max(1, n))()
         self._check(flacdec._lib().rg_flac_verify(self._ctx, paths, n, out))
         return bytes(out)[:n * C.sizeof(flacdec.FlacVerifyRecord)]
+
+    @staticmethod
+    def _rip_flags(n: int, disc, flags):
+        if flags is not None:
+            if len(flags) != n:
+                raise ValueError("flags: one entry per file")
+            return [int(f) for f in flags]
+        out = [0] * n
+        if disc and n:
+            out[0] |= _capi.RIP_FIRST_TRACK
+            out[-1] |= _capi.RIP_LAST_TRACK
+        return out
+
+    def _rip_call(self, files, disc, flags):
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        fl = self._rip_flags(n, disc, flags)
+        out = (_capi.RipRecord * max(1, n))()
+        self._check(self._lib.rg_rip_checksums(self._ctx, paths, n, (C.c_uint32 * max(1, n))(*fl), out))
+        return out, fl
+
+    def rip_checksums(self, files, disc: bool = True, flags=None) -> list:
+        """rg_rip_checksums: `files` (16-bit stereo WAV or FLAC) decoded by the route the analysis uses and, from the PCM where
+        it lies on this GPU, per file the CRC-32, the CRC-32 without null samples and the AccurateRip v1 / v2 signatures ->
+        [RipChecksums].  disc=True takes the files as the tracks of one disc, in order: the first is flagged first, the last
+        last (`flags`: RIP_FIRST_TRACK / RIP_LAST_TRACK per file instead).  A file that takes no part carries its
+        ReplayGainError in `.error`."""
+        n = len(files)
+        out, fl = self._rip_call(files, disc, flags)
+        res = []
+        for i in range(n):
+            r = out[i]
+            err = None
+            if r.status != 0:
+                err = ReplayGainError(int(r.status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
+            res.append(RipChecksums(int(r.crc32), int(r.crc32_nonnull), int(r.arv1), int(r.arv2), int(r.frames), int(r.null_samples),
+                                    int(r.sample_rate), int(r.dropped_frames), bool(r.flags & _capi.RIP_CD_RATE),
+                                    bool(r.flags & _capi.RIP_CD_FRAMES), bool(r.flags & _capi.RIP_COMPLETE),
+                                    bool(fl[i] & _capi.RIP_FIRST_TRACK), bool(fl[i] & _capi.RIP_LAST_TRACK), err))
+        return res
+
+    def rip_checksums_raw(self, files, disc: bool = True, flags=None) -> bytes:
+        """rip_checksums' rg_rip_result array as the C call left it (tests compare routes byte for byte)."""
+        out, _ = self._rip_call(files, disc, flags)
+        return bytes(out)[:len(files) * C.sizeof(_capi.RipRecord)]
+
+    def rip_checksums_arena(self, route: int, descs, flags, arena):
+        """rg_rip_checksums_arena, the seam of the rip checksum kernels: the tracks `descs` describe in the host arena `arena`
+        -> [RipRecord]; route 0 = the serial host twin, route 1 = the arena copied to this GPU and the kernels, route 2 = the
+        kernels' fold arithmetic on the host."""
+        return rip_checksums_arena(self._ctx, route, descs, flags, arena)
 
     def verify_mp3(self, files) -> list:
         """rg_mp3_verify: every file decoded by the route the analysis uses, its dropped frames counted, and the LAME music
