@@ -128,6 +128,8 @@ struct rg_ctx {
     RgSlot &slot() { return slots[cur]; }
     // stream on which the album tail (all-reduce, album percentile, its D2H) runs
     hipStream_t album_stream() { return user_attached ? user_stream : slots[cur].stream; }
+    // stream of the file layer's staging, device decodes and checksum kernels: the same choice
+    hipStream_t file_stream() { return album_stream(); }
 
     RgRateDesign design[RG_NUM_RATES];
     DevBuf<RgCoefDev> d_coefs;
@@ -191,8 +193,6 @@ struct rg_ctx {
     DevBuf<unsigned char> d_mp3_crc;         // rg_mp3_crc.hip: [bytes | range records | frame offsets | tile CRCs | results] of one launch
     PinnedBuf<unsigned char> h_mp3_crc;      // pinned staging of d_mp3_crc's upload, and the results coming back
     DevBuf<unsigned char> d_rip;             // rg_rip_crc.hip: [track records | tile records | sums] of one launch
-    bool keep_mpeg_bytes = false;            // only while rg_mp3_verify runs: the loader pipeline keeps an MPEG stream's bytes as read
-    int32_t file_track_index = -1;           // Some(idx) of the file-level call in progress (src/replaygain.rs:838-851); -1 = None
     unsigned loader_threads = 0;             // tuning key 7: host threads of the file loaders; 0 = every core this process may use
     // Routing knobs of the file layer.  The environment is read ONCE, at rg_create (rg_capi.hip: read_env_defaults; getenv is
     // not safe against a host application's setenv, and a value that does not parse is ignored with a message in
@@ -227,7 +227,7 @@ struct rg_ctx {
     hipEvent_t ingest_copied[2] = {nullptr, nullptr}, ingest_free[2] = {nullptr, nullptr};
     uint64_t tune_ingest_chunk_kib = 0;      // 0 = default (2 GiB)
     DevBuf<unsigned char> d_wav;             // interleaved WAV samples awaiting de-interleave (rg_wav.hip)
-    std::string decoder_cmd;                 // rg_set_decoder_command
+    std::string decoder_cmd;                 // written by rg_set_decoder_command alone; the loaders get it through LoadOpts (rg_files.h)
     std::vector<unsigned char> force_exact;  // per track of the next enqueue: 1 = use variant 1 (exact repeat of flagged tracks)
     bool one_shot = false;  // the enqueue is a synchronous entry point's: ONE batch in flight, not one per pipeline stream (cost model)
     void *r128 = nullptr;                    // rg_r128.hip: buffers and tuning of the EBU R 128 path

@@ -347,19 +347,19 @@ bool stageable(const LoadedAudio &la) {
 // The files of an album, decoded on the host's cores (decode is by far the longest stage of a real run: one core turns
 // about 200 s of stereo audio into PCM per second, the GPU analyses 8 million).  Errors keep the reference's order: the
 // first failing file in input order is the one reported (src/replaygain.rs:1055).
-int load_many(rg_ctx *c, const char *const *paths, size_t n, std::vector<LoadedAudio> *out, std::vector<int> *rcs_out,
+int load_many(rg_ctx *c, const char *const *paths, size_t n, std::vector<LoadedAudio> *out, const LoadOpts &opts, std::vector<int> *rcs_out,
               std::vector<std::string> *errs_out, PartsRun *parts) {
     std::vector<int> rcs(n, RG_OK);
     std::vector<std::string> errs(n);
     if (c->gpu_mp3_decode >= 3 && n) {
-        const int prc = pipe_load_many(c, paths, n, out, &rcs, &errs, parts);
+        const int prc = pipe_load_many(c, paths, n, out, &rcs, &errs, opts, parts);
         if (prc != RG_OK) return prc;
     } else {
         unsigned workers = c->loader_threads ? c->loader_threads : usable_cores();
         if (workers > n) workers = (unsigned)n;
         std::atomic<size_t> next{0};
-        const std::string cmd = c->decoder_cmd;
-        const int32_t track_index = c->file_track_index;
+        const std::string cmd = opts.decoder_command ? c->decoder_cmd : std::string();
+        const int32_t track_index = opts.track_index;
         const int gpu_decode = c->gpu_mp3_decode;
         const int flac_route = c->gpu_flac_decode;
         auto work = [&]() {

@@ -64,7 +64,7 @@ int stage_loaded(rg_ctx *c, const std::vector<LoadedAudio> &in, size_t n, std::v
     RG_HIP(c, c->d_wav.reserve(src_total ? src_total : 16));
     rc = arena_reserve_keep(c, dst_total ? dst_total : 16, keep);
     if (rc != RG_OK) return rc;
-    hipStream_t fs = c->user_attached ? c->user_stream : c->slot().stream;
+    hipStream_t fs = c->file_stream();
     std::vector<RgMp3SplitItem> split;
     std::vector<RgFlacDevStream> flac;
     std::vector<size_t> flac_of;

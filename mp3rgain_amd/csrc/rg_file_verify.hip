@@ -1,0 +1,261 @@
+// rg_file_verify.hip -- the file-level calls that check files instead of measuring loudness: rg_flac_verify
+// (include/mp3rgain_amd_flac.h), rg_mp3_verify (include/mp3rgain_amd_mp3verify.h) and rg_rip_checksums
+// (include/mp3rgain_amd_rip.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
+// command: what this library does not decode itself is not a stream it could vouch for.  A file's status lives in its record,
+// and the record of a file that failed holds nothing else.
+#include <algorithm>
+
+#include "rg_files.h"
+#include "rg_flac_md5.h"
+#include "rg_mp3verify.h"
+#include "rg_rip.h"
+
+using namespace rgf;
+
+// "fail file i with (code, text)" where the status is the record's own: the calls zero their records before the first group
+template <typename Record>
+static auto mark_record(const FileGroup &g, Record *out) {
+    return [&g, out](size_t i, int code, const std::string &text) {
+        memset(&out[i], 0, sizeof out[i]);
+        out[i].status = code;
+        g.c->file_errors[g.first + i] = text;
+    };
+}
+
+// ---- rg_flac_verify -------------------------------------------------------------------------------------------------------
+// one group of the call: the hash of what lies in the arena (device decoder) or of the host decoder's PCM (tuning key 14 = 0),
+// then the per-file records
+static int flac_verify_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, rg_flac_verify_result *out) {
+    out += first;
+    FileGroup g(c, paths, first, n);
+    int rc = g.load(LoadOpts{-1, false});
+    if (rc != RG_OK) return rc;
+    const auto mark = mark_record(g, out);
+    const auto not_flac = [&](size_t i) { return std::string("Not a native FLAC stream: ") + g.paths[i]; };
+    // everything that loaded and is not a WAV stream goes through the staging, as in an analysis call (what the loader
+    // pipeline has put into the arena already stays accounted for); only the FLAC streams are hashed
+    const auto screen = [&](size_t i, std::string *text) -> int {
+        if (g.in[i].kind != LoadedAudio::Wav) return RG_OK;
+        *text = not_flac(i);
+        return RG_ERR_FORMAT;
+    };
+    const auto work = [&]() -> int {
+        const std::vector<LoadedAudio> &in = g.in;
+        std::vector<RgFlacMd5Rec> recs;
+        std::vector<size_t> rec_of;  // record -> position in the batch
+        for (size_t k = 0; k < g.slot.size(); ++k) {
+            const size_t i = g.slot[k];
+            if (in[k].kind != LoadedAudio::Flac) {
+                mark(i, RG_ERR_FORMAT, not_flac(i));
+                continue;
+            }
+            rg_flac_verify_result &r = out[i];
+            rg_flac_info si;
+            (void)rg_flac_scan(in[k].file_bytes.data(), in[k].file_bytes.size(), &si);  // (load_flac has walked this stream)
+            if (rg_flac_stream_md5(in[k].file_bytes.data(), in[k].file_bytes.size(), r.md5_stream) == 1) r.flags |= RG_FLAC_VERIFY_HAS_SIGNATURE;
+            r.frames = g.descs[k].frames;
+            r.total_samples = si.total_samples;
+            r.audio_frames = g.counts[k].decoded;
+            r.dropped_frames = g.counts[k].dropped;
+            RgFlacMd5Rec rec;
+            if (in[k].flac_frames.empty()) {  // the host decoder's PCM, in the arena's format (or a stream without frames)
+                rg_track_desc d = g.descs[k];
+                d.offset_bytes = 0;
+                const int rc = rg_flac_md5_record(c, i, d, in[k].flac_bps, in[k].flac_pcm.data(), in[k].flac_pcm.size(), &rec);
+                if (rc != RG_OK) return rc;
+                rg_flac_md5_host(rec, r.md5_decoded);
+                continue;
+            }
+            const int rc = rg_flac_md5_record(c, i, g.descs[k], in[k].flac_bps, c->d_arena.p, g.arena_bytes, &rec);
+            if (rc != RG_OK) return rc;
+            recs.push_back(rec);
+            rec_of.push_back(k);
+        }
+        if (!recs.empty()) {  // on the stream the decode ran on
+            std::vector<uint8_t> dig(recs.size() * 16);
+            const int rc = rg_flac_md5_device(c, recs.data(), recs.size(), dig.data(), c->file_stream());
+            if (rc != RG_OK) return rc;
+            for (size_t j = 0; j < recs.size(); ++j) memcpy(out[g.slot[rec_of[j]]].md5_decoded, &dig[16 * j], 16);
+        }
+        for (size_t i : g.slot) {
+            rg_flac_verify_result &r = out[i];
+            if (r.status != RG_OK) continue;
+            if ((r.flags & RG_FLAC_VERIFY_HAS_SIGNATURE) && memcmp(r.md5_stream, r.md5_decoded, 16) == 0) r.flags |= RG_FLAC_VERIFY_MD5_MATCH;
+            if (r.total_samples == 0 || r.total_samples == r.frames) r.flags |= RG_FLAC_VERIFY_LENGTH_MATCH;
+            if (r.dropped_frames == 0) r.flags |= RG_FLAC_VERIFY_COMPLETE;
+        }
+        return RG_OK;
+    };
+    g.want_counts = true;
+    return g.run(screen, mark, work);
+}
+
+extern "C" int rg_flac_verify(rg_ctx *c, const char *const *paths, size_t n, rg_flac_verify_result *out) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    if (n) memset(out, 0, n * sizeof *out);
+    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return flac_verify_group(c, paths, first, cnt, out); });
+}
+
+// ---- rg_mp3_verify --------------------------------------------------------------------------------------------------------
+// one group of the call.  The decode side is the analysis's, so how many frames were dropped is the route's own verdict; the
+// loader keeps the bytes of MPEG streams as read.  The checksums: one upload of the group's bytes with their range and frame
+// tables and the kernels of rg_mp3_crc.hip, on the stream the decode ran on; with tuning key 6 = 0 (the host decoder) the host
+// twin.
+static int mp3_verify_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, rg_mp3_verify_result *out) {
+    out += first;
+    FileGroup g(c, paths, first, n);
+    int rc = g.load(LoadOpts{-1, false, true});
+    if (rc != RG_OK) return rc;
+    const auto mark = mark_record(g, out);
+    const auto not_mpeg = [&](size_t i) { return std::string("Not a bare MPEG Layer III stream: ") + g.paths[i]; };
+    const auto screen = [&](size_t i, std::string *text) -> int {
+        const LoadedAudio &la = g.in[i];
+        const bool mpeg = la.kind == LoadedAudio::Planar || la.kind == LoadedAudio::Split || la.kind == LoadedAudio::Staged;
+        if (mpeg && !la.mpeg_in_mp4) return RG_OK;
+        *text = not_mpeg(i);
+        return RG_ERR_FORMAT;
+    };
+    const auto work = [&]() -> int {
+        const std::vector<LoadedAudio> &in = g.in;
+        const size_t m = g.slot.size();
+        std::vector<RgMp3VerifyPlan> plans(m);
+        std::vector<uint32_t> dropped(m, 0);
+        std::vector<char> live(m, 0);
+        for (size_t k = 0; k < m; ++k) {
+            const LoadedAudio &la = in[k];
+            if (rg_mp3_verify_plan(la.file_bytes.data(), la.file_bytes.size(), &plans[k]) != RG_OK) {
+                mark(g.slot[k], RG_ERR_FORMAT, not_mpeg(g.slot[k]));
+                continue;
+            }
+            live[k] = 1;
+            const uint32_t spf = plans[k].si.samples_per_frame ? plans[k].si.samples_per_frame : 1152;
+            dropped[k] = la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
+        }
+        std::vector<uint16_t> music(m, 0);
+        std::vector<uint32_t> failed(m, 0);
+        if (c->gpu_mp3_decode == 0) {  // the host twin
+            for (size_t k = 0; k < m; ++k) {
+                if (!live[k]) continue;
+                const uint8_t *d = in[k].file_bytes.data();
+                music[k] = rg_mp3_crc_range_host(d, plans[k].music_off, plans[k].music_len);
+                for (uint64_t o : plans[k].prot) failed[k] += rg_mp3_frame_crc_host(d, in[k].file_bytes.size(), o) ? 0u : 1u;
+            }
+        } else {
+            std::vector<const uint8_t *> parts(m);
+            std::vector<uint64_t> part_off(m), part_len(m), r_off(m), r_len(m), f_off;
+            std::vector<size_t> f_of;
+            uint64_t total = 0;
+            for (size_t k = 0; k < m; ++k) {
+                parts[k] = in[k].file_bytes.data();
+                part_off[k] = total;
+                part_len[k] = live[k] ? in[k].file_bytes.size() : 0;
+                r_off[k] = total + (live[k] ? plans[k].music_off : 0);
+                r_len[k] = live[k] ? plans[k].music_len : 0;
+                if (live[k])
+                    for (uint64_t o : plans[k].prot) {
+                        f_off.push_back(total + o);
+                        f_of.push_back(k);
+                    }
+                total = (total + part_len[k] + 15) & ~(uint64_t)15;
+            }
+            std::vector<uint8_t> ok(f_off.size() ? f_off.size() : 1);
+            RgMp3CrcJob job;
+            job.parts = parts.data();
+            job.part_off = part_off.data();
+            job.part_len = part_len.data();
+            job.n_parts = m;
+            job.nbytes = total;
+            job.range_off = r_off.data();
+            job.range_len = r_len.data();
+            job.n_ranges = m;
+            job.frame_off = f_off.data();
+            job.n_frames = f_off.size();
+            job.crc_out = music.data();
+            job.ok_out = ok.data();
+            const int rc = rg_mp3_crc_device(c, job, c->file_stream());
+            if (rc != RG_OK) return rc;
+            for (size_t j = 0; j < f_off.size(); ++j) failed[f_of[j]] += ok[j] ? 0u : 1u;
+        }
+        for (size_t k = 0; k < m; ++k)
+            if (live[k]) rg_mp3_verify_fill(in[k].file_bytes.data(), in[k].file_bytes.size(), plans[k], dropped[k], music[k], failed[k], &out[g.slot[k]]);
+        return RG_OK;
+    };
+    return g.run(screen, mark, work);
+}
+
+extern "C" int rg_mp3_verify(rg_ctx *c, const char *const *paths, size_t n, rg_mp3_verify_result *out) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    if (n) memset(out, 0, n * sizeof *out);
+    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return mp3_verify_group(c, paths, first, cnt, out); });
+}
+
+// ---- rg_rip_checksums -----------------------------------------------------------------------------------------------------
+// one group of the call.  The route is rg_flac_verify's, except that 16-bit stereo WAV streams are kept.  Whatever route put a
+// track's PCM into the arena (device FLAC decoder, the host decoder's planes by copy, the WAV de-interleave), the two kernels
+// of rg_rip_crc.hip read it there, on the stream the decode ran on, so tuning key 14 cannot show in the records.
+static int rip_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const uint32_t *track_flags, rg_rip_result *out) {
+    out += first;
+    if (track_flags) track_flags += first;
+    FileGroup g(c, paths, first, n);
+    int rc = g.load(LoadOpts{-1, false});
+    if (rc != RG_OK) return rc;
+    const auto mark = mark_record(g, out);
+    const auto refused = [&](size_t i, const std::string &why) { return "No rip checksums (" + why + "): " + g.paths[i]; };
+    // everything that loaded goes through the staging, as in an analysis call (what the loader pipeline has put into the arena
+    // already stays accounted for), except WAV streams that take no part: the staging cannot lay out every kind of them
+    const auto screen = [&](size_t i, std::string *text) -> int {
+        if (g.in[i].kind != LoadedAudio::Wav) return RG_OK;
+        rg_wav_info w;
+        if (rg_wav_parse(g.in[i].wav.data(), g.in[i].wav.size(), &w) != RG_OK) {
+            *text = std::string("Failed to probe format: ") + g.paths[i];
+            return RG_ERR_FORMAT;
+        }
+        if (w.sample_format == 1 && w.bits_per_sample == 16 && w.channels == 2) return RG_OK;
+        *text = refused(i, std::to_string(w.channels) + " channel(s) of " + std::to_string(w.bits_per_sample) + "-bit " +
+                               (w.sample_format == 3 ? "float" : "integer") + " PCM, not 2 of 16-bit integer");
+        return RG_ERR_FORMAT;
+    };
+    const auto work = [&]() -> int {
+        const std::vector<LoadedAudio> &in = g.in;
+        std::vector<RgRipTrack> recs;
+        std::vector<size_t> rec_of;  // record -> position in the batch
+        for (size_t k = 0; k < g.slot.size(); ++k) {
+            const size_t i = g.slot[k];
+            if (in[k].kind != LoadedAudio::Wav && in[k].kind != LoadedAudio::Flac) {
+                mark(i, RG_ERR_FORMAT, refused(i, "an MPEG stream, not a WAV or native FLAC stream"));
+                continue;
+            }
+            if (in[k].kind == LoadedAudio::Flac && (in[k].flac_bps != 16 || in[k].channels != 2)) {
+                mark(i, RG_ERR_FORMAT, refused(i, std::to_string(in[k].channels) + " channel(s) of " + std::to_string(in[k].flac_bps) + " bits per sample, not 2 of 16"));
+                continue;
+            }
+            RgRipTrack rec;
+            char err[256] = "";
+            const int rc = rg_rip_track_record(i, g.descs[k], track_flags ? track_flags[i] : 0u, g.arena_bytes, &rec, err, sizeof err);
+            if (rc == RG_ERR_FORMAT) {
+                mark(i, RG_ERR_FORMAT, refused(i, err));
+                continue;
+            }
+            if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
+            recs.push_back(rec);
+            rec_of.push_back(k);
+        }
+        if (recs.empty()) return RG_OK;
+        std::vector<RgRipSums> sums(recs.size());
+        const int rc = rg_rip_device(c, c->d_arena.p, recs.data(), recs.size(), sums.data(), c->file_stream());
+        if (rc != RG_OK) return rc;
+        for (size_t j = 0; j < recs.size(); ++j) {
+            const size_t k = rec_of[j];
+            rg_rip_fill(sums[j], g.descs[k].frames, g.descs[k].sample_rate, g.counts[k].dropped, &out[g.slot[k]]);
+        }
+        return RG_OK;
+    };
+    g.want_counts = true;
+    return g.run(screen, mark, work);
+}
+
+extern "C" int rg_rip_checksums(rg_ctx *c, const char *const *paths, size_t n, const uint32_t *track_flags, rg_rip_result *out) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    if (n) memset(out, 0, n * sizeof *out);
+    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return rip_group(c, paths, first, cnt, track_flags, out); });
+}

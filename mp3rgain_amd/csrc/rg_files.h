@@ -1,11 +1,14 @@
 // rg_files.h -- internal: what the translation units of the file layer share.  rg_wav.hip (RIFF/WAVE, de-interleave),
 // rg_file_load.hip (per-file loaders), rg_file_stage.hip (loaded files -> arena), rg_mp3_pipe.hip (the MP3 loader pipeline),
-// rg_files.hip (the C entry points), rg_file_hooks.hip (measurement and parity hooks).  Nothing outside them includes it.
+// rg_files.hip (the ReplayGain and R 128 entry points), rg_file_verify.hip (the verify and rip entry points),
+// rg_file_hooks.hip (measurement and parity hooks).  Nothing outside them includes it.
 #pragma once
 
 #include <string.h>
 
+#include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mp3rgain_amd.h"
@@ -95,6 +98,12 @@ inline uint16_t flac_format(uint32_t bps) { return bps <= 16 ? RG_FMT_S16_PLANAR
 constexpr int kFlacNotHere = 1;  // load_flac: a FLAC stream this library does not decode (the decoder command's to try)
 
 struct PartsRun;
+// What a call asks of the loaders, handed down to every loader thread: nothing of it lives in the context.
+struct LoadOpts {
+    int32_t track_index = -1;      // Some(idx) among the audio tracks of a container (src/replaygain.rs:838-851); -1 = None
+    bool decoder_command = true;   // false: the loaders see no decoder command, whatever rg_set_decoder_command has set
+    bool keep_mpeg_bytes = false;  // the loader pipeline keeps an MPEG stream's bytes as read (rg_mp3_verify: its compaction works in place)
+};
 // the context's pool of LoadedAudio (rg_ctx::file_pool): entry i serves the i-th file of a call
 std::vector<LoadedAudio> &file_pool(rg_ctx *c, size_t n);
 // A native FLAC stream in `out->file_bytes`: the frame walk, and with route 0 the host decoder's PCM in the arena's format.
@@ -111,10 +120,10 @@ int file_outcome(const LoadedAudio &la, int load_rc, const std::string &load_err
                  bool r128 = false /* the EBU R 128 path's rate rule */);
 bool stageable(const LoadedAudio &la);
 // entry i of `out` <- file i; with rcs_out / errs_out the per-file outcome is wanted and nothing aborts
-int load_many(rg_ctx *c, const char *const *paths, size_t n, std::vector<LoadedAudio> *out, std::vector<int> *rcs_out = nullptr,
-              std::vector<std::string> *errs_out = nullptr, PartsRun *parts = nullptr);
+int load_many(rg_ctx *c, const char *const *paths, size_t n, std::vector<LoadedAudio> *out, const LoadOpts &opts,
+              std::vector<int> *rcs_out = nullptr, std::vector<std::string> *errs_out = nullptr, PartsRun *parts = nullptr);
 // `out` is entry 0 of the context's pool
-inline int load_one(rg_ctx *c, const char *path, std::vector<LoadedAudio> *pool) { return load_many(c, &path, 1, pool); }
+inline int load_one(rg_ctx *c, const char *path, std::vector<LoadedAudio> *pool, const LoadOpts &opts) { return load_many(c, &path, 1, pool, opts); }
 
 // ---- rg_file_stage.hip --------------------------------------------------------------------------------------------------
 int arena_reserve_keep(rg_ctx *c, size_t need, size_t keep);
@@ -258,6 +267,88 @@ struct PartsRun {
 // this returns and their PCM sits in c->d_arena (LoadedAudio::Staged), other inputs are loaded as load_audio_for loads
 // them.  rcs / errs: per-file outcome.
 int pipe_load_many(rg_ctx *c, const char *const *paths, size_t n, std::vector<LoadedAudio> *out, std::vector<int> *rcs,
-                   std::vector<std::string> *errs, PartsRun *parts);
+                   std::vector<std::string> *errs, const LoadOpts &opts, PartsRun *parts);
+
+// ---- rg_files.hip, rg_file_verify.hip: what every per-file call is made of ----------------------------------------------
+// An allocation failure on the host must leave an extern "C" function as a status, not as an exception.
+template <typename Fn>
+int no_throw(rg_ctx *c, Fn fn) {
+    try {
+        return fn();
+    } catch (const std::bad_alloc &) {
+        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
+    }
+}
+// Files of a long list in groups whose PCM is estimated to stay within a third of the free device memory (rg_files.hip)
+void file_groups(rg_ctx *c, const char *const *paths, size_t n, std::vector<std::pair<size_t, size_t>> *groups);
+// A per-file call: no messages yet, the device bound, then fn(first, cnt) for each group of the list until one fails the call.
+template <typename Fn>
+int for_each_group(rg_ctx *c, const char *const *paths, size_t n, Fn fn) {
+    return no_throw(c, [&]() -> int {
+        c->file_errors.assign(n, std::string());
+        int rc = rg_bind_device(c);
+        if (rc != RG_OK) return rc;
+        std::vector<std::pair<size_t, size_t>> groups;
+        file_groups(c, paths, n, &groups);
+        for (const auto &g : groups) {
+            rc = fn(g.first, g.second);
+            if (rc != RG_OK) return rc;
+        }
+        return RG_OK;
+    });
+}
+
+// One group of a call, files [first, first + n) of it, on the route every per-file call takes: load(), then run().  `i` is a
+// file's index in the group throughout; the call's numbering, which c->file_errors has, is first + i.
+struct FileGroup {
+    rg_ctx *const c;
+    const char *const *const paths;  // the group's: paths[i]
+    const size_t first, n;
+    std::vector<LoadedAudio> &in;    // the context's pool: in[i] <- file i
+    std::vector<int> rcs;            // load(): per file
+    std::vector<std::string> errs;
+    // run(): the batch, in[k] being file slot[k] from here on (slot ascends)
+    std::vector<size_t> slot;
+    std::vector<rg_track_desc> descs;
+    std::vector<FlacCounts> counts;  // with want_counts
+    size_t arena_bytes = 0;
+    bool done = false;               // the batch was staged and `work` has returned RG_OK
+    // the route's to set before run()
+    bool want_counts = false;        // `counts` is wanted
+    bool stop_at_first = false;      // the first failing file in input order fails the call, and so does a failing batch
+
+    FileGroup(rg_ctx *c, const char *const *call_paths, size_t first, size_t n)
+        : c(c), paths(call_paths + first), first(first), n(n), in(file_pool(c, n)) {}
+    // a status other than RG_OK is the call's, not a file's
+    int load(const LoadOpts &opts, PartsRun *parts = nullptr) { return load_many(c, paths, n, &in, opts, &rcs, &errs, parts); }
+    // Every file gets its outcome, mark(i, code, text): what loading made of it or, for a file that loaded, screen(i, &text)
+    // (*text comes in as the loader's, empty as a rule).  The good files go to the front of the pool (swap keeps every buffer
+    // alive for the next call) and into the arena as one batch, which `work()` then has.  A failure of the batch itself -- a
+    // WAV of a kind the library cannot stage, a device error -- is every file's of the batch: mark(i, rc, c->err).
+    template <typename Screen, typename Mark, typename Work>
+    int run(Screen screen, Mark mark, Work work) {
+        for (size_t i = 0; i < n; ++i) {
+            std::string text = errs[i];
+            const int code = rcs[i] != RG_OK ? rcs[i] : screen(i, &text);
+            mark(i, code, text);
+            if (code != RG_OK && stop_at_first) return rg_set_err(c, code, "%s", text.c_str());
+            if (code == RG_OK) slot.push_back(i);
+        }
+        if (slot.empty()) return RG_OK;
+        for (size_t k = 0; k < slot.size(); ++k)
+            if (slot[k] != k) std::swap(in[k], in[slot[k]]);
+        int rc = stage_loaded(c, in, slot.size(), &descs, &arena_bytes, want_counts ? &counts : nullptr);
+        if (rc == RG_OK) rc = work();
+        done = rc == RG_OK;
+        if (done || stop_at_first) return rc;
+        for (size_t i : slot) mark(i, rc, c->err);
+        return RG_OK;
+    }
+    // results in batch order -> the caller's array, by file
+    template <typename Result>
+    void scatter(const std::vector<Result> &res, Result *out) const {
+        for (size_t k = 0; k < slot.size(); ++k) out[slot[k]] = res[k];
+    }
+};
 
 }  // namespace rgf

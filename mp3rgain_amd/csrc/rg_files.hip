@@ -12,8 +12,9 @@
 //     stream to stdout (rg_set_decoder_command, e.g. "ffmpeg -v error -i {} -f wav -c:a pcm_f32le -").
 // Everything after the arena is the same path as rg_analyze_pcm_batch.
 //
-// This file holds the C entry points and their group helpers; the rest of the file layer: rg_wav.hip, rg_file_load.hip,
-// rg_file_stage.hip, rg_mp3_pipe.hip, rg_file_hooks.hip (shared declarations: rg_files.h).
+// This file holds the ReplayGain and EBU R 128 entry points and their group helpers; the rest of the file layer: rg_wav.hip,
+// rg_file_load.hip, rg_file_stage.hip, rg_mp3_pipe.hip, rg_file_verify.hip (the verify and rip entry points), rg_file_hooks.hip
+// (shared declarations, the call driver and the group route: rg_files.h).
 #include <stdio.h>
 #include <sys/stat.h>
 
@@ -22,10 +23,7 @@
 
 #include "rg_albums.h"
 #include "rg_files.h"
-#include "rg_flac_md5.h"
-#include "rg_mp3verify.h"
 #include "rg_r128.h"
-#include "rg_rip.h"
 
 using namespace rgf;
 
@@ -34,9 +32,7 @@ using namespace rgf;
 static int load_and_stage_one(rg_ctx *c, const char *path, int32_t track_index, rg_track_desc *desc, size_t *arena_bytes,
                               uint32_t *file_type = nullptr) {
     std::vector<LoadedAudio> &pool = file_pool(c, 1);
-    c->file_track_index = track_index;
-    int rc = load_one(c, path, &pool);
-    c->file_track_index = -1;
+    int rc = load_one(c, path, &pool, LoadOpts{track_index});
     if (rc != RG_OK) return rc;
     if (track_index >= 0 && (uint32_t)track_index >= pool[0].n_audio_tracks)
         return rg_set_err(c, RG_ERR_INVALID_ARG, "Track index %d out of range (file has %u audio track(s))", track_index, pool[0].n_audio_tracks);
@@ -61,68 +57,91 @@ static int parts_allowed(rg_ctx *c, size_t n_files, size_t n_groups, bool *use) 
     return RG_OK;
 }
 
-// The files of a group that came through loading (`slot`: their indices in `in`, ascending) as one batch: the good files to the
-// front of the pool (swap keeps every buffer alive for the next call), into the arena, through `run(descs, k, arena_bytes, res)`,
-// and res[k] -> out[slot[k]].  The status is the staging's or the run's: what a failed batch means is the caller's to say.
-template <typename Result, typename Run>
-static int run_good_files(rg_ctx *c, std::vector<LoadedAudio> &in, const std::vector<size_t> &slot, Result *out, Run run) {
-    for (size_t k = 0; k < slot.size(); ++k)
-        if (slot[k] != k) std::swap(in[k], in[slot[k]]);
-    std::vector<rg_track_desc> descs;
-    size_t arena_bytes = 0;
-    int rc = stage_loaded(c, in, slot.size(), &descs, &arena_bytes);
-    if (rc != RG_OK) return rc;
-    std::vector<Result> res(slot.size());
-    rc = run(descs.data(), slot.size(), arena_bytes, res.data());
-    if (rc != RG_OK) return rc;
-    for (size_t k = 0; k < slot.size(); ++k) out[slot[k]] = res[k];
+// Album parts of a group of n files, after loading: if every file was analysed as a part of its chunk (`parts`: the group's, or
+// null if it had none) the results are on their way to the host and, in album mode, the packs are on the device.  *stand: the
+// parts' results are the files' (out[i] <- file i, file_type included); else a file did not come through the pipeline, or a
+// track is flagged and the plain route has to repeat it on the order-faithful kernel: nothing was taken.
+static int take_parts(rg_ctx *c, const PartsRun *parts, const std::vector<LoadedAudio> &in, size_t n, rg_track_result *out, bool *stand) {
+    *stand = false;
+    if (!parts || parts->broken || parts->file_of.size() != n) return RG_OK;
+    RG_HIP(c, rg_sync_slots(c, RG_SLOT_STREAMS));
+    const rg_track_result *res = c->h_part_results.p;
+    for (size_t j = 0; j < n; ++j)
+        if (c->kernel_variant == 0 && (res[j].flags & RG_TRACK_FLAG_IMPRECISE)) return RG_OK;
+    for (size_t j = 0; j < n; ++j) {
+        const size_t i = parts->file_of[j];
+        out[i] = res[j];
+        out[i].file_type = in[i].is_mp4 ? RG_FILE_AAC : RG_FILE_MP3;
+    }
+    *stand = true;
     return RG_OK;
 }
-// a failure of the batch itself (a WAV of a kind the library cannot stage, a device error): every file in it carries it
-// (status_out: the group's; `first`: the group's first file in the call's numbering, which file_errors has)
-static void fail_batch(rg_ctx *c, const std::vector<size_t> &slot, size_t first, int rc, int32_t *status_out) {
-    for (size_t k = 0; k < slot.size(); ++k) {
-        status_out[slot[k]] = rc;
-        c->file_errors[first + slot[k]] = c->err;
+
+// The tail of a many-albums call that failed as a whole (a device error, no memory): what it did not finish -- the files from
+// files_done on, the albums not `done` -- is zeroed and carries the call's code and text, which c->err keeps.
+// (dyn_out / albums_dyn_out: the R 128 calls with dynamics, else null)
+template <typename Track, typename Album>
+static int fail_rest(rg_ctx *c, int rc, size_t files_done, size_t n, const std::vector<char> &done, Track *tracks_out, int32_t *status_out,
+                     Album *albums_out, int32_t *album_status_out, rg_r128_dynamics *dyn_out = nullptr, rg_r128_dynamics *albums_dyn_out = nullptr) {
+    const std::string text = c->err;
+    for (size_t i = files_done; i < n; ++i) {
+        memset(&tracks_out[i], 0, sizeof tracks_out[i]);
+        if (dyn_out) memset(&dyn_out[i], 0, sizeof dyn_out[i]);
+        status_out[i] = rc;
+        c->file_errors[i] = text;
     }
+    for (size_t a = 0; a < done.size(); ++a)
+        if (!done[a]) {
+            memset(&albums_out[a], 0, sizeof albums_out[a]);
+            if (albums_dyn_out) memset(&albums_dyn_out[a], 0, sizeof albums_dyn_out[a]);
+            album_status_out[a] = rc;
+        }
+    c->err = text;
+    return rc;
 }
 
 // =================================================================================================
 extern "C" int rg_set_decoder_command(rg_ctx *c, const char *command_template) {
     if (!c) return RG_ERR_INVALID_ARG;
-    c->decoder_cmd = command_template ? command_template : "";
-    return RG_OK;
+    return no_throw(c, [&]() -> int {
+        c->decoder_cmd = command_template ? command_template : "";
+        return RG_OK;
+    });
 }
 
 extern "C" int rg_analyze_wav_batch(rg_ctx *c, const void *const *wav, const size_t *wav_len, size_t n, int album,
                                     rg_track_result *out, rg_album_result *album_out) {
     if (!c) return RG_ERR_INVALID_ARG;
-    if (n && (!wav || !wav_len)) return rg_set_err(c, RG_ERR_INVALID_ARG, "null input array");
-    std::vector<rg_track_desc> descs;
-    size_t arena_bytes = 0;
-    int rc = stage_wavs(c, wav, wav_len, n, &descs, &arena_bytes);
-    if (rc != RG_OK) return rc;
-    // the planar arena is on the device: the rest is rg_analyze_pcm_batch / rg_analyze_album_pcm, exact pass included
-    if (album) return rg_analyze_album_pcm(c, descs.data(), n, c->d_arena.p, arena_bytes, 1, out, album_out, nullptr);
-    return rg_analyze_pcm_batch(c, descs.data(), n, c->d_arena.p, arena_bytes, 1, out, nullptr);
+    return no_throw(c, [&]() -> int {
+        if (n && (!wav || !wav_len)) return rg_set_err(c, RG_ERR_INVALID_ARG, "null input array");
+        std::vector<rg_track_desc> descs;
+        size_t arena_bytes = 0;
+        int rc = stage_wavs(c, wav, wav_len, n, &descs, &arena_bytes);
+        if (rc != RG_OK) return rc;
+        // the planar arena is on the device: the rest is rg_analyze_pcm_batch / rg_analyze_album_pcm, exact pass included
+        if (album) return rg_analyze_album_pcm(c, descs.data(), n, c->d_arena.p, arena_bytes, 1, out, album_out, nullptr);
+        return rg_analyze_pcm_batch(c, descs.data(), n, c->d_arena.p, arena_bytes, 1, out, nullptr);
+    });
 }
 
 extern "C" int rg_analyze_track(rg_ctx *c, const char *path, int32_t track_index, rg_track_result *out) {
     if (!c || !out) return RG_ERR_INVALID_ARG;
-    rg_track_desc desc;
-    size_t arena_bytes = 0;
-    uint32_t file_type = 0;
-    int rc = load_and_stage_one(c, path, track_index, &desc, &arena_bytes, &file_type);
-    if (rc != RG_OK) return rc;
-    rc = rg_analyze_pcm_batch(c, &desc, 1, c->d_arena.p, arena_bytes, 1, out, nullptr);
-    if (rc != RG_OK) return rc;
-    out->file_type = file_type;
-    return RG_OK;
+    return no_throw(c, [&]() -> int {
+        rg_track_desc desc;
+        size_t arena_bytes = 0;
+        uint32_t file_type = 0;
+        int rc = load_and_stage_one(c, path, track_index, &desc, &arena_bytes, &file_type);
+        if (rc != RG_OK) return rc;
+        rc = rg_analyze_pcm_batch(c, &desc, 1, c->d_arena.p, arena_bytes, 1, out, nullptr);
+        if (rc != RG_OK) return rc;
+        out->file_type = file_type;
+        return RG_OK;
+    });
 }
 
 // Files of a long list in groups whose PCM is estimated (24 bytes of planar f32 per byte of file: a 128 kb/s stereo MP3;
 // denser files decode to less) to stay within a third of the free device memory, at most 64 GB.
-static void file_groups(rg_ctx *c, const char *const *paths, size_t n, std::vector<std::pair<size_t, size_t>> *groups) {
+void rgf::file_groups(rg_ctx *c, const char *const *paths, size_t n, std::vector<std::pair<size_t, size_t>> *groups) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)48 << 30;
     size_t budget = std::min((size_t)64 << 30, (free_b + c->d_arena.cap) / 3);
@@ -149,10 +168,7 @@ static void file_groups(rg_ctx *c, const char *const *paths, size_t n, std::vect
 // reported -- and *failed_index (if given) says which one it was.  An album whose PCM does not fit the device at once is
 // analysed in parts and the parts' histograms and peaks are folded (u32 adds commute: the result does not depend on the
 // partition).
-extern "C" int rg_analyze_album_begin(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, rg_track_result *tracks_out,
-                                      size_t *failed_index) {
-    if (failed_index) *failed_index = (size_t)-1;
-    if (!c || (n && (!paths || !tracks_out))) return RG_ERR_INVALID_ARG;
+static int album_begin_impl(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, rg_track_result *tracks_out, size_t *failed_index) {
     int rc = rg_bind_device(c);
     if (rc != RG_OK) return rc;
     std::vector<std::pair<size_t, size_t>> groups;
@@ -163,62 +179,57 @@ extern "C" int rg_analyze_album_begin(rg_ctx *c, const char *const *paths, size_
         if (failed_index) *failed_index = i;
         return code;
     };
-    for (size_t g = 0; g < std::max<size_t>(groups.size(), 1); ++g) {
-        const size_t first = groups.empty() ? 0 : groups[g].first, cnt = groups.empty() ? 0 : groups[g].second;
-        std::vector<LoadedAudio> &in = file_pool(c, cnt);
+    // (a status that is not a file's failure leaves *failed_index at (size_t)-1, so that a node prefers real file errors of other shares)
+    for (size_t gi = 0; gi < std::max<size_t>(groups.size(), 1); ++gi) {
+        const size_t first = groups.empty() ? 0 : groups[gi].first, cnt = groups.empty() ? 0 : groups[gi].second;
+        FileGroup g(c, paths, first, cnt);
         const double t0 = now();
-        std::vector<int> rcs;
-        std::vector<std::string> errs;
         PartsRun parts;  // album parts: one album that fits the device
         bool use_parts = false;
         rc = parts_allowed(c, cnt, groups.size(), &use_parts);
         if (rc != RG_OK) return rc;
-        c->file_track_index = track_index;
-        rc = load_many(c, paths + first, cnt, &in, &rcs, &errs, use_parts ? &parts : nullptr);
-        c->file_track_index = -1;
-        if (rc != RG_OK) return rc;  // not a file's failure: *failed_index stays (size_t)-1, so that a node prefers real file errors of other shares
+        rc = g.load(LoadOpts{track_index}, use_parts ? &parts : nullptr);
+        if (rc != RG_OK) return rc;
         for (size_t i = 0; i < cnt; ++i) {
             std::string msg;
-            const int frc = file_outcome(in[i], rcs[i], errs[i], paths[first + i], track_index, &msg);
+            const int frc = file_outcome(g.in[i], g.rcs[i], g.errs[i], g.paths[i], track_index, &msg);
             if (frc != RG_OK) return fail_at(first + i, rg_set_err(c, frc, "%s", msg.c_str()));
         }
         const double t1 = now();
-        if (use_parts && !parts.broken && parts.file_of.size() == cnt) {
-            // every file was analysed as a part of its chunk: the results are on their way to the host, the packs are on the device
-            RG_HIP(c, rg_sync_slots(c, RG_SLOT_STREAMS));
-            bool flagged = false;
-            for (size_t j = 0; j < cnt; ++j) {
-                const rg_track_result &r = c->h_part_results.p[j];
-                flagged = flagged || (c->kernel_variant == 0 && (r.flags & RG_TRACK_FLAG_IMPRECISE));
-                tracks_out[first + parts.file_of[j]] = r;
-            }
-            if (!flagged) {  // (a flagged track: the plain route below repeats it on the order-faithful kernel)
-                rc = rg_album_parts_fold(c, parts.n_parts);
-                if (rc != RG_OK) return rc;
-                for (size_t i = 0; i < cnt; ++i) tracks_out[first + i].file_type = in[i].is_mp4 ? RG_FILE_AAC : RG_FILE_MP3;
-                if (trace) fprintf(stderr, "[rg_analyze_album] load + decode + analysis in %zu parts %.1f ms, results %.1f ms\n", parts.n_parts, (t1 - t0) * 1e3, (now() - t1) * 1e3);
-                return RG_OK;
-            }
+        bool stand = false;
+        rc = take_parts(c, use_parts ? &parts : nullptr, g.in, cnt, tracks_out + first, &stand);
+        if (rc != RG_OK) return rc;
+        if (stand) {
+            rc = rg_album_parts_fold(c, parts.n_parts);
+            if (rc == RG_OK && trace) fprintf(stderr, "[rg_analyze_album] load + decode + analysis in %zu parts %.1f ms, results %.1f ms\n", parts.n_parts, (t1 - t0) * 1e3, (now() - t1) * 1e3);
+            return rc;
         }
         std::vector<rg_track_desc> descs;
         size_t arena_bytes = 0;
-        rc = stage_loaded(c, in, cnt, &descs, &arena_bytes);
+        rc = stage_loaded(c, g.in, cnt, &descs, &arena_bytes);
         if (trace) fprintf(stderr, "[rg_analyze_album] load %.1f ms, stage + device decode %.1f ms\n", (t1 - t0) * 1e3, (now() - t1) * 1e3);
         if (rc == RG_ERR_FORMAT) {  // "input i ..." -> the reference's text with the file's name
             size_t i = 0;
             if (sscanf(c->err.c_str(), "input %zu", &i) == 1 && i < cnt)
-                return fail_at(first + i, rg_set_err(c, RG_ERR_FORMAT, "Failed to probe format: %s", paths[first + i]));
+                return fail_at(first + i, rg_set_err(c, RG_ERR_FORMAT, "Failed to probe format: %s", g.paths[i]));
         }
-        if (rc != RG_OK) return rc;  // not a file's failure: *failed_index stays (size_t)-1, so that a node prefers real file errors of other shares
+        if (rc != RG_OK) return rc;
         const double t2 = now();
         if (groups.size() <= 1) rc = rg_album_local_pcm(c, descs.data(), cnt, c->d_arena.p, arena_bytes, 1, tracks_out);
-        else rc = rg_album_part(c, descs.data(), cnt, c->d_arena.p, arena_bytes, g, groups.size(), tracks_out + first);
-        if (rc != RG_OK) return rc;  // not a file's failure: *failed_index stays (size_t)-1, so that a node prefers real file errors of other shares
-        for (size_t i = 0; i < cnt; ++i) tracks_out[first + i].file_type = in[i].is_mp4 ? RG_FILE_AAC : RG_FILE_MP3;
+        else rc = rg_album_part(c, descs.data(), cnt, c->d_arena.p, arena_bytes, gi, groups.size(), tracks_out + first);
+        if (rc != RG_OK) return rc;
+        for (size_t i = 0; i < cnt; ++i) tracks_out[first + i].file_type = g.in[i].is_mp4 ? RG_FILE_AAC : RG_FILE_MP3;
         if (trace) fprintf(stderr, "[rg_analyze_album] analysis %.1f ms\n", (now() - t2) * 1e3);
     }
     if (groups.size() > 1) return rg_album_parts_fold(c, groups.size());
     return RG_OK;
+}
+
+extern "C" int rg_analyze_album_begin(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, rg_track_result *tracks_out,
+                                      size_t *failed_index) {
+    if (failed_index) *failed_index = (size_t)-1;
+    if (!c || (n && (!paths || !tracks_out))) return RG_ERR_INVALID_ARG;
+    return no_throw(c, [&] { return album_begin_impl(c, paths, n, track_index, tracks_out, failed_index); });
 }
 
 extern "C" int rg_analyze_album(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, rg_track_result *tracks_out,
@@ -233,12 +244,9 @@ extern "C" int rg_analyze_album(rg_ctx *c, const char *const *paths, size_t n, i
 // (fold: rg_analyze_albums -- every batch's tracks are folded into their albums' packs as well)
 static int analyze_tracks_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, int32_t track_index, rg_track_result *out,
                                 int32_t *status_out, AlbumFold *fold = nullptr) {
-    paths += first;
     out += first;
     status_out += first;
-    std::vector<LoadedAudio> &in = file_pool(c, n);
-    std::vector<int> rcs;
-    std::vector<std::string> errs;
+    FileGroup g(c, paths, first, n);
     // parts (PartsRun), track mode: every file of the group has to come through the loader pipeline for them to count
     PartsRun parts;
     parts.album = 0;
@@ -246,61 +254,45 @@ static int analyze_tracks_group(rg_ctx *c, const char *const *paths, size_t firs
     bool use_parts = false;
     int rc = parts_allowed(c, n, 1 /* the call's other groups do not matter: tracks are independent */, &use_parts);
     if (rc != RG_OK) return rc;
-    c->file_track_index = track_index;
-    rc = load_many(c, paths, n, &in, &rcs, &errs, use_parts ? &parts : nullptr);
-    c->file_track_index = -1;
+    rc = g.load(LoadOpts{track_index}, use_parts ? &parts : nullptr);
     if (rc != RG_OK) return rc;
-    if (use_parts && !parts.broken && parts.file_of.size() == n) {
-        RG_HIP(c, rg_sync_slots(c, RG_SLOT_STREAMS));
-        bool flagged = false;
-        for (size_t j = 0; j < n; ++j) flagged = flagged || (c->kernel_variant == 0 && (c->h_part_results.p[j].flags & RG_TRACK_FLAG_IMPRECISE));
-        if (!flagged) {  // (else: the plain route below, which repeats flagged tracks on the order-faithful kernel)
-            for (size_t j = 0; j < n; ++j) {
-                const size_t i = parts.file_of[j];
-                out[i] = c->h_part_results.p[j];
-                out[i].file_type = in[i].is_mp4 ? RG_FILE_AAC : RG_FILE_MP3;
-                status_out[i] = RG_OK;
-                c->file_errors[first + i].clear();
-            }
-            return RG_OK;
+    bool stand = false;
+    rc = take_parts(c, use_parts ? &parts : nullptr, g.in, n, out, &stand);
+    if (rc != RG_OK) return rc;
+    if (stand) {
+        for (size_t i = 0; i < n; ++i) {
+            status_out[i] = RG_OK;
+            c->file_errors[first + i].clear();
         }
+        return RG_OK;
     }
     if (fold && parts.n_parts) {  // parts were folded already: the plain route below starts the packs over
         rc = fold_init(c, fold);
         if (rc != RG_OK) return rc;
     }
-    // the batch holds the files that loaded and whose rate the analysis knows; `slot` maps them back
-    std::vector<size_t> slot;
-    for (size_t i = 0; i < n; ++i) {
+    const auto mark = [&](size_t i, int code, const std::string &text) {
         memset(&out[i], 0, sizeof out[i]);
-        status_out[i] = rcs[i];
-        c->file_errors[first + i] = errs[i];
-        if (rcs[i] != RG_OK) continue;
-        std::string msg;
-        const int frc = file_outcome(in[i], RG_OK, errs[i], paths[i], track_index, &msg);
-        if (frc != RG_OK) {
-            status_out[i] = frc;
-            c->file_errors[first + i] = msg;
-            continue;
-        }
-        if (fold && !stageable(in[i])) {  // rg_analyze_albums: this file fails alone instead of failing every file of the batch
-            status_out[i] = RG_ERR_FORMAT;
-            c->file_errors[first + i] = std::string("Failed to probe format: ") + paths[i];
-            continue;
-        }
-        slot.push_back(i);
-    }
-    if (slot.empty()) return RG_OK;
-    rc = run_good_files(c, in, slot, out, [&](const rg_track_desc *descs, size_t k, size_t arena_bytes, rg_track_result *res) {
-        return rg_analyze_pcm_batch(c, descs, k, c->d_arena.p, arena_bytes, 1, res, nullptr);
-    });
-    if (rc != RG_OK) {
-        fail_batch(c, slot, first, rc, status_out);
+        status_out[i] = code;
+        c->file_errors[first + i] = text;
+    };
+    // the batch holds the files that loaded and whose rate the analysis knows
+    const auto screen = [&](size_t i, std::string *text) -> int {
+        const int frc = file_outcome(g.in[i], RG_OK, g.errs[i], g.paths[i], track_index, text);
+        if (frc != RG_OK || !fold || stageable(g.in[i])) return frc;
+        *text = std::string("Failed to probe format: ") + g.paths[i];  // rg_analyze_albums: this file fails alone instead of failing every file of the batch
+        return RG_ERR_FORMAT;
+    };
+    const auto work = [&]() -> int {
+        std::vector<rg_track_result> res(g.slot.size());
+        const int wrc = rg_analyze_pcm_batch(c, g.descs.data(), g.slot.size(), c->d_arena.p, g.arena_bytes, 1, res.data(), nullptr);
+        if (wrc != RG_OK) return wrc;
+        g.scatter(res, out);
+        for (size_t k = 0; k < g.slot.size(); ++k) out[g.slot[k]].file_type = g.in[k].is_mp4 ? RG_FILE_AAC : RG_FILE_MP3;
         return RG_OK;
-    }
-    for (size_t k = 0; k < slot.size(); ++k) out[slot[k]].file_type = in[k].is_mp4 ? RG_FILE_AAC : RG_FILE_MP3;
-    if (fold) return fold_batch(c, fold, slot.data(), slot.size(), c->slot().stream);
-    return RG_OK;
+    };
+    rc = g.run(screen, mark, work);
+    if (rc != RG_OK || !g.done || !fold) return rc;
+    return fold_batch(c, fold, g.slot.data(), g.slot.size(), c->slot().stream);
 }
 
 // `-r` over a whole library must not need the whole library's PCM in HBM at once: the files are taken in groups
@@ -308,16 +300,7 @@ static int analyze_tracks_group(rg_ctx *c, const char *const *paths, size_t firs
 extern "C" int rg_analyze_tracks(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, rg_track_result *out,
                                  int32_t *status_out) {
     if (!c || (n && (!paths || !out || !status_out))) return RG_ERR_INVALID_ARG;
-    c->file_errors.assign(n, std::string());
-    int rc = rg_bind_device(c);
-    if (rc != RG_OK) return rc;
-    std::vector<std::pair<size_t, size_t>> groups;
-    file_groups(c, paths, n, &groups);
-    for (const auto &g : groups) {
-        rc = analyze_tracks_group(c, paths, g.first, g.second, track_index, out, status_out);
-        if (rc != RG_OK) return rc;
-    }
-    return RG_OK;
+    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return analyze_tracks_group(c, paths, first, cnt, track_index, out, status_out); });
 }
 
 extern "C" const char *rg_tracks_error(const rg_ctx *c, size_t i) {
@@ -442,512 +425,142 @@ extern "C" int rg_analyze_albums(rg_ctx *c, const char *const *paths, size_t n, 
                                  int32_t track_index, rg_track_result *tracks_out, int32_t *status_out, rg_album_result *albums_out,
                                  int32_t *album_status_out) {
     if (!c) return RG_ERR_INVALID_ARG;
-    if ((n && (!paths || !tracks_out || !status_out)) || (n_albums && (!albums_out || !album_status_out)))
-        return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_analyze_albums: null input or output array");
-    std::string why;
-    if (rg_albums_check(album_first, n_albums, n, &why) != RG_OK) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_analyze_albums: %s", why.c_str());
-    c->file_errors.assign(n, std::string());
-    for (size_t a = 0; a < n_albums; ++a) memset(&albums_out[a], 0, sizeof albums_out[a]);
-    std::vector<char> done(n_albums, 0);
-    size_t files_done = 0;
-    int rc = rg_bind_device(c);
-    if (rc == RG_OK)
-        rc = analyze_albums_impl(c, paths, n, album_first, n_albums, track_index, tracks_out, status_out, albums_out, album_status_out,
-                                 done, &files_done);
-    if (rc != RG_OK) {  // the call itself failed (a device error): what it did not finish carries the call's code and text
-        const std::string text = c->err;
-        for (size_t i = files_done; i < n; ++i) {
-            memset(&tracks_out[i], 0, sizeof tracks_out[i]);
-            status_out[i] = rc;
-            c->file_errors[i] = text;
-        }
-        for (size_t a = 0; a < n_albums; ++a)
-            if (!done[a]) {
-                memset(&albums_out[a], 0, sizeof albums_out[a]);
-                album_status_out[a] = rc;
-            }
-        c->err = text;
-    }
-    return rc;
-}
-
-// ---- rg_flac_verify (include/mp3rgain_amd_flac.h) ---------------------------------------------------------------------------
-// one group of the call: files [first, first + n).  The route is the analysis's: load_many, stage_loaded, then the hash of
-// what lies in the arena (device decoder) or of the host decoder's PCM (tuning key 14 = 0), then the per-file records.
-static int flac_verify_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, rg_flac_verify_result *out) {
-    paths += first;
-    out += first;
-    std::vector<LoadedAudio> &in = file_pool(c, n);
-    std::vector<int> rcs;
-    std::vector<std::string> errs;
-    // no decoder command here: what this library does not decode itself is not a FLAC stream it could verify
-    std::string cmd;
-    cmd.swap(c->decoder_cmd);
-    int rc = load_many(c, paths, n, &in, &rcs, &errs, nullptr);
-    cmd.swap(c->decoder_cmd);
-    if (rc != RG_OK) return rc;
-    // everything that loaded and is not a WAV stream goes through the staging, as in an analysis call (what the loader
-    // pipeline has put into the arena already stays accounted for); only the FLAC streams are hashed
-    std::vector<size_t> slot;
-    for (size_t i = 0; i < n; ++i) {
-        out[i].status = rcs[i];
-        c->file_errors[first + i] = errs[i];
-        if (rcs[i] != RG_OK) continue;
-        if (in[i].kind == LoadedAudio::Wav) {
-            out[i].status = RG_ERR_FORMAT;
-            c->file_errors[first + i] = std::string("Not a native FLAC stream: ") + paths[i];
-            continue;
-        }
-        slot.push_back(i);
-    }
-    if (slot.empty()) return RG_OK;
-    for (size_t k = 0; k < slot.size(); ++k)
-        if (slot[k] != k) std::swap(in[k], in[slot[k]]);
-    auto fail_all = [&](int code) {
-        for (size_t k = 0; k < slot.size(); ++k) {
-            memset(&out[slot[k]], 0, sizeof out[slot[k]]);
-            out[slot[k]].status = code;
-            c->file_errors[first + slot[k]] = c->err;
-        }
+    return no_throw(c, [&]() -> int {
+        if ((n && (!paths || !tracks_out || !status_out)) || (n_albums && (!albums_out || !album_status_out)))
+            return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_analyze_albums: null input or output array");
+        std::string why;
+        if (rg_albums_check(album_first, n_albums, n, &why) != RG_OK) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_analyze_albums: %s", why.c_str());
+        c->file_errors.assign(n, std::string());
+        for (size_t a = 0; a < n_albums; ++a) memset(&albums_out[a], 0, sizeof albums_out[a]);
+        std::vector<char> done(n_albums, 0);
+        size_t files_done = 0;
+        int rc = rg_bind_device(c);
+        if (rc == RG_OK)
+            rc = no_throw(c, [&] {
+                return analyze_albums_impl(c, paths, n, album_first, n_albums, track_index, tracks_out, status_out, albums_out, album_status_out,
+                                           done, &files_done);
+            });
+        if (rc != RG_OK) return fail_rest(c, rc, files_done, n, done, tracks_out, status_out, albums_out, album_status_out);
         return RG_OK;
-    };
-    std::vector<rg_track_desc> descs;
-    std::vector<FlacCounts> counts;
-    size_t arena_bytes = 0;
-    rc = stage_loaded(c, in, slot.size(), &descs, &arena_bytes, &counts);
-    if (rc != RG_OK) return fail_all(rc);
-    std::vector<RgFlacMd5Rec> recs;
-    std::vector<size_t> rec_of;  // record -> position in the batch
-    for (size_t k = 0; k < slot.size(); ++k) {
-        rg_flac_verify_result &r = out[slot[k]];
-        if (in[k].kind != LoadedAudio::Flac) {
-            r.status = RG_ERR_FORMAT;
-            c->file_errors[first + slot[k]] = std::string("Not a native FLAC stream: ") + paths[slot[k]];
-            continue;
-        }
-        rg_flac_info si;
-        (void)rg_flac_scan(in[k].file_bytes.data(), in[k].file_bytes.size(), &si);  // (load_flac has walked this stream)
-        if (rg_flac_stream_md5(in[k].file_bytes.data(), in[k].file_bytes.size(), r.md5_stream) == 1) r.flags |= RG_FLAC_VERIFY_HAS_SIGNATURE;
-        r.frames = descs[k].frames;
-        r.total_samples = si.total_samples;
-        r.audio_frames = counts[k].decoded;
-        r.dropped_frames = counts[k].dropped;
-        RgFlacMd5Rec rec;
-        if (in[k].flac_frames.empty()) {  // the host decoder's PCM, in the arena's format (or a stream without frames)
-            rg_track_desc d = descs[k];
-            d.offset_bytes = 0;
-            rc = rg_flac_md5_record(c, slot[k], d, in[k].flac_bps, in[k].flac_pcm.data(), in[k].flac_pcm.size(), &rec);
-            if (rc != RG_OK) return fail_all(rc);
-            rg_flac_md5_host(rec, r.md5_decoded);
-            continue;
-        }
-        rc = rg_flac_md5_record(c, slot[k], descs[k], in[k].flac_bps, c->d_arena.p, arena_bytes, &rec);
-        if (rc != RG_OK) return fail_all(rc);
-        recs.push_back(rec);
-        rec_of.push_back(k);
-    }
-    if (!recs.empty()) {  // on the stream the decode ran on
-        std::vector<uint8_t> dig(recs.size() * 16);
-        rc = rg_flac_md5_device(c, recs.data(), recs.size(), dig.data(), c->user_attached ? c->user_stream : c->slot().stream);
-        if (rc != RG_OK) return fail_all(rc);
-        for (size_t j = 0; j < recs.size(); ++j) memcpy(out[slot[rec_of[j]]].md5_decoded, &dig[16 * j], 16);
-    }
-    for (size_t k = 0; k < slot.size(); ++k) {
-        rg_flac_verify_result &r = out[slot[k]];
-        if (r.status != RG_OK) continue;
-        if ((r.flags & RG_FLAC_VERIFY_HAS_SIGNATURE) && memcmp(r.md5_stream, r.md5_decoded, 16) == 0) r.flags |= RG_FLAC_VERIFY_MD5_MATCH;
-        if (r.total_samples == 0 || r.total_samples == r.frames) r.flags |= RG_FLAC_VERIFY_LENGTH_MATCH;
-        if (r.dropped_frames == 0) r.flags |= RG_FLAC_VERIFY_COMPLETE;
-    }
-    return RG_OK;
-}
-
-extern "C" int rg_flac_verify(rg_ctx *c, const char *const *paths, size_t n, rg_flac_verify_result *out) {
-    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
-    c->file_errors.assign(n, std::string());
-    if (n) memset(out, 0, n * sizeof *out);
-    int rc = rg_bind_device(c);
-    if (rc != RG_OK) return rc;
-    try {
-        std::vector<std::pair<size_t, size_t>> groups;
-        file_groups(c, paths, n, &groups);
-        for (const auto &g : groups) {
-            rc = flac_verify_group(c, paths, g.first, g.second, out);
-            if (rc != RG_OK) return rc;
-        }
-    } catch (const std::bad_alloc &) {
-        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
-    }
-    return RG_OK;
-}
-
-// ---- rg_mp3_verify (include/mp3rgain_amd_mp3verify.h) ---------------------------------------------------------------------
-// one group of the call.  The decode side is the analysis's (load_many without a decoder command, stage_loaded), so how many
-// frames were dropped is the route's own verdict; the loader keeps the bytes of MPEG streams as read while this runs.  The
-// checksums: one upload of the group's bytes with their range and frame tables and the kernels of rg_mp3_crc.hip, on the
-// stream the decode ran on; with tuning key 6 = 0 (the host decoder) the host twin.
-static int mp3_verify_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, rg_mp3_verify_result *out) {
-    paths += first;
-    out += first;
-    std::vector<LoadedAudio> &in = file_pool(c, n);
-    std::vector<int> rcs;
-    std::vector<std::string> errs;
-    struct Quiet {  // no decoder command; MPEG bytes kept
-        rg_ctx *c;
-        std::string cmd;
-        explicit Quiet(rg_ctx *c) : c(c) { cmd.swap(c->decoder_cmd); c->keep_mpeg_bytes = true; }
-        ~Quiet() { cmd.swap(c->decoder_cmd); c->keep_mpeg_bytes = false; }
-    };
-    int rc;
-    {
-        Quiet q(c);
-        rc = load_many(c, paths, n, &in, &rcs, &errs, nullptr);
-    }
-    if (rc != RG_OK) return rc;
-    std::vector<size_t> slot;
-    for (size_t i = 0; i < n; ++i) {
-        out[i].status = rcs[i];
-        c->file_errors[first + i] = errs[i];
-        if (rcs[i] != RG_OK) continue;
-        const bool mpeg = in[i].kind == LoadedAudio::Planar || in[i].kind == LoadedAudio::Split || in[i].kind == LoadedAudio::Staged;
-        if (!mpeg || in[i].mpeg_in_mp4) {
-            out[i].status = RG_ERR_FORMAT;
-            c->file_errors[first + i] = std::string("Not a bare MPEG Layer III stream: ") + paths[i];
-            continue;
-        }
-        slot.push_back(i);
-    }
-    if (slot.empty()) return RG_OK;
-    for (size_t k = 0; k < slot.size(); ++k)
-        if (slot[k] != k) std::swap(in[k], in[slot[k]]);
-    const size_t m = slot.size();
-    auto fail_all = [&](int code) {
-        for (size_t k = 0; k < m; ++k) {
-            memset(&out[slot[k]], 0, sizeof out[slot[k]]);
-            out[slot[k]].status = code;
-            c->file_errors[first + slot[k]] = c->err;
-        }
-        return RG_OK;
-    };
-    std::vector<rg_track_desc> descs;
-    size_t arena_bytes = 0;
-    rc = stage_loaded(c, in, m, &descs, &arena_bytes);
-    if (rc != RG_OK) return fail_all(rc);
-    std::vector<RgMp3VerifyPlan> plans(m);
-    std::vector<uint32_t> dropped(m, 0);
-    std::vector<char> live(m, 0);
-    for (size_t k = 0; k < m; ++k) {
-        const LoadedAudio &la = in[k];
-        if (rg_mp3_verify_plan(la.file_bytes.data(), la.file_bytes.size(), &plans[k]) != RG_OK) {
-            out[slot[k]].status = RG_ERR_FORMAT;
-            c->file_errors[first + slot[k]] = std::string("Not a bare MPEG Layer III stream: ") + paths[slot[k]];
-            continue;
-        }
-        live[k] = 1;
-        const uint32_t spf = plans[k].si.samples_per_frame ? plans[k].si.samples_per_frame : 1152;
-        dropped[k] = la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
-    }
-    std::vector<uint16_t> music(m, 0);
-    std::vector<uint32_t> failed(m, 0);
-    if (c->gpu_mp3_decode == 0) {  // the host twin
-        for (size_t k = 0; k < m; ++k) {
-            if (!live[k]) continue;
-            const uint8_t *d = in[k].file_bytes.data();
-            music[k] = rg_mp3_crc_range_host(d, plans[k].music_off, plans[k].music_len);
-            for (uint64_t o : plans[k].prot) failed[k] += rg_mp3_frame_crc_host(d, in[k].file_bytes.size(), o) ? 0u : 1u;
-        }
-    } else {
-        std::vector<const uint8_t *> parts(m);
-        std::vector<uint64_t> part_off(m), part_len(m), r_off(m), r_len(m), f_off;
-        std::vector<size_t> f_of;
-        uint64_t total = 0;
-        for (size_t k = 0; k < m; ++k) {
-            parts[k] = in[k].file_bytes.data();
-            part_off[k] = total;
-            part_len[k] = live[k] ? in[k].file_bytes.size() : 0;
-            r_off[k] = total + (live[k] ? plans[k].music_off : 0);
-            r_len[k] = live[k] ? plans[k].music_len : 0;
-            if (live[k])
-                for (uint64_t o : plans[k].prot) {
-                    f_off.push_back(total + o);
-                    f_of.push_back(k);
-                }
-            total = (total + part_len[k] + 15) & ~(uint64_t)15;
-        }
-        std::vector<uint8_t> ok(f_off.size() ? f_off.size() : 1);
-        RgMp3CrcJob job;
-        job.parts = parts.data();
-        job.part_off = part_off.data();
-        job.part_len = part_len.data();
-        job.n_parts = m;
-        job.nbytes = total;
-        job.range_off = r_off.data();
-        job.range_len = r_len.data();
-        job.n_ranges = m;
-        job.frame_off = f_off.data();
-        job.n_frames = f_off.size();
-        job.crc_out = music.data();
-        job.ok_out = ok.data();
-        rc = rg_mp3_crc_device(c, job, c->user_attached ? c->user_stream : c->slot().stream);
-        if (rc != RG_OK) return fail_all(rc);
-        for (size_t j = 0; j < f_off.size(); ++j) failed[f_of[j]] += ok[j] ? 0u : 1u;
-    }
-    for (size_t k = 0; k < m; ++k)
-        if (live[k]) rg_mp3_verify_fill(in[k].file_bytes.data(), in[k].file_bytes.size(), plans[k], dropped[k], music[k], failed[k], &out[slot[k]]);
-    return RG_OK;
-}
-
-extern "C" int rg_mp3_verify(rg_ctx *c, const char *const *paths, size_t n, rg_mp3_verify_result *out) {
-    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
-    c->file_errors.assign(n, std::string());
-    if (n) memset(out, 0, n * sizeof *out);
-    int rc = rg_bind_device(c);
-    if (rc != RG_OK) return rc;
-    try {
-        std::vector<std::pair<size_t, size_t>> groups;
-        file_groups(c, paths, n, &groups);
-        for (const auto &g : groups) {
-            rc = mp3_verify_group(c, paths, g.first, g.second, out);
-            if (rc != RG_OK) return rc;
-        }
-    } catch (const std::bad_alloc &) {
-        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
-    }
-    return RG_OK;
+    });
 }
 
 // find_peak_amplitude (src/replaygain.rs:1140-1249): max |x| over ALL channels, no loudness analysis
-// ---- rg_rip_checksums (include/mp3rgain_amd_rip.h) --------------------------------------------------------------------------
-// one group of the call: files [first, first + n).  The route is rg_flac_verify's -- load_many without a decoder command,
-// stage_loaded -- except that 16-bit stereo WAV streams are kept.  Whatever route put a track's PCM into the arena (device
-// FLAC decoder, the host decoder's planes by copy, the WAV de-interleave), the two kernels of rg_rip_crc.hip read it there, on
-// the stream the decode ran on, so tuning key 14 cannot show in the records.
-static int rip_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const uint32_t *track_flags, rg_rip_result *out) {
-    paths += first;
-    out += first;
-    if (track_flags) track_flags += first;
-    std::vector<LoadedAudio> &in = file_pool(c, n);
-    std::vector<int> rcs;
-    std::vector<std::string> errs;
-    std::string cmd;
-    cmd.swap(c->decoder_cmd);
-    int rc = load_many(c, paths, n, &in, &rcs, &errs, nullptr);
-    cmd.swap(c->decoder_cmd);
-    if (rc != RG_OK) return rc;
-    auto refuse = [&](size_t i, const std::string &why) {
-        out[i].status = RG_ERR_FORMAT;
-        c->file_errors[first + i] = "No rip checksums (" + why + "): " + paths[i];
-    };
-    // everything that loaded goes through the staging, as in an analysis call (what the loader pipeline has put into the arena
-    // already stays accounted for), except WAV streams that take no part: the staging cannot lay out every kind of them
-    std::vector<size_t> slot;
-    for (size_t i = 0; i < n; ++i) {
-        out[i].status = rcs[i];
-        c->file_errors[first + i] = errs[i];
-        if (rcs[i] != RG_OK) continue;
-        if (in[i].kind == LoadedAudio::Wav) {
-            rg_wav_info w;
-            if (rg_wav_parse(in[i].wav.data(), in[i].wav.size(), &w) != RG_OK) {
-                out[i].status = RG_ERR_FORMAT;
-                c->file_errors[first + i] = std::string("Failed to probe format: ") + paths[i];
-                continue;
-            }
-            if (w.sample_format != 1 || w.bits_per_sample != 16 || w.channels != 2) {
-                refuse(i, std::to_string(w.channels) + " channel(s) of " + std::to_string(w.bits_per_sample) + "-bit " +
-                              (w.sample_format == 3 ? "float" : "integer") + " PCM, not 2 of 16-bit integer");
-                continue;
-            }
-        }
-        slot.push_back(i);
-    }
-    if (slot.empty()) return RG_OK;
-    for (size_t k = 0; k < slot.size(); ++k)
-        if (slot[k] != k) std::swap(in[k], in[slot[k]]);
-    auto fail_all = [&](int code) {
-        for (size_t k = 0; k < slot.size(); ++k) {
-            memset(&out[slot[k]], 0, sizeof out[slot[k]]);
-            out[slot[k]].status = code;
-            c->file_errors[first + slot[k]] = c->err;
-        }
-        return RG_OK;
-    };
-    std::vector<rg_track_desc> descs;
-    std::vector<FlacCounts> counts;
-    size_t arena_bytes = 0;
-    rc = stage_loaded(c, in, slot.size(), &descs, &arena_bytes, &counts);
-    if (rc != RG_OK) return fail_all(rc);
-    std::vector<RgRipTrack> recs;
-    std::vector<size_t> rec_of;  // record -> position in the batch
-    for (size_t k = 0; k < slot.size(); ++k) {
-        const size_t i = slot[k];
-        if (in[k].kind != LoadedAudio::Wav && in[k].kind != LoadedAudio::Flac) {
-            refuse(i, "an MPEG stream, not a WAV or native FLAC stream");
-            continue;
-        }
-        if (in[k].kind == LoadedAudio::Flac && (in[k].flac_bps != 16 || in[k].channels != 2)) {
-            refuse(i, std::to_string(in[k].channels) + " channel(s) of " + std::to_string(in[k].flac_bps) + " bits per sample, not 2 of 16");
-            continue;
-        }
-        RgRipTrack rec;
-        char err[256] = "";
-        rc = rg_rip_track_record(i, descs[k], track_flags ? track_flags[i] : 0u, arena_bytes, &rec, err, sizeof err);
-        if (rc == RG_ERR_FORMAT) {
-            refuse(i, err);
-            continue;
-        }
-        if (rc != RG_OK) return fail_all(rg_set_err(c, rc, "%s", err));
-        recs.push_back(rec);
-        rec_of.push_back(k);
-    }
-    if (recs.empty()) return RG_OK;
-    std::vector<RgRipSums> sums(recs.size());
-    rc = rg_rip_device(c, c->d_arena.p, recs.data(), recs.size(), sums.data(), c->user_attached ? c->user_stream : c->slot().stream);
-    if (rc != RG_OK) return fail_all(rc);
-    for (size_t j = 0; j < recs.size(); ++j) {
-        const size_t k = rec_of[j];
-        rg_rip_fill(sums[j], descs[k].frames, descs[k].sample_rate, counts[k].dropped, &out[slot[k]]);
-    }
-    return RG_OK;
-}
-
-extern "C" int rg_rip_checksums(rg_ctx *c, const char *const *paths, size_t n, const uint32_t *track_flags, rg_rip_result *out) {
-    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
-    c->file_errors.assign(n, std::string());
-    if (n) memset(out, 0, n * sizeof *out);
-    int rc = rg_bind_device(c);
-    if (rc != RG_OK) return rc;
-    try {
-        std::vector<std::pair<size_t, size_t>> groups;
-        file_groups(c, paths, n, &groups);
-        for (const auto &g : groups) {
-            rc = rip_group(c, paths, g.first, g.second, track_flags, out);
-            if (rc != RG_OK) return rc;
-        }
-    } catch (const std::bad_alloc &) {
-        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
-    }
-    return RG_OK;
-}
-
 extern "C" int rg_find_peak_amplitude(rg_ctx *c, const char *path, rg_peak_result *out) {
     if (!c || !out) return RG_ERR_INVALID_ARG;
-    rg_track_desc desc;
-    size_t arena_bytes = 0;
-    const int rc = load_and_stage_one(c, path, -1, &desc, &arena_bytes);
-    if (rc != RG_OK) return rc;
-    // the arena was produced on the stream rg_find_peak_pcm uses, so no further ordering is needed
-    return rg_find_peak_pcm(c, &desc, c->d_arena.p, arena_bytes, 1, out);
+    return no_throw(c, [&]() -> int {
+        rg_track_desc desc;
+        size_t arena_bytes = 0;
+        const int rc = load_and_stage_one(c, path, -1, &desc, &arena_bytes);
+        if (rc != RG_OK) return rc;
+        // the arena was produced on the stream rg_find_peak_pcm uses, so no further ordering is needed
+        return rg_find_peak_pcm(c, &desc, c->d_arena.p, arena_bytes, 1, out);
+    });
 }
 
 // ---- EBU R 128 (include/mp3rgain_amd_r128.h): the same loaders, decoders and groups; the analysis is rg_r128.hip's ---------
-// one group of files -> their results; album: the first failing file in input order aborts (its index in *failed), else a
-// failing file fails alone
+// one group of files -> their results; album: the first failing file in input order aborts the call, else a failing file
+// fails alone
 // (kept_tr / kept_slot / kept_e, rg_r128_analyze_albums: the device descriptors of the files that were analysed, their indices in
 // the group, and their hop energies in a buffer that is the caller's to free)
 static int r128_files_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, int32_t track_index, int want_tp, bool album,
                             rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out /* tracks only; may be nullptr */,
                             std::vector<RgR128TrackDev> *kept_tr = nullptr, std::vector<size_t> *kept_slot = nullptr,
                             double **kept_e = nullptr) {
-    paths += first;
     out += first;
     if (dyn_out) {
         dyn_out += first;
         memset(dyn_out, 0, n * sizeof *dyn_out);
     }
-    std::vector<LoadedAudio> &in = file_pool(c, n);
-    std::vector<int> rcs;
-    std::vector<std::string> errs;
-    c->file_track_index = track_index;
-    int rc = load_many(c, paths, n, &in, &rcs, &errs, nullptr);
-    c->file_track_index = -1;
+    FileGroup g(c, paths, first, n);
+    int rc = g.load(LoadOpts{track_index});
     if (rc != RG_OK) return rc;
     const bool layout = rg_r128_channel_mode(c) == RG_R128_CHANNELS_LAYOUT;
-    std::vector<size_t> slot;
-    for (size_t i = 0; i < n; ++i) {
+    const auto screen = [&](size_t i, std::string *text) -> int {
+        const LoadedAudio &la = g.in[i];
+        text->clear();
+        const int frc = file_outcome(la, RG_OK, g.errs[i], g.paths[i], track_index, text, true);
+        if (frc != RG_OK) return frc;
+        if (!stageable(la)) {
+            *text = std::string("Failed to probe format: ") + g.paths[i];
+            return RG_ERR_FORMAT;
+        }
+        if (!layout) return RG_OK;
+        uint32_t channels = la.channels;  // a layout has 1 to 8 channels
+        if (la.kind == LoadedAudio::Wav) {
+            rg_wav_info wi;
+            channels = rg_wav_parse(la.wav.data(), la.wav.size(), &wi) == RG_OK ? wi.channels : 0;
+        }
+        if (channels >= 1 && channels <= 8) return RG_OK;
+        char m[128];
+        snprintf(m, sizeof m, "Unsupported channel count for layout analysis: %u (1 to 8)", channels);
+        *text = m;
+        return RG_ERR_INVALID_ARG;
+    };
+    const auto mark = [&](size_t i, int code, const std::string &text) {
         memset(&out[i], 0, sizeof out[i]);
-        std::string msg;
-        int frc = file_outcome(in[i], rcs[i], errs[i], paths[i], track_index, &msg, true);
-        if (frc == RG_OK && !stageable(in[i])) {
-            frc = RG_ERR_FORMAT;
-            msg = std::string("Failed to probe format: ") + paths[i];
-        }
-        if (frc == RG_OK && layout) {  // a layout has 1 to 8 channels
-            uint32_t channels = in[i].channels;
-            if (in[i].kind == LoadedAudio::Wav) {
-                rg_wav_info wi;
-                channels = rg_wav_parse(in[i].wav.data(), in[i].wav.size(), &wi) == RG_OK ? wi.channels : 0;
-            }
-            if (channels < 1 || channels > 8) {
-                char m[128];
-                snprintf(m, sizeof m, "Unsupported channel count for layout analysis: %u (1 to 8)", channels);
-                frc = RG_ERR_INVALID_ARG;
-                msg = m;
-            }
-        }
-        if (frc != RG_OK && album) return rg_set_err(c, frc, "%s", msg.c_str());
-        if (status_out) {
-            status_out[first + i] = frc;
-            c->file_errors[first + i] = msg;
-        }
-        if (frc == RG_OK) slot.push_back(i);
-    }
-    if (slot.empty()) return RG_OK;
-    std::vector<rg_r128_dynamics> dyn(dyn_out ? slot.size() : 0);
-    if (kept_tr) kept_tr->resize(slot.size());
-    rc = run_good_files(c, in, slot, out, [&](const rg_track_desc *descs, size_t k, size_t arena_bytes, rg_r128_track_result *res) {
+        if (!status_out) return;  // album: the first failing file fails the call
+        status_out[first + i] = code;
+        c->file_errors[first + i] = text;
+    };
+    std::vector<rg_r128_dynamics> dyn;
+    const auto work = [&]() -> int {
+        const size_t k = g.slot.size();
         // LAYOUT mode: every file's weights from its container's channel mask (file j of the batch is in[j] by now)
         std::vector<rg_r128_channel_weights> weights(layout ? k : 0);
         for (size_t j = 0; j < weights.size(); ++j) {
-            const uint32_t mask = in[j].kind == LoadedAudio::Wav ? wav_channel_mask(in[j].wav.data(), in[j].wav.size()) : 0u;
-            if (rg_r128_layout_weights(descs[j].channels, mask, &weights[j]) != RG_OK)
-                return rg_set_err(c, RG_ERR_INVALID_ARG, "Unsupported channel count for layout analysis: %u (1 to 8)", descs[j].channels);
+            const uint32_t mask = g.in[j].kind == LoadedAudio::Wav ? wav_channel_mask(g.in[j].wav.data(), g.in[j].wav.size()) : 0u;
+            if (rg_r128_layout_weights(g.descs[j].channels, mask, &weights[j]) != RG_OK)
+                return rg_set_err(c, RG_ERR_INVALID_ARG, "Unsupported channel count for layout analysis: %u (1 to 8)", g.descs[j].channels);
         }
-        return rg_r128_run(c, descs, k, c->d_arena.p, arena_bytes, want_tp, album ? 1 : 0, res, nullptr, dyn_out ? dyn.data() : nullptr, nullptr,
-                           kept_tr ? kept_tr->data() : nullptr, kept_e, layout ? weights.data() : nullptr);
-    });
-    if (rc != RG_OK) {
-        if (album) return rc;
-        if (kept_tr) kept_tr->clear();
-        fail_batch(c, slot, first, rc, status_out + first);
+        std::vector<rg_r128_track_result> res(k);
+        dyn.resize(dyn_out ? k : 0);
+        if (kept_tr) kept_tr->resize(k);
+        const int wrc = rg_r128_run(c, g.descs.data(), k, c->d_arena.p, g.arena_bytes, want_tp, album ? 1 : 0, res.data(), nullptr,
+                                    dyn_out ? dyn.data() : nullptr, nullptr, kept_tr ? kept_tr->data() : nullptr, kept_e,
+                                    layout ? weights.data() : nullptr);
+        if (wrc == RG_OK) g.scatter(res, out);
+        return wrc;
+    };
+    g.stop_at_first = album;
+    rc = g.run(screen, mark, work);
+    if (rc != RG_OK) return rc;
+    if (!g.done) {  // no file for the batch, or the batch failed and its files carry that
+        if (kept_tr && !g.slot.empty()) kept_tr->clear();
         return RG_OK;
     }
-    if (kept_slot) *kept_slot = slot;
-    for (size_t k = 0; k < slot.size() && dyn_out; ++k) dyn_out[slot[k]] = dyn[k];
+    if (kept_slot) *kept_slot = g.slot;
+    for (size_t k = 0; k < g.slot.size() && dyn_out; ++k) dyn_out[g.slot[k]] = dyn[k];
     return RG_OK;
 }
 
 static int r128_tracks(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
                        rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out) {
     if (!c || (n && (!paths || !out || !status_out))) return RG_ERR_INVALID_ARG;
-    c->file_errors.assign(n, std::string());
-    int rc = rg_bind_device(c);
-    if (rc != RG_OK) return rc;
-    std::vector<std::pair<size_t, size_t>> groups;
-    file_groups(c, paths, n, &groups);
-    for (const auto &g : groups) {
-        rc = r128_files_group(c, paths, g.first, g.second, track_index, want_true_peak, false, out, status_out, dyn_out);
-        if (rc != RG_OK) return rc;
-    }
-    return RG_OK;
+    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) {
+        return r128_files_group(c, paths, first, cnt, track_index, want_true_peak, false, out, status_out, dyn_out);
+    });
 }
 
 static int r128_album(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
                       rg_r128_track_result *tracks_out, rg_r128_album_result *album_out, rg_r128_dynamics *dyn_out,
                       rg_r128_dynamics *album_dyn_out) {
     if (!c || (n && (!paths || !tracks_out)) || !album_out) return RG_ERR_INVALID_ARG;
-    int rc = rg_bind_device(c);
-    if (rc != RG_OK) return rc;
-    std::vector<std::pair<size_t, size_t>> groups;
-    file_groups(c, paths, n, &groups);
-    rg_r128_album_reset(c);
-    for (const auto &g : groups) {
-        rc = r128_files_group(c, paths, g.first, g.second, track_index, want_true_peak, true, tracks_out, nullptr, nullptr);
-        if (rc != RG_OK) {
-            rg_r128_album_reset(c);
-            return rc;
+    return no_throw(c, [&]() -> int {
+        int rc = rg_bind_device(c);
+        if (rc != RG_OK) return rc;
+        std::vector<std::pair<size_t, size_t>> groups;
+        file_groups(c, paths, n, &groups);
+        rg_r128_album_reset(c);
+        for (const auto &g : groups) {
+            rc = r128_files_group(c, paths, g.first, g.second, track_index, want_true_peak, true, tracks_out, nullptr, nullptr);
+            if (rc != RG_OK) {
+                rg_r128_album_reset(c);
+                return rc;
+            }
         }
-    }
-    return rg_r128_album_end(c, want_true_peak, album_out, dyn_out, album_dyn_out, nullptr);
+        return rg_r128_album_end(c, want_true_peak, album_out, dyn_out, album_dyn_out, nullptr);
+    });
 }
 
 extern "C" int rg_r128_analyze_tracks(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
@@ -962,14 +575,14 @@ extern "C" int rg_r128_analyze_album(rg_ctx *c, const char *const *paths, size_t
 
 extern "C" int rg_r128_analyze_tracks_dynamics(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
                                                rg_r128_track_result *out, int32_t *status_out, rg_r128_dynamics *dyn_out) {
-    if (c && n && !dyn_out) return rg_set_err(c, RG_ERR_INVALID_ARG, "null dyn_out");
+    if (c && n && !dyn_out) return no_throw(c, [&] { return rg_set_err(c, RG_ERR_INVALID_ARG, "null dyn_out"); });
     return r128_tracks(c, paths, n, track_index, want_true_peak, out, status_out, dyn_out);
 }
 
 extern "C" int rg_r128_analyze_album_dynamics(rg_ctx *c, const char *const *paths, size_t n, int32_t track_index, int want_true_peak,
                                               rg_r128_track_result *tracks_out, rg_r128_album_result *album_out,
                                               rg_r128_dynamics *dyn_out, rg_r128_dynamics *album_dyn_out) {
-    if (c && ((n && !dyn_out) || !album_dyn_out)) return rg_set_err(c, RG_ERR_INVALID_ARG, "null dynamics output");
+    if (c && ((n && !dyn_out) || !album_dyn_out)) return no_throw(c, [&] { return rg_set_err(c, RG_ERR_INVALID_ARG, "null dynamics output"); });
     return r128_album(c, paths, n, track_index, want_true_peak, tracks_out, album_out, dyn_out, album_dyn_out);
 }
 
@@ -1055,42 +668,33 @@ static int r128_albums(rg_ctx *c, const char *fn, const char *const *paths, size
                        rg_r128_album_result *albums_out, int32_t *album_status_out, bool dynamics, rg_r128_dynamics *dyn_out,
                        rg_r128_dynamics *albums_dyn_out) {
     if (!c) return RG_ERR_INVALID_ARG;
-    if ((n && (!paths || !tracks_out || !status_out || (dynamics && !dyn_out))) ||
-        (n_albums && (!albums_out || !album_status_out || (dynamics && !albums_dyn_out))))
-        return rg_set_err(c, RG_ERR_INVALID_ARG, "%s: null input or output array", fn);
-    std::string why;
-    if (rg_albums_check(album_first, n_albums, n, &why) != RG_OK) return rg_set_err(c, RG_ERR_INVALID_ARG, "%s: %s", fn, why.c_str());
-    c->file_errors.assign(n, std::string());
-    for (size_t a = 0; a < n_albums; ++a) {
-        memset(&albums_out[a], 0, sizeof albums_out[a]);
-        if (dynamics) memset(&albums_dyn_out[a], 0, sizeof albums_dyn_out[a]);
-    }
-    if (dynamics && n) memset(dyn_out, 0, n * sizeof *dyn_out);
-    std::vector<char> done(n_albums, 0);
-    size_t files_done = 0;
-    std::vector<std::pair<size_t, double *>> bufs;
-    int rc = rg_bind_device(c);
-    if (rc == RG_OK)
-        rc = r128_albums_impl(c, paths, n, album_first, n_albums, track_index, want_tp, tracks_out, status_out, albums_out,
-                              album_status_out, dynamics, dyn_out, albums_dyn_out, done, &files_done, bufs);
-    for (const auto &b : bufs) (void)hipFree(b.second);
-    if (rc != RG_OK) {  // the call itself failed (a device error): what it did not finish carries the call's code and text
-        const std::string text = c->err;
-        for (size_t i = files_done; i < n; ++i) {
-            memset(&tracks_out[i], 0, sizeof tracks_out[i]);
-            if (dynamics) memset(&dyn_out[i], 0, sizeof dyn_out[i]);
-            status_out[i] = rc;
-            c->file_errors[i] = text;
+    return no_throw(c, [&]() -> int {
+        if ((n && (!paths || !tracks_out || !status_out || (dynamics && !dyn_out))) ||
+            (n_albums && (!albums_out || !album_status_out || (dynamics && !albums_dyn_out))))
+            return rg_set_err(c, RG_ERR_INVALID_ARG, "%s: null input or output array", fn);
+        std::string why;
+        if (rg_albums_check(album_first, n_albums, n, &why) != RG_OK) return rg_set_err(c, RG_ERR_INVALID_ARG, "%s: %s", fn, why.c_str());
+        c->file_errors.assign(n, std::string());
+        for (size_t a = 0; a < n_albums; ++a) {
+            memset(&albums_out[a], 0, sizeof albums_out[a]);
+            if (dynamics) memset(&albums_dyn_out[a], 0, sizeof albums_dyn_out[a]);
         }
-        for (size_t a = 0; a < n_albums; ++a)
-            if (!done[a]) {
-                memset(&albums_out[a], 0, sizeof albums_out[a]);
-                if (dynamics) memset(&albums_dyn_out[a], 0, sizeof albums_dyn_out[a]);
-                album_status_out[a] = rc;
-            }
-        c->err = text;
-    }
-    return rc;
+        if (dynamics && n) memset(dyn_out, 0, n * sizeof *dyn_out);
+        std::vector<char> done(n_albums, 0);
+        size_t files_done = 0;
+        std::vector<std::pair<size_t, double *>> bufs;
+        int rc = rg_bind_device(c);
+        if (rc == RG_OK)
+            rc = no_throw(c, [&] {
+                return r128_albums_impl(c, paths, n, album_first, n_albums, track_index, want_tp, tracks_out, status_out, albums_out,
+                                        album_status_out, dynamics, dyn_out, albums_dyn_out, done, &files_done, bufs);
+            });
+        for (const auto &b : bufs) (void)hipFree(b.second);
+        if (rc != RG_OK)
+            return fail_rest(c, rc, files_done, n, done, tracks_out, status_out, albums_out, album_status_out, dynamics ? dyn_out : nullptr,
+                             dynamics ? albums_dyn_out : nullptr);
+        return RG_OK;
+    });
 }
 
 extern "C" int rg_r128_analyze_albums(rg_ctx *c, const char *const *paths, size_t n, const size_t *album_first, size_t n_albums,

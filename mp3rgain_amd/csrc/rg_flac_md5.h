@@ -1,5 +1,5 @@
 // rg_flac_md5.h -- internal: the MD5 of decoded FLAC audio in the analysis arena (rg_flac_md5.hip), as the file layer's
-// verify call (rg_files.hip: rg_flac_verify) uses it.
+// verify call (rg_file_verify.hip: rg_flac_verify) uses it.
 #pragma once
 
 #include <hip/hip_runtime.h>

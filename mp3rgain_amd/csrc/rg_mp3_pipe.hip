@@ -126,8 +126,8 @@ double now() { return std::chrono::duration<double>(std::chrono::steady_clock::n
 class PipeCall {
 public:
     PipeCall(rg_ctx *c, const char *const *paths, size_t n, std::vector<LoadedAudio> *out, std::vector<int> *rcs, std::vector<std::string> *errs,
-             PartsRun *parts)
-        : c(c), P(mp3_pipe(c)), paths(paths), n(n), out(out), rcs(rcs), errs(errs), parts(parts), pf(n) {}
+             const LoadOpts &opts, PartsRun *parts)
+        : c(c), P(mp3_pipe(c)), paths(paths), n(n), out(out), rcs(rcs), errs(errs), opts(opts), parts(parts), pf(n) {}
     int run();
 
 private:
@@ -138,6 +138,7 @@ private:
     std::vector<LoadedAudio> *const out;
     std::vector<int> *const rcs;
     std::vector<std::string> *const errs;
+    const LoadOpts opts;  // the call's own copy: the loader threads read it
     PartsRun *const parts;
     std::vector<PipeFile> pf;
     // fixed by prepare()
@@ -146,8 +147,7 @@ private:
     size_t stage_want = 0;
     bool trace = false;
     double t_start = 0.0, copy_bound_at = 0.0;
-    std::string cmd;
-    int32_t track_index = -1;
+    std::string cmd;  // the decoder command, empty where the call's options withhold it
     int flac_route = 0, device = 0;
     // shared
     std::atomic<size_t> next_file{0};
@@ -224,8 +224,7 @@ int PipeCall::prepare() {
         if (c->stage_bytes()) cap = c->stage_bytes();  // tests: tiny blocks, so that a handful of small files exercises the whole rotation
         stage_want = std::min(cap, total + total / 8 + ((size_t)1 << 16));
     }
-    cmd = c->decoder_cmd;
-    track_index = c->file_track_index;
+    if (opts.decoder_command) cmd = c->decoder_cmd;
     flac_route = c->gpu_flac_decode;
     device = c->device;
     copy_bound_at = parts ? c->parts_min_bpu() : 0.0;
@@ -260,7 +259,7 @@ bool PipeCall::classify(size_t i, Mp3Scratch &sc, uint64_t *units, double *tl) {
             return false;
         }
         la.kind = LoadedAudio::Wav;
-        (*rcs)[i] = cmd.empty() ? RG_ERR_FORMAT : load_audio_for(cmd, 2, path, &la, &err, track_index, flac_route);
+        (*rcs)[i] = cmd.empty() ? RG_ERR_FORMAT : load_audio_for(cmd, 2, path, &la, &err, opts.track_index, flac_route);
         return false;
     }
     const bool mp4 = len >= 8 && memcmp(sc.p + 4, "ftyp", 4) == 0;
@@ -268,9 +267,9 @@ bool PipeCall::classify(size_t i, Mp3Scratch &sc, uint64_t *units, double *tl) {
     rg_mp3_stream_info si;
     uint64_t main_len = 0;
     tl[1] = trace ? now() : 0.0;
-    if (c->keep_mpeg_bytes && !mp4) la.file_bytes.assign(sc.p, sc.p + len);  // rg_mp3_verify: the compaction below works in place
+    if (opts.keep_mpeg_bytes && !mp4) la.file_bytes.assign(sc.p, sc.p + len);  // rg_mp3_verify: the compaction below works in place
     if (mp4 || rg_mp3_compact_stream(sc.p, len, &sc.slots, &sc.tiles, &main_len, &si) != RG_MP3DEC_OK || si.audio_frames == 0) {
-        (*rcs)[i] = load_audio_for(cmd, 2, path, &la, &err, track_index, flac_route);  // the decoder command, or the reference's probe error
+        (*rcs)[i] = load_audio_for(cmd, 2, path, &la, &err, opts.track_index, flac_route);  // the decoder command, or the reference's probe error
         return false;
     }
     la.sample_rate = si.sample_rate;
@@ -447,7 +446,7 @@ int PipeCall::analyze_part(const PipeChunk *ch, size_t index, bool last, bool st
         const size_t i = files[k];
         LoadedAudio &la = (*out)[i];
         std::string msg;
-        if (la.kind != LoadedAudio::Staged || file_outcome(la, (*rcs)[i], (*errs)[i], paths[i], track_index, &msg) != RG_OK) {
+        if (la.kind != LoadedAudio::Staged || file_outcome(la, (*rcs)[i], (*errs)[i], paths[i], opts.track_index, &msg) != RG_OK) {
             parts->broken = true;  // the plain route reports it, in input order
             return RG_OK;
         }
@@ -584,6 +583,6 @@ int PipeCall::run() {
 }  // namespace
 
 int rgf::pipe_load_many(rg_ctx *c, const char *const *paths, size_t n, std::vector<LoadedAudio> *out, std::vector<int> *rcs,
-                        std::vector<std::string> *errs, PartsRun *parts) {
-    return PipeCall(c, paths, n, out, rcs, errs, parts).run();
+                        std::vector<std::string> *errs, const LoadOpts &opts, PartsRun *parts) {
+    return PipeCall(c, paths, n, out, rcs, errs, opts, parts).run();
 }

@@ -1,5 +1,5 @@
 // rg_mp3verify.h -- internal: what rg_mp3verify.cpp (host: info-tag parser, frame walk, host twin of both CRCs, the result
-// record), rg_mp3_crc.hip (the kernels and their launcher) and rg_files.hip (rg_mp3_verify) share.
+// record), rg_mp3_crc.hip (the kernels and their launcher) and rg_file_verify.hip (rg_mp3_verify) share.
 #pragma once
 
 #include <stddef.h>

@@ -1,5 +1,5 @@
 // rg_rip.h -- internal: the rip checksums (include/mp3rgain_amd_rip.h) as rg_rip_crc.hip (kernels, launcher, seams),
-// rg_rip_host.cpp (the serial host twin and the kernels' fold arithmetic on the host) and rg_files.hip (rg_rip_checksums)
+// rg_rip_host.cpp (the serial host twin and the kernels' fold arithmetic on the host) and rg_file_verify.hip (rg_rip_checksums)
 // share them.  What one lane hashes, how two neighbours fold and how a track is finished is host and device code, written
 // once here; the kernels and the folded host route differ only in who walks the lanes.
 #pragma once

@@ -219,7 +219,7 @@ int stage_wavs(rg_ctx *c, const void *const *wav, const size_t *wav_len, size_t 
     RG_HIP(c, rg_sync_slots(c, c->n_slots));
     RG_HIP(c, c->d_wav.reserve(src_total ? src_total : 16));
     RG_HIP(c, c->d_arena.reserve(dst_total ? dst_total : 16));
-    hipStream_t fs = c->user_attached ? c->user_stream : c->slot().stream;
+    hipStream_t fs = c->file_stream();
     for (size_t i = 0; i < n; ++i) {
         rc = wav_copy_launch(c, items[i], c->d_arena.p + (*descs)[i].offset_bytes, fs);
         if (rc != RG_OK) return rc;
