@@ -29,7 +29,20 @@
  *                      arv2 = sum of lo32(p) + hi32(p)  mod 2^32
  *                  So a first track leaves out its first 2939 frames, and a last track leaves out its last 2940.
  *
- * Not here: drive-offset search, disc IDs and database lookups, CUETools DB parity, other widths or channel counts,
+ * DRIVE OFFSETS (rg_rip_offset_signatures).  A different pressing, or a drive whose read offset was not corrected, shifts the
+ * audio of a rip by a few samples; then every AccurateRip signature differs although the audio is the same.  So the signatures
+ * are also computed at every sample offset of a window.  The `n` tracks of a call are one disc, in call order.  Track t has
+ * N_t frames, and B_t = sum of N_u over u < t.  Disc positions are 64-bit.  W[j] = (uint16)L | (uint16)R << 16 of disc frame
+ * j for 0 <= j < sum N, and 0 for every other j.  from_t and to_t are exactly those above, from the track's flags.  For every
+ * offset o with -radius <= o <= radius, where 0 <= radius <= 2939 (RG_RIP_OFFSET_MAX), let
+ * p = (uint64)W[B_t + i - 1 + o] * i.  Then
+ *                      arv1_t(o) = sum over the i that count of lo32(p)            mod 2^32
+ *                      arv2_t(o) = sum over the i that count of lo32(p) + hi32(p)  mod 2^32
+ * A positive o takes the samples that lie later on the disc.  At o = 0 both are arv1 / arv2 above, bit for bit.  A first and
+ * a last track that are flagged never read outside the disc -- that is what the 2940 is for; unflagged tracks at the disc's
+ * edges read zeros outside it.  THE SIGN CONVENTION AND THE +-2939 WINDOW WERE NOT CHECKED AGAINST A RIPPER either.
+ *
+ * Not here: disc IDs and database lookups, CUETools DB parity, other widths or channel counts,
  * checksums of MPEG-decoded audio, cue sheets.  Nothing is written to files.
  */
 #ifndef MP3RGAIN_AMD_RIP_H
@@ -47,6 +60,8 @@ extern "C" {
 #define RG_RIP_CD_FRAMES   2u /* result flag: frames % 588 == 0   */
 #define RG_RIP_COMPLETE    4u /* result flag: dropped_frames == 0 */
 #define RG_RIP_AR_SKIP 2940u  /* 5 CD sectors of 588 frames */
+#define RG_RIP_OFFSET_MAX 2939        /* the largest radius of the offset window */
+#define RG_RIP_DISC_MAX_TRACKS 1024u  /* tracks of one disc: bounds the device's signature tables at about 48 MB */
 
 typedef struct rg_rip_result {
     int32_t status;          /* RG_OK, or why there are no checksums (text: rg_tracks_error(ctx, i)) */
@@ -94,6 +109,45 @@ int rg_rip_crc32_algebra(uint32_t a, uint32_t b, uint64_t n, uint32_t *product, 
  * kernels' (it must be 0).  `ctx` is an rg_ctx. */
 int rg_rip_rate(void *ctx, size_t n, uint64_t frames, int table_layout, size_t host_tracks, uint32_t threads, uint32_t reps, double warm_ms,
                 double *dev_ms, double *host_ms, size_t *mismatches);
+
+/* The AccurateRip signatures of a disc at every offset of -radius .. radius (DRIVE OFFSETS above).  The route is
+ * rg_rip_checksums': same loaders, both FLAC decoders (tuning key 14), WAV, no decoder command; out[i] is byte for byte what
+ * rg_rip_checksums gives for the same files and flags.  arv1 / arv2: n x (2 radius + 1) values, row-major, [t][o + radius];
+ * either may be NULL.  The tables are computed only when every file took part (status == RG_OK for all of them): a hole in
+ * the disc would silently shift every later track.  Otherwise the call returns RG_ERR_REFUSED, the text (rg_last_error) names
+ * the first file that failed, out[] is still filled and the tables are zero.  A FLAC file with dropped frames takes part with
+ * what was decoded; out[i] says so.  A disc must lie in the arena at once: a list the route would cut into groups (tuning key
+ * 13, or the device's size) is RG_ERR_REFUSED before anything is loaded, out[] and the tables zero.  RG_ERR_INVALID_ARG for a
+ * radius outside 0 .. RG_RIP_OFFSET_MAX or n > RG_RIP_DISC_MAX_TRACKS.  The tables are byte for byte the same for tuning key
+ * 14 = 1 and 14 = 0. */
+int rg_rip_offset_signatures(rg_ctx *ctx, const char *const *paths, size_t n, const uint32_t *track_flags, int32_t radius, rg_rip_result *out,
+                             uint32_t *arv1, uint32_t *arv2);
+
+/* Test seam: the disc that descs[0 .. n) describe in the host arena `arena`, as rg_rip_checksums_arena takes them (the same
+ * argument errors; in addition RG_ERR_INVALID_ARG for a radius outside 0 .. RG_RIP_OFFSET_MAX and n > RG_RIP_DISC_MAX_TRACKS;
+ * n = 0 is RG_OK).  Tracks lie anywhere in the arena, in any order, and may alias.  Tables as above; either may be NULL.
+ *   route 0  the definition, serially and as plainly as possible; `ctx` may be NULL
+ *   route 1  the arena copied to the device, and the kernel of rg_rip_offsets.hip (`ctx` is an rg_ctx)
+ *   route 2  arv1 only (arv2 must be NULL, else RG_ERR_INVALID_ARG), by the sliding recurrence on the host; `ctx` may be
+ *            NULL.  With f = max(from, 1), T = to, c = B - 1:  A(o + 1) = A(o) - f W[c + f + o] + (T + 1) W[c + T + 1 + o] - S(o),
+ *            where S(o) = sum of W[c + i + o] over i = f + 1 .. T + 1 slides as well.  An independent check on signs and edges. */
+int rg_rip_offsets_arena(void *ctx, int route, size_t n, const rg_track_desc *descs, const uint32_t *track_flags, int32_t radius,
+                         const void *arena, size_t arena_bytes, uint32_t *arv1, uint32_t *arv2);
+
+/* Test seam: how the offsets kernel cuts a disc.  tile_frames: frames of a track one block takes (tiles are counted from
+ * the track's first frame); block_lanes: its lanes.  Either may be NULL. */
+int rg_rip_offsets_kernel_shape(uint32_t *tile_frames, uint32_t *block_lanes);
+
+/* Measurement hook (tools/rip_offsets_rate.py): a disc of `n` tracks of `frames` frames of 16-bit stereo PCM, filled on the
+ * device, the first track flagged first and the last last.  After a warm-up of `warm_ms` milliseconds of launches, `reps`
+ * rounds of the tables' zeroing and the kernel at `radius` (dev_ms[r], HIP events around them), a lane holding `lane_offsets`
+ * consecutive offsets in registers: 23, the product's kernel, or 1, the plain form it is measured against.  Then the
+ * definition (route 0's arithmetic) for all n tracks at `host_offsets` offsets spread evenly over the window, -radius and
+ * +radius among them, on `threads` host threads over a host copy of the disc: *host_ms, the wall time of that;
+ * *host_products, the products it took (the disc's are *disc_products, which may be NULL).  *mismatches: (track, offset)
+ * pairs whose host values differ from the kernel's (it must be 0).  host_offsets = 0 runs no host pass.  `ctx` is an rg_ctx. */
+int rg_rip_offsets_rate(void *ctx, size_t n, uint64_t frames, int32_t radius, uint32_t lane_offsets, uint32_t host_offsets, uint32_t threads, uint32_t reps,
+                        double warm_ms, double *dev_ms, double *host_ms, uint64_t *host_products, uint64_t *disc_products, size_t *mismatches);
 
 #ifdef __cplusplus
 }

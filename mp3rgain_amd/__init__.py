@@ -24,11 +24,14 @@ from .replaygain import (  # noqa: F401
     ReplayGainError,
     ReplayGainResult,
     RipChecksums,
+    RipOffsetSignatures,
     analyze_album,
     analyze_track,
     find_peak_amplitude,
     is_available,
     r128_layout_weights,
+    rip_offsets_arena,
+    rip_offsets_kernel_shape,
 )
 
 __version__ = "0.1.0"

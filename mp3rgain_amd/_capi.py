@@ -247,6 +247,7 @@ R128_SYMBOLS = [
 # include/mp3rgain_amd_rip.h (rip checksums: CRC-32 and AccurateRip v1 / v2 per track)
 RIP_FIRST_TRACK, RIP_LAST_TRACK = 1, 2
 RIP_CD_RATE, RIP_CD_FRAMES, RIP_COMPLETE = 1, 2, 4
+RIP_OFFSET_MAX, RIP_DISC_MAX_TRACKS = 2939, 1024
 
 
 class RipRecord(C.Structure):  # rg_rip_result
@@ -270,6 +271,10 @@ RIP_SYMBOLS = [
     ("rg_rip_kernel_shape", _int, [_P(_u32), _P(_u32), _P(_u32)]),
     ("rg_rip_crc32_algebra", _int, [_u32, _u32, _u64, _P(_u32), _P(_u32)]),
     ("rg_rip_rate", _int, [_vp, _sz, _u64, _int, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_sz)]),
+    ("rg_rip_offset_signatures", _int, [_vp, _P(C.c_char_p), _sz, _P(_u32), C.c_int32, _P(RipRecord), _P(_u32), _P(_u32)]),
+    ("rg_rip_offsets_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _P(_u32), C.c_int32, _vp, _sz, _P(_u32), _P(_u32)]),
+    ("rg_rip_offsets_kernel_shape", _int, [_P(_u32), _P(_u32)]),
+    ("rg_rip_offsets_rate", _int, [_vp, _sz, _u64, C.c_int32, _u32, _u32, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_u64), _P(_u64), _P(_sz)]),
 ]
 
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions

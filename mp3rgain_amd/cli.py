@@ -67,6 +67,7 @@ class Options:  # src/main.rs:65-96
     verify: bool = False     # this façade only (--verify): FLAC files against the MD5 signature of their STREAMINFO
     rip: bool = False        # this façade only (--rip): the files are the tracks of one disc; CRC-32 and AccurateRip checksums
     rip_log: Optional[str] = None  # with --rip (--rip-log LOG): a ripper's log to compare the checksums with
+    rip_offsets: bool = False  # with --rip --rip-log (--rip-offsets): look for the log's drive offset within +-2939 samples
     files: List[Path] = field(default_factory=list)
 
 
@@ -132,6 +133,8 @@ def parse_args(args: List[str], out, err) -> Options:
             o.verify = True
         elif arg == "--rip":  # not in the reference: a command of its own, like --verify
             o.rip = True
+        elif arg == "--rip-offsets":
+            o.rip_offsets = True
         elif arg == "--rip-log":
             o.rip_log = need("--rip-log", "--rip-log requires an argument")
         elif arg == "--decoder":  # not in the reference: see the module docstring
@@ -230,6 +233,10 @@ def parse_args(args: List[str], out, err) -> Options:
         raise CliError("--surround requires --r128")
     if o.rip_log is not None and not o.rip:
         raise CliError("--rip-log requires --rip")
+    if o.rip_offsets and not o.rip:
+        raise CliError("--rip-offsets requires --rip")
+    if o.rip_offsets and o.rip_log is None:
+        raise CliError("--rip-offsets requires --rip-log")
     return o
 
 
@@ -320,7 +327,7 @@ def _finite(x):
     return x
 
 
-def _print_json(out, files=None, album=None, summary=None):
+def _print_json(out, files=None, album=None, summary=None, **extra):
     files, album = _finite(files), _finite(album)
     d = {}
     if files is not None:
@@ -329,6 +336,7 @@ def _print_json(out, files=None, album=None, summary=None):
         d["album"] = album
     if summary is not None:
         d["summary"] = summary
+    d.update(extra)
     print(json.dumps(d, indent=2), file=out)
 
 
@@ -576,7 +584,11 @@ class Cli:
         the first GPU.  With --rip-log the log's track sections are compared with the files in order.  Exit status 1 when a
         file fails, a log value mismatches, or the number of sections differs from the number of files.  TSV, one row per file
         and no header: `file, status, frames, null samples, CRC32, CRC32 without nulls, ARv1, ARv2` and, with a log, its
-        verdict."""
+        verdict.  With --rip-offsets (rg_rip_offset_signatures) the AccurateRip signatures are also computed at every sample
+        offset within +-2939, and the one offset at which every logged signature is the computed one is looked for
+        (riplog.find_offset).  At offset 0, or without a common offset, the verdicts are those above; at another offset the
+        AccurateRip checks are made there, the CRCs -- which are over other samples -- are not comparable, and the exit status
+        is 0.  Text, TSV (a last row `offset`) and JSON (`offset`) say which offset it was."""
         from . import riplog
 
         o = self.o
@@ -588,8 +600,20 @@ class Cli:
                 self.e(f"error: cannot read {o.rip_log}: {ex.strerror or ex}")
                 return 1
         devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        search = table = None
         with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
-            res = an.rip_checksums(o.files, disc=True)
+            if o.rip_offsets:
+                try:
+                    table = an.rip_offset_signatures(o.files, disc=True)
+                    res = table.tracks
+                    search = riplog.find_offset(sections, table)
+                except rgmod.ReplayGainError as ex:
+                    if ex.code != -10:  # RG_ERR_REFUSED: a file takes no part, or the disc is too large: no search, the files' own outcomes
+                        raise
+                    self.e(f"warning: no offset search: {ex}")
+            if table is None:
+                res = an.rip_checksums(o.files, disc=True)
+        shift = search.offset if search is not None and search.offset else 0
         if self.talk:
             self.p(f"mp3rgain Rip checksums of {len(o.files)} file(s), taken as one disc")
             self.p()
@@ -598,7 +622,8 @@ class Cli:
         for i, (file, r) in enumerate(zip(o.files, res)):
             verdict = None
             if sections is not None and r.error is None:
-                verdict = riplog.compare(sections[i], r) if i < len(sections) else None
+                if i < len(sections):
+                    verdict = riplog.compare_at(sections[i], shift, *table.at(i, shift)) if shift else riplog.compare(sections[i], r)
             bad = r.error is not None or (verdict is not None and not verdict.ok) or (sections is not None and r.error is None and verdict is None)
             failed += bad
             vtext = None if sections is None or r.error is not None else (verdict.text if verdict is not None else "no log section")
@@ -615,6 +640,10 @@ class Cli:
                         d["log"] = vtext
                         if verdict is not None:
                             d["log_checks"] = [{"name": n, "logged": f"{v:08X}", "ok": ok} for n, v, _, ok in verdict.checks]
+                            if shift:
+                                d["offset"] = shift
+                                for c, (_, _, _, ok) in zip(d["log_checks"], verdict.checks):
+                                    c["text"] = verdict.check_text(ok)
                 results.append(d)
             elif o.output_format == "tsv":
                 if r.error is not None:
@@ -635,7 +664,12 @@ class Cli:
         if count_differs:
             self.e(f"error: {o.rip_log} has {len(sections)} track section(s) for {len(o.files)} file(s)")
         if o.output_format == "json":
-            _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+            extra = {"offset": search.offset, "offset_search": search.text} if search is not None else {}
+            _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False), **extra)
+        elif search is not None and o.output_format == "tsv":
+            self.p("offset\t" + ("none" if search.offset is None else str(search.offset)))
+        elif search is not None:
+            self.p(f"log: {search.text}")
         return 1 if failed or count_differs else 0
 
     # ---- find_max_amplitude, src/lib.rs:1174-1199 ------------------------------------------------------------
@@ -1276,6 +1310,8 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "--rip       The files are the tracks of one ripped disc (16-bit stereo WAV or FLAC), in order: CRC-32, CRC-32 without",
         "            null samples and AccurateRip v1 / v2 signatures per track, computed on the GPU",
         "--rip-log <log>  With --rip: compare with the track sections of a ripper's log (EAC, XLD), in order",
+        "--rip-offsets    With --rip --rip-log: AccurateRip signatures at every sample offset within +-2939 on the GPU, and the",
+        "            offset at which the log's signatures match (another pressing, an uncorrected drive read offset)",
         "-v          Show version",
         "-h          Show this help",
     ):

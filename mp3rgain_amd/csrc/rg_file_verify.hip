@@ -193,7 +193,14 @@ extern "C" int rg_mp3_verify(rg_ctx *c, const char *const *paths, size_t n, rg_m
 // one group of the call.  The route is rg_flac_verify's, except that 16-bit stereo WAV streams are kept.  Whatever route put a
 // track's PCM into the arena (device FLAC decoder, the host decoder's planes by copy, the WAV de-interleave), the two kernels
 // of rg_rip_crc.hip read it there, on the stream the decode ran on, so tuning key 14 cannot show in the records.
-static int rip_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const uint32_t *track_flags, rg_rip_result *out) {
+// With `ofs` (rg_rip_offset_signatures: the group is the whole call) the batch is also taken as one disc, when every file is
+// in it: the signatures at every offset of the window, from the same arena on the same stream.
+struct RipOffsets {
+    int32_t radius;
+    uint32_t *arv1, *arv2;
+};
+static int rip_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const uint32_t *track_flags, rg_rip_result *out,
+                     const RipOffsets *ofs = nullptr) {
     out += first;
     if (track_flags) track_flags += first;
     FileGroup g(c, paths, first, n);
@@ -248,7 +255,10 @@ static int rip_group(rg_ctx *c, const char *const *paths, size_t first, size_t n
             const size_t k = rec_of[j];
             rg_rip_fill(sums[j], g.descs[k].frames, g.descs[k].sample_rate, g.counts[k].dropped, &out[g.slot[k]]);
         }
-        return RG_OK;
+        if (!ofs || recs.size() != n) return RG_OK;  // a hole in the disc would shift every later track: no tables then
+        std::vector<RgRipDiscTrack> disc(n + 1);
+        rg_rip_disc(recs.data(), n, disc.data());
+        return rg_rip_offsets_device(c, c->d_arena.p, disc.data(), n, ofs->radius, ofs->arv1, ofs->arv2, c->file_stream());
     };
     g.want_counts = true;
     return g.run(screen, mark, work);
@@ -258,4 +268,34 @@ extern "C" int rg_rip_checksums(rg_ctx *c, const char *const *paths, size_t n, c
     if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
     if (n) memset(out, 0, n * sizeof *out);
     return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return rip_group(c, paths, first, cnt, track_flags, out); });
+}
+
+// ---- rg_rip_offset_signatures ---------------------------------------------------------------------------------------------
+// rg_rip_checksums' route for one disc that lies in the arena at once, and the offsets kernel (rg_rip_offsets.hip) behind it.
+extern "C" int rg_rip_offset_signatures(rg_ctx *c, const char *const *paths, size_t n, const uint32_t *track_flags, int32_t radius, rg_rip_result *out,
+                                        uint32_t *arv1, uint32_t *arv2) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    if (radius < 0 || radius > RG_RIP_OFFSET_MAX) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_rip_offset_signatures: radius %d is outside 0..%d", (int)radius, RG_RIP_OFFSET_MAX);
+    if (n > RG_RIP_DISC_MAX_TRACKS) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_rip_offset_signatures: %zu files, a disc has at most %u tracks", n, RG_RIP_DISC_MAX_TRACKS);
+    const size_t table = n * (2 * (size_t)radius + 1) * sizeof(uint32_t);
+    if (n) memset(out, 0, n * sizeof *out);
+    if (arv1 && table) memset(arv1, 0, table);
+    if (arv2 && table) memset(arv2, 0, table);
+    return no_throw(c, [&]() -> int {
+        c->file_errors.assign(n, std::string());
+        int rc = rg_bind_device(c);
+        if (rc != RG_OK || !n) return rc;
+        std::vector<std::pair<size_t, size_t>> groups;
+        file_groups(c, paths, n, &groups);
+        if (groups.size() != 1)
+            return rg_set_err(c, RG_ERR_REFUSED, "No offset signatures: the %zu files would be decoded in %zu groups, and a disc must lie on the device at once", n,
+                              groups.size());
+        const RipOffsets ofs{radius, arv1, arv2};
+        rc = rip_group(c, paths, 0, n, track_flags, out, &ofs);
+        if (rc != RG_OK) return rc;
+        for (size_t i = 0; i < n; ++i)
+            if (out[i].status != RG_OK)
+                return rg_set_err(c, RG_ERR_REFUSED, "No offset signatures: not every file of the disc took part: %s", c->file_errors[i].c_str());
+        return RG_OK;
+    });
 }

@@ -1,11 +1,14 @@
 // rg_rip.h -- internal: the rip checksums (include/mp3rgain_amd_rip.h) as rg_rip_crc.hip (kernels, launcher, seams),
 // rg_rip_host.cpp (the serial host twin and the kernels' fold arithmetic on the host) and rg_file_verify.hip (rg_rip_checksums)
 // share them.  What one lane hashes, how two neighbours fold and how a track is finished is host and device code, written
-// once here; the kernels and the folded host route differ only in who walks the lanes.
+// once here; the kernels and the folded host route differ only in who walks the lanes.  The signatures at every drive offset
+// (rg_rip_offsets.hip, rg_rip_offset_signatures) share the disc's records, the tile table and the product further down.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include <vector>
 
 #include "../../include/mp3rgain_amd_rip.h"
 #include "rg_crc32.h"
@@ -157,8 +160,63 @@ void rg_rip_fill(const RgRipSums &s, uint64_t frames, uint32_t sample_rate, uint
 int rg_rip_arena_host(int route, size_t n, const rg_track_desc *descs, const uint32_t *track_flags, const void *arena, size_t arena_bytes,
                       rg_rip_result *out, char *err, size_t err_len);
 
+// ---- the signatures at every drive offset (rg_rip_offsets.hip, rg_rip_host.cpp) -------------------------------------------
+#define RG_RIP_OFF_TILE 4096u   // T: frames of a track one block takes
+#define RG_RIP_OFF_BLOCK 256u   // lanes of a block
+#define RG_RIP_OFF_J 23u        // consecutive offsets one lane holds in registers: BLOCK * J = 5888 >= 2 * 2939 + 1
+#define RG_RIP_OFF_SPAN (RG_RIP_OFF_BLOCK * RG_RIP_OFF_J)
+#define RG_RIP_OFF_LDS (RG_RIP_OFF_TILE + RG_RIP_OFF_SPAN)  // disc words of a block: 9984 (39 936 bytes, four blocks a CU)
+
+// One track of a disc.  A launch has n + 1 of them: entry n is the disc's end (base = the disc's length, frames = 0).
+struct RgRipDiscTrack {
+    uint64_t off;     // of plane L from the arena's base, in bytes; plane R follows at off + 2 * frames
+    uint64_t frames;  // N < 2^32
+    uint64_t base;    // B: disc position of the track's first frame
+    int64_t to;       // positions from..to count (1-based, inclusive; empty when to < from)
+    uint32_t from;
+    uint32_t reserved;
+};  // 40 bytes
+// One block's work: frames k0 .. k0 + T - 1 of track `track` (those of them that count)
+struct RgRipOffTile {
+    uint32_t track, k0;
+};
+
+// the track that holds disc position pos (0 <= pos < tr[n].base): the last u with tr[u].base <= pos, which is never empty
+RG_CRC32_HD uint32_t rg_rip_disc_find(const RgRipDiscTrack *tr, uint32_t n, uint64_t pos) {
+    uint32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1) >> 1;
+        if (tr[mid].base <= pos) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+// one product into the two sums, of lo32(p) and of hi32(p): they cannot be one 64-bit sum (its high word would hold lo's carries)
+RG_CRC32_HD void rg_rip_off_product(uint32_t w, uint32_t i, uint32_t *lo, uint32_t *hi) {
+    const uint64_t p = (uint64_t)w * i;
+    *lo += (uint32_t)p;
+    *hi += (uint32_t)(p >> 32);
+}
+
+// rg_rip_host.cpp: the disc of `n` track records (rg_rip_track_record) in call order: out[0 .. n] (n + 1 entries)
+void rg_rip_disc(const RgRipTrack *recs, size_t n, RgRipDiscTrack *out);
+// the blocks of a launch: every tile of every track that holds a frame that counts
+void rg_rip_offsets_plan(const RgRipDiscTrack *tr, size_t n, std::vector<RgRipOffTile> *tiles);
+// W[0 .. tr[n].base) of a disc in host memory
+void rg_rip_disc_words(const unsigned char *arena, const RgRipDiscTrack *tr, size_t n, std::vector<uint32_t> *W);
+// the definition: one track at one offset
+void rg_rip_offsets_cell(const std::vector<uint32_t> &W, const RgRipDiscTrack &t, int32_t o, uint32_t *v1, uint32_t *v2);
+// routes 0 and 2 of rg_rip_offsets_arena, and every route's argument checks (recs: n + 1 entries on RG_OK)
+int rg_rip_offsets_check(int route, size_t n, const rg_track_desc *descs, const uint32_t *track_flags, int32_t radius, const void *arena,
+                         size_t arena_bytes, const uint32_t *arv2, std::vector<RgRipDiscTrack> *recs, char *err, size_t err_len);
+int rg_rip_offsets_host(int route, const std::vector<RgRipDiscTrack> &recs, int32_t radius, const void *arena, uint32_t *arv1, uint32_t *arv2);
+
 #if defined(__HIPCC__)
 struct rg_ctx;
+// the disc tr[0 .. n] in the device arena at `d_arena`: the kernel on `s`, arv1 / arv2 (host, n x (2 radius + 1), either may
+// be null) <- the tables; `s` has been synchronised on return
+int rg_rip_offsets_device(rg_ctx *c, const unsigned char *d_arena, const RgRipDiscTrack *tr, size_t n, int32_t radius, uint32_t *arv1, uint32_t *arv2,
+                          hipStream_t s);
 // `n` records of planes in the device arena at `d_arena` (allocated in whole 16-byte words): the two kernels on `s`,
 // sums[i] <- track i; `s` has been synchronised on return
 int rg_rip_device(rg_ctx *c, const unsigned char *d_arena, RgRipTrack *recs, size_t n, RgRipSums *sums, hipStream_t s);

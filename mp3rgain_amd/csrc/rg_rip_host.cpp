@@ -1,7 +1,8 @@
 // rg_rip_host.cpp -- the host side of the rip checksums (include/mp3rgain_amd_rip.h, rg_rip.h): the track records and their
 // checks, the serial host twin (route 0: the definitions, written plainly), and the kernels' fold arithmetic walked by the
-// host (route 2: the same chunk, combine and finish functions as rg_rip_crc.hip runs, lane by lane).  Plain C++: no device
-// and no context, so a sanitizer build needs nothing else.
+// host (route 2: the same chunk, combine and finish functions as rg_rip_crc.hip runs, lane by lane); and of the signatures at
+// every drive offset: the disc's records, the definition (route 0) and arv1's sliding recurrence (route 2).  Plain C++: no
+// device and no context, so a sanitizer build needs nothing else.
 #include <stdio.h>
 #include <string.h>
 
@@ -172,6 +173,127 @@ int rg_rip_arena_host(int route, size_t n, const rg_track_desc *descs, const uin
     }
     for (size_t i = 0; i < n; ++i)
         rg_rip_fill(route == 0 ? rg_rip_serial_host(base, recs[i]) : rg_rip_folded_host(base, recs[i], P), descs[i].frames, descs[i].sample_rate, 0, &out[i]);
+    return RG_OK;
+}
+
+// ---- the signatures at every drive offset ----------------------------------------------------------------------------------
+void rg_rip_disc(const RgRipTrack *recs, size_t n, RgRipDiscTrack *out) {
+    uint64_t base = 0;
+    for (size_t t = 0; t <= n; ++t) {
+        memset(&out[t], 0, sizeof out[t]);
+        out[t].base = base;
+        if (t == n) break;  // the disc's end
+        out[t].off = recs[t].off;
+        out[t].frames = recs[t].frames;
+        out[t].from = recs[t].from;
+        out[t].to = recs[t].to;
+        base += recs[t].frames;
+    }
+}
+
+void rg_rip_offsets_plan(const RgRipDiscTrack *tr, size_t n, std::vector<RgRipOffTile> *tiles) {
+    tiles->clear();
+    for (size_t t = 0; t < n; ++t) {
+        const int64_t k_lo = tr[t].from > 1u ? (int64_t)tr[t].from - 1 : 0, k_hi = tr[t].to;  // frames [k_lo, k_hi) count
+        for (int64_t k0 = k_lo / RG_RIP_OFF_TILE * RG_RIP_OFF_TILE; k0 < k_hi; k0 += RG_RIP_OFF_TILE)
+            tiles->push_back(RgRipOffTile{(uint32_t)t, (uint32_t)k0});
+    }
+}
+
+void rg_rip_disc_words(const unsigned char *arena, const RgRipDiscTrack *tr, size_t n, std::vector<uint32_t> *W) {
+    W->resize((size_t)tr[n].base);
+    for (size_t t = 0; t < n; ++t) {
+        const unsigned char *L = arena + tr[t].off, *R = L + 2 * tr[t].frames;
+        for (uint64_t k = 0; k < tr[t].frames; ++k) (*W)[(size_t)(tr[t].base + k)] = sample_at(L, k) | (sample_at(R, k) << 16);
+    }
+}
+
+// ---- route 0: the definition -----------------------------------------------------------------------------------------------
+void rg_rip_offsets_cell(const std::vector<uint32_t> &W, const RgRipDiscTrack &t, int32_t o, uint32_t *v1, uint32_t *v2) {
+    const int64_t total = (int64_t)W.size();
+    uint32_t lo = 0, hi = 0;
+    for (int64_t i = t.from > 1u ? t.from : 1; i <= t.to; ++i) {  // positions are 1-based
+        const int64_t j = (int64_t)t.base + i - 1 + o;
+        const uint32_t w = j >= 0 && j < total ? W[(size_t)j] : 0u;
+        rg_rip_off_product(w, (uint32_t)i, &lo, &hi);
+    }
+    *v1 = lo;
+    *v2 = lo + hi;
+}
+
+// ---- route 2: arv1 by the sliding recurrence ----------------------------------------------------------------------------------
+static void offsets_sliding(const std::vector<uint32_t> &W, const RgRipDiscTrack &t, int32_t radius, uint32_t *v1) {
+    const int64_t total = (int64_t)W.size(), f = t.from > 1u ? t.from : 1, T = t.to, c = (int64_t)t.base - 1;
+    const auto w = [&](int64_t j) -> uint32_t { return j >= 0 && j < total ? W[(size_t)j] : 0u; };
+    if (T < f) {
+        for (int32_t o = -radius; o <= radius; ++o) v1[o + radius] = 0;
+        return;
+    }
+    uint32_t A = 0, S = 0;  // A(-radius) and S(-radius) = sum of W[c + i - radius] over i = f + 1 .. T + 1, both mod 2^32
+    for (int64_t i = f; i <= T; ++i) A += w(c + i - radius) * (uint32_t)i;
+    for (int64_t i = f + 1; i <= T + 1; ++i) S += w(c + i - radius);
+    for (int32_t o = -radius;; ++o) {
+        v1[o + radius] = A;
+        if (o == radius) break;
+        A = A - (uint32_t)f * w(c + f + o) + (uint32_t)(T + 1) * w(c + T + 1 + o) - S;
+        S = S - w(c + f + 1 + o) + w(c + T + 2 + o);
+    }
+}
+
+int rg_rip_offsets_check(int route, size_t n, const rg_track_desc *descs, const uint32_t *track_flags, int32_t radius, const void *arena,
+                         size_t arena_bytes, const uint32_t *arv2, std::vector<RgRipDiscTrack> *recs, char *err, size_t err_len) {
+    if (route < 0 || route > 2) {
+        snprintf(err, err_len, "rg_rip_offsets_arena: route %d (0 = the definition, 1 = kernel, 2 = arv1 by the sliding recurrence)", route);
+        return RG_ERR_INVALID_ARG;
+    }
+    if (route == 2 && arv2) {
+        snprintf(err, err_len, "rg_rip_offsets_arena: route 2 computes arv1 only");
+        return RG_ERR_INVALID_ARG;
+    }
+    if (radius < 0 || radius > RG_RIP_OFFSET_MAX) {
+        snprintf(err, err_len, "rg_rip_offsets_arena: radius %d is outside 0..%d", (int)radius, RG_RIP_OFFSET_MAX);
+        return RG_ERR_INVALID_ARG;
+    }
+    if (n > RG_RIP_DISC_MAX_TRACKS) {
+        snprintf(err, err_len, "rg_rip_offsets_arena: %zu tracks, a disc has at most %u", n, RG_RIP_DISC_MAX_TRACKS);
+        return RG_ERR_INVALID_ARG;
+    }
+    if (n && (!descs || (arena_bytes && !arena))) {
+        snprintf(err, err_len, "rg_rip_offsets_arena: null array");
+        return RG_ERR_INVALID_ARG;
+    }
+    std::vector<RgRipTrack> tracks(n ? n : 1);
+    for (size_t i = 0; i < n; ++i) {
+        const int rc = rg_rip_track_record(i, descs[i], track_flags ? track_flags[i] : 0u, arena_bytes, &tracks[i], err, err_len);
+        if (rc != RG_OK) return rc;
+    }
+    recs->resize(n + 1);
+    rg_rip_disc(tracks.data(), n, recs->data());
+    return RG_OK;
+}
+
+int rg_rip_offsets_host(int route, const std::vector<RgRipDiscTrack> &recs, int32_t radius, const void *arena, uint32_t *arv1, uint32_t *arv2) {
+    const size_t n = recs.size() - 1, n_off = 2 * (size_t)radius + 1;
+    std::vector<uint32_t> W;
+    rg_rip_disc_words(static_cast<const unsigned char *>(arena), recs.data(), n, &W);
+    for (size_t t = 0; t < n; ++t) {
+        if (route == 2) {
+            if (arv1) offsets_sliding(W, recs[t], radius, arv1 + t * n_off);
+            continue;
+        }
+        for (int32_t o = -radius; o <= radius; ++o) {
+            uint32_t v1, v2;
+            rg_rip_offsets_cell(W, recs[t], o, &v1, &v2);
+            if (arv1) arv1[t * n_off + (size_t)(o + radius)] = v1;
+            if (arv2) arv2[t * n_off + (size_t)(o + radius)] = v2;
+        }
+    }
+    return RG_OK;
+}
+
+extern "C" int rg_rip_offsets_kernel_shape(uint32_t *tile_frames, uint32_t *block_lanes) {
+    if (tile_frames) *tile_frames = RG_RIP_OFF_TILE;
+    if (block_lanes) *block_lanes = RG_RIP_OFF_BLOCK;
     return RG_OK;
 }
 

@@ -176,6 +176,30 @@ def rip_kernel_shape():
     return c.value, t.value, f.value
 
 
+def rip_offsets_arena(ctx, route: int, descs, flags, radius: int, arena, want=(True, True)):
+    """rg_rip_offsets_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> (arv1, arv2), uint32
+    arrays [n, 2 radius + 1] indexed [t][o + radius]; `want` says which of the two are computed (the other is None)."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    fl = None if flags is None else (C.c_uint32 * max(1, n))(*[int(f) for f in flags])
+    width = 2 * max(0, min(int(radius), _capi.RIP_OFFSET_MAX)) + 1
+    tabs = [np.zeros((n, width), dtype=np.uint32) if w else None for w in want]
+    ptr = [t.ctypes.data_as(C.POINTER(C.c_uint32)) if t is not None else None for t in tabs]
+    rc = L.rg_rip_offsets_arena(ctx, int(route), n, d, fl, int(radius), arena.ctypes.data if arena.size else None, arena.size, ptr[0], ptr[1])
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return tabs[0], tabs[1]
+
+
+def rip_offsets_kernel_shape():
+    """rg_rip_offsets_kernel_shape -> (tile_frames, block_lanes)."""
+    t, b = C.c_uint32(), C.c_uint32()
+    _capi.load().rg_rip_offsets_kernel_shape(C.byref(t), C.byref(b))
+    return t.value, b.value
+
+
 @dataclass
 class FlacVerifyResult:
     """One file of Analyzer.verify_flac (rg_flac_verify_result): the decoded PCM's MD5 against STREAMINFO's signature."""
@@ -213,6 +237,19 @@ class RipChecksums:
     first_track: bool = False  # what the call was told about the file's place on its disc
     last_track: bool = False
     error: Optional["ReplayGainError"] = None  # why there are no checksums; every other field is then zero
+
+
+@dataclass
+class RipOffsetSignatures:
+    """Analyzer.rip_offset_signatures (rg_rip_offset_signatures): a disc's AccurateRip signatures at every drive offset."""
+    tracks: list             # [RipChecksums], what rip_checksums gives for the same files and flags
+    radius: int
+    arv1: np.ndarray         # uint32 [n, 2 radius + 1]: track t at offset o is [t][o + radius]
+    arv2: np.ndarray
+
+    def at(self, track: int, offset: int):
+        """(arv1, arv2) of track `track` read `offset` frames later on the disc."""
+        return int(self.arv1[track][offset + self.radius]), int(self.arv2[track][offset + self.radius])
 
 
 @dataclass
@@ -831,14 +868,7 @@ class Analyzer:
         self._check(self._lib.rg_rip_checksums(self._ctx, paths, n, (C.c_uint32 * max(1, n))(*fl), out))
         return out, fl
 
-    def rip_checksums(self, files, disc: bool = True, flags=None) -> list:
-        """rg_rip_checksums: `files` (16-bit stereo WAV or FLAC) decoded by the route the analysis uses and, from the PCM where
-        it lies on this GPU, per file the CRC-32, the CRC-32 without null samples and the AccurateRip v1 / v2 signatures ->
-        [RipChecksums].  disc=True takes the files as the tracks of one disc, in order: the first is flagged first, the last
-        last (`flags`: RIP_FIRST_TRACK / RIP_LAST_TRACK per file instead).  A file that takes no part carries its
-        ReplayGainError in `.error`."""
-        n = len(files)
-        out, fl = self._rip_call(files, disc, flags)
+    def _rip_results(self, out, fl, n):
         res = []
         for i in range(n):
             r = out[i]
@@ -851,10 +881,56 @@ class Analyzer:
                                     bool(fl[i] & _capi.RIP_FIRST_TRACK), bool(fl[i] & _capi.RIP_LAST_TRACK), err))
         return res
 
+    def rip_checksums(self, files, disc: bool = True, flags=None) -> list:
+        """rg_rip_checksums: `files` (16-bit stereo WAV or FLAC) decoded by the route the analysis uses and, from the PCM where
+        it lies on this GPU, per file the CRC-32, the CRC-32 without null samples and the AccurateRip v1 / v2 signatures ->
+        [RipChecksums].  disc=True takes the files as the tracks of one disc, in order: the first is flagged first, the last
+        last (`flags`: RIP_FIRST_TRACK / RIP_LAST_TRACK per file instead).  A file that takes no part carries its
+        ReplayGainError in `.error`."""
+        out, fl = self._rip_call(files, disc, flags)
+        return self._rip_results(out, fl, len(files))
+
     def rip_checksums_raw(self, files, disc: bool = True, flags=None) -> bytes:
         """rip_checksums' rg_rip_result array as the C call left it (tests compare routes byte for byte)."""
         out, _ = self._rip_call(files, disc, flags)
         return bytes(out)[:len(files) * C.sizeof(_capi.RipRecord)]
+
+    def _rip_offsets_call(self, files, disc, flags, radius):
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        fl = self._rip_flags(n, disc, flags)
+        out = (_capi.RipRecord * max(1, n))()
+        width = 2 * max(0, min(int(radius), _capi.RIP_OFFSET_MAX)) + 1
+        v1, v2 = np.full((n, width), 0xA5A5A5A5, dtype=np.uint32), np.full((n, width), 0xA5A5A5A5, dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        rc = self._lib.rg_rip_offset_signatures(self._ctx, paths, n, (C.c_uint32 * max(1, n))(*fl), int(radius), out, v1.ctypes.data_as(u32p),
+                                                v2.ctypes.data_as(u32p))
+        return rc, out, v1, v2, fl
+
+    def rip_offset_signatures_raw(self, files, disc: bool = True, flags=None, radius: int = _capi.RIP_OFFSET_MAX):
+        """rg_rip_offset_signatures as the C call left its arrays -> (status, records' bytes, arv1, arv2): nothing is raised,
+        so that a refused call's records and tables can be looked at."""
+        rc, out, v1, v2, _ = self._rip_offsets_call(files, disc, flags, radius)
+        return rc, bytes(out)[:len(files) * C.sizeof(_capi.RipRecord)], v1, v2
+
+    def rip_offset_signatures(self, files, disc: bool = True, flags=None, radius: int = _capi.RIP_OFFSET_MAX) -> RipOffsetSignatures:
+        """rg_rip_offset_signatures: the files are the tracks of one disc, in order (`disc`, `flags`: as rip_checksums); per
+        track the AccurateRip v1 / v2 signatures at every sample offset -radius .. radius, computed on this GPU from the one
+        decode that also gives `.tracks`, the rip_checksums results -> RipOffsetSignatures.  Raises ReplayGainError
+        (RG_ERR_REFUSED) when a file takes no part or the disc does not fit the device at once."""
+        rc, out, v1, v2, fl = self._rip_offsets_call(files, disc, flags, radius)
+        self._check(rc)
+        return RipOffsetSignatures(self._rip_results(out, fl, len(files)), int(radius), v1, v2)
+
+    def rip_offsets_arena(self, route: int, descs, flags, radius: int, arena, want=(True, True)):
+        """rg_rip_offsets_arena, the seam of the offsets kernel: the disc `descs` describe in the host arena `arena` ->
+        (arv1, arv2) [n, 2 radius + 1]; route 0 = the definition on the host, route 1 = the arena copied to this GPU and the
+        kernel, route 2 = arv1 by the sliding recurrence on the host (want=(True, False))."""
+        return rip_offsets_arena(self._ctx, route, descs, flags, radius, arena, want)
+
+    @staticmethod
+    def rip_offsets_kernel_shape():
+        return rip_offsets_kernel_shape()
 
     def rip_checksums_arena(self, route: int, descs, flags, arena):
         """rg_rip_checksums_arena, the seam of the rip checksum kernels: the tracks `descs` describe in the host arena `arena`

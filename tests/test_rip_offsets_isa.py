@@ -1,0 +1,26 @@
+"""The offsets kernel (mp3rgain_amd/csrc/rg_rip_offsets.hip) keeps a lane's window of disc words and its two accumulators per
+offset in registers: compiled for gfx950 here (hipcc cross-compiles without a GPU), every kernel descriptor of the file shows
+no private segment and no dynamic stack."""
+import re
+import shutil
+import subprocess
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+def test_rip_offsets_kernels_use_no_scratch(tmp_path):
+    if not Path(HIPCC).exists():
+        pytest.skip("no hipcc")
+    out = tmp_path / "rg_rip_offsets.s"
+    subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
+                    str(ROOT / "mp3rgain_amd" / "csrc" / "rg_rip_offsets.hip"), "-o", str(out)], check=True, capture_output=True, timeout=600)
+    kernels = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", out.read_text(), re.S)
+    assert any("rg_rip_offsets_kernel" in k for k, _ in kernels) and any("rg_rip_offsets_fill_kernel" in k for k, _ in kernels)
+    for name, body in kernels:
+        m = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body)
+        assert m and int(m.group(1)) == 0, name
+        assert re.search(r"\.amdhsa_uses_dynamic_stack 0", body), name
