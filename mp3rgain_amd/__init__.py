@@ -14,8 +14,10 @@ from .replaygain import (  # noqa: F401
     AlbumGainResult,
     Analyzer,
     AudioFileType,
+    ChannelStats,
     FlacVerifyResult,
     Node,
+    PcmStats,
     PcmTrack,
     PeakAmplitudeResult,
     R128AlbumResult,
@@ -29,6 +31,8 @@ from .replaygain import (  # noqa: F401
     analyze_track,
     find_peak_amplitude,
     is_available,
+    pcm_stats_arena,
+    pcm_stats_kernel_shape,
     r128_layout_weights,
     rip_offsets_arena,
     rip_offsets_kernel_shape,

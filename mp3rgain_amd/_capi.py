@@ -277,6 +277,59 @@ RIP_SYMBOLS = [
     ("rg_rip_offsets_rate", _int, [_vp, _sz, _u64, C.c_int32, _u32, _u32, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_u64), _P(_u64), _P(_sz)]),
 ]
 
+# include/mp3rgain_amd_stats.h (PCM defect scan: clipping runs, dropouts, DC, padded bits)
+STATS_CLIPPED, STATS_DROPOUT, STATS_PADDED, STATS_NONFINITE, STATS_SILENT, STATS_COMPLETE = 1, 2, 4, 8, 16, 32
+STATS_MAX_CHANNELS, STATS_MIN_CLIP_RUN, STATS_MIN_ZERO_RUN = 8, 3, 64
+
+
+class PcmStatsOpts(C.Structure):  # rg_pcm_stats_opts
+    _fields_ = [("min_clip_run", C.c_uint32), ("min_zero_run", C.c_uint32)]
+
+
+class PcmStatsChannel(C.Structure):  # rg_pcm_stats_channel
+    _fields_ = [
+        ("min", C.c_double),
+        ("max", C.c_double),
+        ("sum", C.c_int64),
+        ("or_mask", C.c_uint32),
+        ("effective_bits", C.c_uint32),
+        ("clipped", C.c_uint32),
+        ("clip_runs", C.c_uint32),
+        ("longest_clip_run", C.c_uint32),
+        ("first_clip_run", C.c_uint32),
+        ("zeros", C.c_uint32),
+        ("lead_zeros", C.c_uint32),
+        ("trail_zeros", C.c_uint32),
+        ("zero_runs", C.c_uint32),
+        ("longest_zero_run", C.c_uint32),
+        ("nonfinite", C.c_uint32),
+    ]
+
+
+class PcmStatsRecord(C.Structure):  # rg_pcm_stats_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("bits", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("lead_silence_frames", C.c_uint32),
+        ("trail_silence_frames", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("ch", PcmStatsChannel * STATS_MAX_CHANNELS),
+    ]
+
+
+STATS_SYMBOLS = [
+    ("rg_pcm_stats", _int, [_vp, _P(C.c_char_p), _sz, _P(PcmStatsOpts), _P(PcmStatsRecord)]),
+    ("rg_pcm_stats_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _P(_u32), _P(PcmStatsOpts), _vp, _sz, _P(PcmStatsRecord)]),
+    ("rg_pcm_stats_kernel_shape", _int, [_P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_pcm_stats_rate", _int, [_vp, _sz, _u64, _u32, _int, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz)]),
+]
+
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions
 NODE_OPEN = C.CFUNCTYPE(_vp, _int, _vp)
 NODE_CLOSE = C.CFUNCTYPE(None, _vp, _vp)
@@ -317,7 +370,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

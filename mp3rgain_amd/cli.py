@@ -68,6 +68,9 @@ class Options:  # src/main.rs:65-96
     rip: bool = False        # this façade only (--rip): the files are the tracks of one disc; CRC-32 and AccurateRip checksums
     rip_log: Optional[str] = None  # with --rip (--rip-log LOG): a ripper's log to compare the checksums with
     rip_offsets: bool = False  # with --rip --rip-log (--rip-offsets): look for the log's drive offset within +-2939 samples
+    stats: bool = False      # this façade only (--stats): clipping runs, dropouts, DC offset, padded bits, edge silence per file
+    clip_run: Optional[int] = None  # with --stats (--clip-run N): full-scale samples in a row that count as a clip run
+    zero_run: Optional[int] = None  # with --stats (--zero-run N): zero samples in a row inside the audio that count as a dropout
     files: List[Path] = field(default_factory=list)
 
 
@@ -137,6 +140,12 @@ def parse_args(args: List[str], out, err) -> Options:
             o.rip_offsets = True
         elif arg == "--rip-log":
             o.rip_log = need("--rip-log", "--rip-log requires an argument")
+        elif arg == "--stats":  # not in the reference: a command of its own, like --verify and --rip
+            o.stats = True
+        elif arg == "--clip-run":
+            o.clip_run = _parse_int(need("--clip-run", "--clip-run requires an argument"), "invalid run length", 32, signed=False)
+        elif arg == "--zero-run":
+            o.zero_run = _parse_int(need("--zero-run", "--zero-run requires an argument"), "invalid run length", 32, signed=False)
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -237,6 +246,12 @@ def parse_args(args: List[str], out, err) -> Options:
         raise CliError("--rip-offsets requires --rip")
     if o.rip_offsets and o.rip_log is None:
         raise CliError("--rip-offsets requires --rip-log")
+    if o.clip_run is not None and not o.stats:
+        raise CliError("--clip-run requires --stats")
+    if o.zero_run is not None and not o.stats:
+        raise CliError("--zero-run requires --stats")
+    if o.clip_run == 0 or o.zero_run == 0:
+        raise CliError("--clip-run and --zero-run take a length of at least 1")
     return o
 
 
@@ -468,6 +483,8 @@ class Cli:
             return self.cmd_verify()
         if o.rip:
             return self.cmd_rip()
+        if o.stats:
+            return self.cmd_stats()
         if o.max_amplitude_only:
             return self.cmd_max_amplitude()
         if o.stored_tag_mode == "delete":
@@ -671,6 +688,74 @@ class Cli:
         elif search is not None:
             self.p(f"log: {search.text}")
         return 1 if failed or count_differs else 0
+
+    # ---- --stats (not in the reference): what is wrong with the audio itself, on the GPU ------------------------------
+    @staticmethod
+    def _clock(sample: int, rate: int) -> str:
+        """A sample position as m:ss.mmm."""
+        ms = sample * 1000 // rate if rate else 0
+        return f"{ms // 60000}:{ms // 1000 % 60:02d}.{ms % 1000:03d}"
+
+    def cmd_stats(self) -> int:
+        """Every file decoded by the route the analysis uses and scanned on the first GPU (rg_pcm_stats): per channel the peak,
+        the DC offset, clipped samples and clip runs, the bits in use, dropouts, and per file the digital silence at its edges.
+        The findings are a report: exit status 1 only when a file fails or has dropped frames.  TSV, no header: a row per file
+        `file, verdicts, frames, sample rate, channels, bits, effective bits, lead silence, trail silence, dropped frames` and a
+        row per channel `file, "ch", index, peak, DC offset, clipped, clip runs, longest clip run, first clip run, zeros, dropouts,
+        longest dropout`, told apart by the word in the second field (a failing file: `file, error text`)."""
+        o = self.o
+        clip_run = 3 if o.clip_run is None else o.clip_run
+        zero_run = 64 if o.zero_run is None else o.zero_run
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            res = an.pcm_stats(o.files, clip_run, zero_run)
+        if self.talk:
+            self.p(f"mp3rgain PCM stats of {len(o.files)} file(s): clip runs from {clip_run} samples, dropouts from {zero_run}")
+            self.p()
+        results, failed = [], 0
+        for file, r in zip(o.files, res):
+            bad = r.error is not None or not r.complete
+            failed += bad
+            words = r.verdicts
+            if o.output_format == "json":
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                else:
+                    d.update(verdicts=words, frames=r.frames, sample_rate=r.sample_rate, bits=r.bits, effective_bits=r.effective_bits,
+                             float=r.bits == 0, lead_silence_frames=r.lead_silence_frames, trail_silence_frames=r.trail_silence_frames,
+                             dropped_frames=r.dropped_frames, clipped=r.clipped, dropout=r.dropout, padded=r.padded, nonfinite=r.nonfinite,
+                             silent=r.silent, complete=r.complete,
+                             channels=[{"peak": c.peak, "min": c.min, "max": c.max, "dc_offset": c.dc_offset, "sum": c.sum, "or_mask": f"{c.or_mask:08X}",
+                                        "effective_bits": c.effective_bits, "clipped": c.clipped, "clip_runs": c.clip_runs,
+                                        "longest_clip_run": c.longest_clip_run,
+                                        "first_clip_run": c.first_clip_run if c.clip_runs else None, "zeros": c.zeros, "lead_zeros": c.lead_zeros,
+                                        "trail_zeros": c.trail_zeros, "zero_runs": c.zero_runs, "longest_zero_run": c.longest_zero_run,
+                                        "nonfinite": c.nonfinite} for c in r.channels])
+                results.append(d)
+            elif o.output_format == "tsv":
+                if r.error is not None:
+                    self.p(f"{_name(file)}\t{r.error}")
+                    continue
+                self.p(f"{_name(file)}\t{','.join(words)}\t{r.frames}\t{r.sample_rate}\t{len(r.channels)}\t{r.bits}\t{r.effective_bits}\t"
+                       f"{r.lead_silence_frames}\t{r.trail_silence_frames}\t{r.dropped_frames}")
+                for k, c in enumerate(r.channels):
+                    self.p(f"{_name(file)}\tch\t{k}\t{c.peak:.6f}\t{c.dc_offset:+.6f}\t{c.clipped}\t{c.clip_runs}\t{c.longest_clip_run}\t"
+                           f"{c.first_clip_run if c.clip_runs else ''}\t{c.zeros}\t{c.zero_runs}\t{c.longest_zero_run}")
+            elif r.error is not None:
+                self.e(f"{_name(file)} - {r.error}")
+            elif bad or not o.quiet:
+                width = "float" if r.bits == 0 else f"{r.effective_bits} of {r.bits} bits"
+                self.p(f"{_name(file)} - {', '.join(words)}  [{width}, silence {r.lead_silence_frames} + {r.trail_silence_frames} frames"
+                       + (f", {r.dropped_frames} frames dropped" if r.dropped_frames else "") + "]")
+                for k, c in enumerate(r.channels):
+                    first = f" first at {self._clock(c.first_clip_run, r.sample_rate)}" if c.clip_runs else ""
+                    self.p(f"    ch {k}: peak {c.peak:.6f}  DC {c.dc_offset:+.6f}  clipped {c.clipped} in {c.clip_runs} run(s){first}"
+                           f"  dropouts {c.zero_runs}" + (f" (longest {c.longest_zero_run})" if c.zero_runs else "")
+                           + (f"  non-finite {c.nonfinite}" if c.nonfinite else ""))
+        if o.output_format == "json":
+            _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+        return 1 if failed else 0
 
     # ---- find_max_amplitude, src/lib.rs:1174-1199 ------------------------------------------------------------
     def find_max_amplitude(self, file: Path):
@@ -1312,6 +1397,11 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "--rip-log <log>  With --rip: compare with the track sections of a ripper's log (EAC, XLD), in order",
         "--rip-offsets    With --rip --rip-log: AccurateRip signatures at every sample offset within +-2939 on the GPU, and the",
         "            offset at which the log's signatures match (another pressing, an uncorrected drive read offset)",
+        "--stats     PCM defect scan on the GPU (WAV, FLAC, MP3): per channel peak, DC offset, clipped samples and clip runs, bits",
+        "            in use, dropouts (zero runs inside the audio); per file the digital silence at its edges.  A report: exit",
+        "            status 1 only for a file that fails or has dropped frames",
+        "--clip-run <n>   With --stats: full-scale samples in a row that count as a clip run (default 3)",
+        "--zero-run <n>   With --stats: zero samples in a row inside the audio that count as a dropout (default 64)",
         "-v          Show version",
         "-h          Show this help",
     ):

@@ -220,4 +220,7 @@ int rg_rip_offsets_device(rg_ctx *c, const unsigned char *d_arena, const RgRipDi
 // `n` records of planes in the device arena at `d_arena` (allocated in whole 16-byte words): the two kernels on `s`,
 // sums[i] <- track i; `s` has been synchronised on return
 int rg_rip_device(rg_ctx *c, const unsigned char *d_arena, RgRipTrack *recs, size_t n, RgRipSums *sums, hipStream_t s);
+// rg_pcm_stats_rate's yardstick, the same two kernels without their copies: with `upload` the `n` planned records (rg_rip_plan:
+// `n_tiles`) go to the device on `s` and nothing is launched; without it the two kernels are enqueued over what was uploaded
+int rg_rip_kernels(rg_ctx *c, const unsigned char *d_arena, const RgRipTrack *recs, size_t n, uint64_t n_tiles, bool upload, hipStream_t s);
 #endif

@@ -177,6 +177,16 @@ int rg_rip_device(rg_ctx *c, const unsigned char *d_arena, RgRipTrack *recs, siz
     return RG_OK;
 }
 
+int rg_rip_kernels(rg_ctx *c, const unsigned char *d_arena, const RgRipTrack *recs, size_t n, uint64_t n_tiles, bool upload, hipStream_t s) {
+    const RipLayout l = rip_layout(n, n_tiles);
+    if (upload) {
+        RG_HIP(c, c->d_rip.reserve(l.end));
+        RG_HIP(c, hipMemcpyAsync(c->d_rip.p, recs, n * sizeof(RgRipTrack), hipMemcpyHostToDevice, s));
+        return RG_OK;
+    }
+    return rip_launch(c, d_arena, c->d_rip.p, l, n, n_tiles, RG_RIP_TABLE_LAYOUT, s);
+}
+
 // ---- test seam (include/mp3rgain_amd_rip.h) ---------------------------------------------------------------------------------
 extern "C" int rg_rip_checksums_arena(void *ctx, int route, size_t n, const rg_track_desc *descs, const uint32_t *track_flags, const void *arena,
                                       size_t arena_bytes, rg_rip_result *out) {

@@ -200,6 +200,140 @@ def rip_offsets_kernel_shape():
     return t.value, b.value
 
 
+def _stats_opts(min_clip_run, min_zero_run):
+    """rg_pcm_stats_opts, or NULL (the header's defaults) when both are None."""
+    if min_clip_run is None and min_zero_run is None:
+        return None
+    return C.byref(_capi.PcmStatsOpts(_capi.STATS_MIN_CLIP_RUN if min_clip_run is None else int(min_clip_run),
+                                      _capi.STATS_MIN_ZERO_RUN if min_zero_run is None else int(min_zero_run)))
+
+
+def pcm_stats_arena(ctx, route: int, descs, bits, arena, min_clip_run=None, min_zero_run=None):
+    """rg_pcm_stats_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> [PcmStatsRecord].  `bits`:
+    one entry per track, or None (the container's width everywhere); both run lengths None = the header's defaults."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    b = None if bits is None else (C.c_uint32 * max(1, n))(*[int(x) for x in bits])
+    out = (_capi.PcmStatsRecord * max(1, n))()
+    rc = L.rg_pcm_stats_arena(ctx, int(route), n, d, b, _stats_opts(min_clip_run, min_zero_run), arena.ctypes.data if arena.size else None,
+                              arena.size, out)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return list(out[:n])
+
+
+def pcm_stats_kernel_shape():
+    """rg_pcm_stats_kernel_shape -> (chunk_samples, tile_samples, fold_lanes)."""
+    c, t, f = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _capi.load().rg_pcm_stats_kernel_shape(C.byref(c), C.byref(t), C.byref(f))
+    return c.value, t.value, f.value
+
+
+@dataclass
+class ChannelStats:
+    """One channel of a PcmStats (rg_pcm_stats_channel, include/mp3rgain_amd_stats.h)."""
+    min: float               # over the stored values (the finite ones for float)
+    max: float
+    sum: int                 # of the stored values; float: of llrint(clamp(x, -256, 256) * 2^23)
+    or_mask: int
+    effective_bits: int
+    clipped: int             # samples at full scale
+    clip_runs: int           # stretches of at least min_clip_run of them
+    longest_clip_run: int
+    first_clip_run: int      # first sample of the first counted stretch; `frames` when there is none
+    zeros: int
+    lead_zeros: int
+    trail_zeros: int
+    zero_runs: int           # zero stretches of at least min_zero_run that touch neither end
+    longest_zero_run: int
+    nonfinite: int
+    frames: int = 0
+    full_scale: float = 1.0  # 2^(W-1) for the integer formats, 1.0 for float: what min and max are relative to
+    sum_scale: float = 1.0   # 2^(W-1) for the integer formats, 2^23 for float
+
+    @property
+    def dc_offset(self) -> float:
+        """The mean sample value relative to full scale."""
+        return self.sum / self.frames / self.sum_scale if self.frames else 0.0
+
+    @property
+    def peak(self) -> float:
+        """max(|min|, |max|) relative to full scale."""
+        return max(abs(self.min), abs(self.max)) / self.full_scale
+
+
+@dataclass
+class PcmStats:
+    """One file of Analyzer.pcm_stats (rg_pcm_stats_result): what is wrong with the audio itself."""
+    frames: int
+    sample_rate: int
+    format: int              # rg_sample_format of the planes that were scanned
+    bits: int                # 0 for float
+    dropped_frames: int
+    lead_silence_frames: int
+    trail_silence_frames: int
+    flags: int
+    channels: list           # [ChannelStats]
+    error: Optional["ReplayGainError"] = None  # why there are no numbers; every other field is then zero
+
+    @property
+    def clipped(self) -> bool:
+        return bool(self.flags & _capi.STATS_CLIPPED)
+
+    @property
+    def dropout(self) -> bool:
+        return bool(self.flags & _capi.STATS_DROPOUT)
+
+    @property
+    def padded(self) -> bool:
+        return bool(self.flags & _capi.STATS_PADDED)
+
+    @property
+    def nonfinite(self) -> bool:
+        return bool(self.flags & _capi.STATS_NONFINITE)
+
+    @property
+    def silent(self) -> bool:
+        return bool(self.flags & _capi.STATS_SILENT)
+
+    @property
+    def complete(self) -> bool:
+        return bool(self.flags & _capi.STATS_COMPLETE)
+
+    @property
+    def effective_bits(self) -> int:
+        return max((c.effective_bits for c in self.channels), default=0)
+
+    @property
+    def dc_offset(self) -> float:
+        """The largest DC offset of the channels, by magnitude."""
+        return max((c.dc_offset for c in self.channels), key=abs, default=0.0)
+
+    @property
+    def verdicts(self) -> list:
+        """The flags as words, in a fixed order; ["ok"] when there is nothing to report."""
+        names = (("clipped", self.clipped), ("dropout", self.dropout), ("padded", self.padded), ("nonfinite", self.nonfinite),
+                 ("silent", self.silent), ("incomplete", self.error is None and not self.complete))
+        return [n for n, on in names if on] or ["ok"]
+
+
+def pcm_stats_from_record(r, error=None) -> PcmStats:
+    """A PcmStats from an rg_pcm_stats_result."""
+    w = 16 if r.format == _capi.FMT_S16_PLANAR else 32
+    is_float = r.format == _capi.FMT_F32_PLANAR
+    full, scale = (1.0, float(1 << 23)) if is_float else (float(1 << (w - 1)),) * 2
+    ch = []
+    for k in range(int(r.channels)):
+        c = r.ch[k]
+        ch.append(ChannelStats(float(c.min), float(c.max), int(c.sum), int(c.or_mask), int(c.effective_bits), int(c.clipped), int(c.clip_runs),
+                               int(c.longest_clip_run), int(c.first_clip_run), int(c.zeros), int(c.lead_zeros), int(c.trail_zeros),
+                               int(c.zero_runs), int(c.longest_zero_run), int(c.nonfinite), int(r.frames), full, scale))
+    return PcmStats(int(r.frames), int(r.sample_rate), int(r.format), int(r.bits), int(r.dropped_frames), int(r.lead_silence_frames),
+                    int(r.trail_silence_frames), int(r.flags), ch, error)
+
+
 @dataclass
 class FlacVerifyResult:
     """One file of Analyzer.verify_flac (rg_flac_verify_result): the decoded PCM's MD5 against STREAMINFO's signature."""
@@ -937,6 +1071,42 @@ class Analyzer:
         -> [RipRecord]; route 0 = the serial host twin, route 1 = the arena copied to this GPU and the kernels, route 2 = the
         kernels' fold arithmetic on the host."""
         return rip_checksums_arena(self._ctx, route, descs, flags, arena)
+
+    def _pcm_stats_call(self, files, min_clip_run, min_zero_run):
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (_capi.PcmStatsRecord * max(1, n))()
+        self._check(self._lib.rg_pcm_stats(self._ctx, paths, n, _stats_opts(min_clip_run, min_zero_run), out))
+        return out
+
+    def pcm_stats(self, files, min_clip_run: int = _capi.STATS_MIN_CLIP_RUN, min_zero_run: int = _capi.STATS_MIN_ZERO_RUN) -> list:
+        """rg_pcm_stats: `files` (WAV, FLAC or MPEG Layer III) decoded by the route the analysis uses and, from the PCM where it
+        lies on this GPU, per channel the clipped samples and clip runs, the zero runs inside the audio and at its edges, the DC
+        sum, the bits in use, minimum and maximum -> [PcmStats].  A file that takes no part carries its ReplayGainError in
+        `.error`."""
+        out = self._pcm_stats_call(files, min_clip_run, min_zero_run)
+        res = []
+        for i in range(len(files)):
+            err = None
+            if out[i].status != 0:
+                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
+            res.append(pcm_stats_from_record(out[i], err))
+        return res
+
+    def pcm_stats_raw(self, files, min_clip_run=None, min_zero_run=None) -> bytes:
+        """pcm_stats' rg_pcm_stats_result array as the C call left it (tests compare routes byte for byte)."""
+        out = self._pcm_stats_call(files, min_clip_run, min_zero_run)
+        return bytes(out)[:len(files) * C.sizeof(_capi.PcmStatsRecord)]
+
+    def pcm_stats_arena(self, route: int, descs, bits, arena, min_clip_run=None, min_zero_run=None):
+        """rg_pcm_stats_arena, the seam of the stats kernels: the tracks `descs` describe in the host arena `arena` ->
+        [PcmStatsRecord]; route 0 = the serial host twin, route 1 = the arena copied to this GPU and the kernels, route 2 = the
+        kernels' chunking and fold arithmetic on the host."""
+        return pcm_stats_arena(self._ctx, route, descs, bits, arena, min_clip_run, min_zero_run)
+
+    @staticmethod
+    def pcm_stats_kernel_shape():
+        return pcm_stats_kernel_shape()
 
     def verify_mp3(self, files) -> list:
         """rg_mp3_verify: every file decoded by the route the analysis uses, its dropped frames counted, and the LAME music
