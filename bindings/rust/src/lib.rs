@@ -548,3 +548,75 @@ pub mod replaygain {
         })
     }
 }
+
+/// The spectral scan of `include/mp3rgain_amd_spectrum.h`: per channel of every WAV, FLAC or MP3 file the long-term power
+/// spectrum in 256 bands, the frequency above which there is nothing and the depth of the edge there.  A module of its own:
+/// [`ffi`] stays the C ABI of `mp3rgain_amd.h` and `mp3rgain_amd_node.h` alone.  `tests/test_rust_spectrum_layout.py` compares
+/// these declarations with the header.
+pub mod spectrum {
+    use super::ffi::{RgCtx, RgTrackDesc};
+    use std::os::raw::{c_char, c_int, c_void};
+
+    pub const SPEC_BANDLIMITED: u32 = 1;
+    pub const SPEC_UPSAMPLED: u32 = 2;
+    pub const SPEC_SHORT: u32 = 4;
+    pub const SPEC_NONFINITE: u32 = 8;
+    pub const SPEC_COMPLETE: u32 = 16;
+    pub const SPEC_MAX_CHANNELS: usize = 8;
+    pub const SPEC_BANDS: usize = 256;
+
+    #[derive(Clone, Copy, Debug)]
+    #[repr(C)]
+    /// `rg_spectrum_opts`: both greater than 0; a null pointer means `{30.0, 4000.0}`
+    pub struct RgSpectrumOpts {
+        pub edge_db: f64,
+        pub min_cutoff_hz: f64,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_spectrum_channel`
+    pub struct RgSpectrumChannel {
+        pub cutoff_hz: f64,
+        pub edge_db: f64,
+        pub analysed_frames: u32,
+        pub skipped_frames: u32,
+        pub flags: u32,
+        pub reserved: u32,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_spectrum_result`
+    pub struct RgSpectrumResult {
+        pub status: i32,
+        pub flags: u32,
+        pub frames: u64,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub format: u32,
+        pub dropped_frames: u32,
+        pub cutoff_hz: f64,
+        pub ch: [RgSpectrumChannel; 8],
+    }
+
+    extern "C" {
+        pub fn rg_spectrum(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, opts: *const RgSpectrumOpts, out: *mut RgSpectrumResult, bands_out: *mut f64) -> c_int;
+        pub fn rg_spectrum_arena(ctx: *mut c_void, route: c_int, n: usize, descs: *const RgTrackDesc, opts: *const RgSpectrumOpts, arena: *const c_void, arena_bytes: usize, out: *mut RgSpectrumResult, bands_out: *mut f64) -> c_int;
+        pub fn rg_spectrum_verdict(p: *const f64, analysed_frames: u32, sample_rate: u32, opts: *const RgSpectrumOpts, out: *mut RgSpectrumChannel) -> c_int;
+        pub fn rg_spectrum_kernel_shape(frame: *mut u32, hop: *mut u32, bands: *mut u32, frames_per_tile: *mut u32) -> c_int;
+        pub fn rg_spectrum_rate(ctx: *mut c_void, n: usize, frames: u64, format: u32, host_tracks: usize, threads: u32, reps: u32, warm_ms: f64, kernel_ms: *mut f64, host_ms: *mut f64, mismatches: *mut usize) -> c_int;
+    }
+
+    /// The verdict on a caller's 256 band levels (`rg_spectrum_verdict`); `None` for a sample rate of 0 or an option not above 0.
+    pub fn verdict(p: &[f64; 256], analysed_frames: u32, sample_rate: u32, opts: Option<RgSpectrumOpts>) -> Option<RgSpectrumChannel> {
+        let mut out = RgSpectrumChannel::default();
+        let o = opts.as_ref().map_or(std::ptr::null(), |o| o as *const RgSpectrumOpts);
+        let rc = unsafe { rg_spectrum_verdict(p.as_ptr(), analysed_frames, sample_rate, o, &mut out) };
+        if rc == 0 {
+            Some(out)
+        } else {
+            None
+        }
+    }
+}

@@ -51,7 +51,8 @@
  *   RG_STATS_SILENT     every sample is zero, or N = 0
  *   RG_STATS_COMPLETE   dropped_frames == 0
  *
- * Not here: RMS or loudness (the R 128 path has them), spectral detection of lossy transcodes, the node and multi-GPU calls.
+ * Not here: RMS or loudness (the R 128 path has them), the node and multi-GPU calls.  Spectral detection of lossy transcodes
+ * and upsampled files is rg_spectrum (mp3rgain_amd_spectrum.h).
  * Nothing is written to files.
  */
 #ifndef MP3RGAIN_AMD_STATS_H

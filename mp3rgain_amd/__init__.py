@@ -14,6 +14,7 @@ from .replaygain import (  # noqa: F401
     AlbumGainResult,
     Analyzer,
     AudioFileType,
+    ChannelSpectrum,
     ChannelStats,
     FlacVerifyResult,
     Node,
@@ -27,6 +28,7 @@ from .replaygain import (  # noqa: F401
     ReplayGainResult,
     RipChecksums,
     RipOffsetSignatures,
+    Spectrum,
     analyze_album,
     analyze_track,
     find_peak_amplitude,
@@ -36,6 +38,9 @@ from .replaygain import (  # noqa: F401
     r128_layout_weights,
     rip_offsets_arena,
     rip_offsets_kernel_shape,
+    spectrum_arena,
+    spectrum_kernel_shape,
+    spectrum_verdict,
 )
 
 __version__ = "0.1.0"

@@ -330,6 +330,49 @@ STATS_SYMBOLS = [
     ("rg_pcm_stats_rate", _int, [_vp, _sz, _u64, _u32, _int, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz)]),
 ]
 
+# include/mp3rgain_amd_spectrum.h (spectral scan: band spectrum, cutoff, upsampled files)
+SPEC_BANDLIMITED, SPEC_UPSAMPLED, SPEC_SHORT, SPEC_NONFINITE, SPEC_COMPLETE = 1, 2, 4, 8, 16
+SPEC_MAX_CHANNELS, SPEC_FRAME, SPEC_HOP, SPEC_BANDS = 8, 4096, 2048, 256
+SPEC_EDGE_DB, SPEC_MIN_CUTOFF_HZ = 30.0, 4000.0
+
+
+class SpectrumOpts(C.Structure):  # rg_spectrum_opts
+    _fields_ = [("edge_db", C.c_double), ("min_cutoff_hz", C.c_double)]
+
+
+class SpectrumChannel(C.Structure):  # rg_spectrum_channel
+    _fields_ = [
+        ("cutoff_hz", C.c_double),
+        ("edge_db", C.c_double),
+        ("analysed_frames", C.c_uint32),
+        ("skipped_frames", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class SpectrumRecord(C.Structure):  # rg_spectrum_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("cutoff_hz", C.c_double),
+        ("ch", SpectrumChannel * SPEC_MAX_CHANNELS),
+    ]
+
+
+SPECTRUM_SYMBOLS = [
+    ("rg_spectrum", _int, [_vp, _P(C.c_char_p), _sz, _P(SpectrumOpts), _P(SpectrumRecord), _P(_dbl)]),
+    ("rg_spectrum_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _P(SpectrumOpts), _vp, _sz, _P(SpectrumRecord), _P(_dbl)]),
+    ("rg_spectrum_verdict", _int, [_P(_dbl), _u32, _u32, _P(SpectrumOpts), _P(SpectrumChannel)]),
+    ("rg_spectrum_kernel_shape", _int, [_P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_spectrum_rate", _int, [_vp, _sz, _u64, _u32, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_sz)]),
+]
+
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions
 NODE_OPEN = C.CFUNCTYPE(_vp, _int, _vp)
 NODE_CLOSE = C.CFUNCTYPE(None, _vp, _vp)
@@ -370,7 +413,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

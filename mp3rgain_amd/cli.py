@@ -71,6 +71,9 @@ class Options:  # src/main.rs:65-96
     stats: bool = False      # this façade only (--stats): clipping runs, dropouts, DC offset, padded bits, edge silence per file
     clip_run: Optional[int] = None  # with --stats (--clip-run N): full-scale samples in a row that count as a clip run
     zero_run: Optional[int] = None  # with --stats (--zero-run N): zero samples in a row inside the audio that count as a dropout
+    spectrum: bool = False   # this façade only (--spectrum): where the spectrum ends, per file and channel (lossy transcodes, upsampled files)
+    edge_db: Optional[float] = None  # with --spectrum (--edge-db DB): how far the spectrum must fall across the edge
+    min_cutoff: Optional[float] = None  # with --spectrum (--min-cutoff HZ): edges below this frequency are not reported
     files: List[Path] = field(default_factory=list)
 
 
@@ -99,6 +102,13 @@ def _parse_float(s: str, what: str) -> float:
         return float(s)
     except ValueError:
         raise CliError(f"{what}: {s}")
+
+
+def _parse_positive(s: str, what: str) -> float:
+    v = _parse_float(s, what)
+    if not (v > 0.0 and v != float("inf")):
+        raise CliError(f"{what}: {s}")
+    return v
 
 
 def parse_args(args: List[str], out, err) -> Options:
@@ -146,6 +156,12 @@ def parse_args(args: List[str], out, err) -> Options:
             o.clip_run = _parse_int(need("--clip-run", "--clip-run requires an argument"), "invalid run length", 32, signed=False)
         elif arg == "--zero-run":
             o.zero_run = _parse_int(need("--zero-run", "--zero-run requires an argument"), "invalid run length", 32, signed=False)
+        elif arg == "--spectrum":  # not in the reference: a command of its own, like --stats
+            o.spectrum = True
+        elif arg == "--edge-db":
+            o.edge_db = _parse_positive(need("--edge-db", "--edge-db requires an argument"), "invalid edge depth")
+        elif arg == "--min-cutoff":
+            o.min_cutoff = _parse_positive(need("--min-cutoff", "--min-cutoff requires an argument"), "invalid frequency")
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -252,6 +268,10 @@ def parse_args(args: List[str], out, err) -> Options:
         raise CliError("--zero-run requires --stats")
     if o.clip_run == 0 or o.zero_run == 0:
         raise CliError("--clip-run and --zero-run take a length of at least 1")
+    if o.edge_db is not None and not o.spectrum:
+        raise CliError("--edge-db requires --spectrum")
+    if o.min_cutoff is not None and not o.spectrum:
+        raise CliError("--min-cutoff requires --spectrum")
     return o
 
 
@@ -485,6 +505,8 @@ class Cli:
             return self.cmd_rip()
         if o.stats:
             return self.cmd_stats()
+        if o.spectrum:
+            return self.cmd_spectrum()
         if o.max_amplitude_only:
             return self.cmd_max_amplitude()
         if o.stored_tag_mode == "delete":
@@ -753,6 +775,64 @@ class Cli:
                     self.p(f"    ch {k}: peak {c.peak:.6f}  DC {c.dc_offset:+.6f}  clipped {c.clipped} in {c.clip_runs} run(s){first}"
                            f"  dropouts {c.zero_runs}" + (f" (longest {c.longest_zero_run})" if c.zero_runs else "")
                            + (f"  non-finite {c.nonfinite}" if c.nonfinite else ""))
+        if o.output_format == "json":
+            _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+        return 1 if failed else 0
+
+    # ---- --spectrum (not in the reference): where the spectrum ends, on the GPU -----------------------------------------
+    def cmd_spectrum(self) -> int:
+        """Every file decoded by the route the analysis uses and transformed on the first GPU (rg_spectrum): per channel the
+        frequency above which there is nothing, the depth of the edge there, the frames analysed and skipped.  The findings are
+        a report: exit status 1 only when a file fails or has dropped frames.  TSV, no header: a row per file `file, verdicts,
+        cutoff Hz (the record's: the maximum over the channels), edge dB (of the band-limited channel with the lowest cutoff, 0
+        without one), frames, sample rate, channels, dropped frames` and a row per channel `file, "ch", index, cutoff Hz,
+        edge dB, analysed frames, skipped frames, flags`, told apart by the word in the second field (a failing file: `file,
+        error text`).  JSON adds per channel the 256 band levels in dB relative to the loudest band (null for an empty band)."""
+        o = self.o
+        want_bands = o.output_format == "json"
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            res = an.spectrum(o.files, o.edge_db, o.min_cutoff, bands=want_bands)
+        if self.talk:
+            self.p(f"mp3rgain spectrum of {len(o.files)} file(s): edges of at least {30.0 if o.edge_db is None else o.edge_db:g} dB "
+                   f"above {4000.0 if o.min_cutoff is None else o.min_cutoff:g} Hz")
+            self.p()
+        results, failed = [], 0
+        for file, r in zip(o.files, res):
+            bad = r.error is not None or not r.complete
+            failed += bad
+            words = r.verdicts
+            flag_words = lambda c: ",".join(w for w, on in (("bandlimited", c.bandlimited), ("upsampled", c.upsampled)) if on) or "ok"  # noqa: E731
+            if o.output_format == "json":
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                else:
+                    d.update(verdicts=words, summary=r.words, cutoff_hz=r.cutoff_hz, edge_db=r.edge_db, frames=r.frames, sample_rate=r.sample_rate,
+                             dropped_frames=r.dropped_frames, bandlimited=r.bandlimited, upsampled=r.upsampled, short=r.short,
+                             nonfinite=r.nonfinite, complete=r.complete,
+                             channels=[{"cutoff_hz": c.cutoff_hz, "edge_db": c.edge_db, "analysed_frames": c.analysed_frames,
+                                        "skipped_frames": c.skipped_frames, "bandlimited": c.bandlimited, "upsampled": c.upsampled,
+                                        "band_hz": r.sample_rate * 8 / 4096,
+                                        "levels_db": [None if x == float("-inf") else round(x, 2) for x in c.levels_db]} for c in r.channels])
+                results.append(d)
+            elif o.output_format == "tsv":
+                if r.error is not None:
+                    self.p(f"{_name(file)}\t{r.error}")
+                    continue
+                self.p(f"{_name(file)}\t{','.join(words)}\t{r.cutoff_hz:.1f}\t{r.edge_db:.1f}\t{r.frames}\t{r.sample_rate}\t{len(r.channels)}\t"
+                       f"{r.dropped_frames}")
+                for k, c in enumerate(r.channels):
+                    self.p(f"{_name(file)}\tch\t{k}\t{c.cutoff_hz:.1f}\t{c.edge_db:.1f}\t{c.analysed_frames}\t{c.skipped_frames}\t{flag_words(c)}")
+            elif r.error is not None:
+                self.e(f"{_name(file)} - {r.error}")
+            elif bad or not o.quiet:
+                self.p(f"{_name(file)} - {', '.join(words)}  [{r.sample_rate} Hz"
+                       + (f", {r.dropped_frames} frames dropped" if r.dropped_frames else "") + "]")
+                self.p(f"    {r.words}")
+                for k, c in enumerate(r.channels):
+                    self.p(f"    ch {k}: cutoff {c.cutoff_hz:.0f} Hz  edge {c.edge_db:.1f} dB  frames {c.analysed_frames}"
+                           + (f" (+{c.skipped_frames} skipped)" if c.skipped_frames else "") + f"  {flag_words(c)}")
         if o.output_format == "json":
             _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
         return 1 if failed else 0
@@ -1402,6 +1482,11 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "            status 1 only for a file that fails or has dropped frames",
         "--clip-run <n>   With --stats: full-scale samples in a row that count as a clip run (default 3)",
         "--zero-run <n>   With --stats: zero samples in a row inside the audio that count as a dropout (default 64)",
+        "--spectrum  Spectral scan on the GPU (WAV, FLAC, MP3): per channel the frequency above which there is nothing and the depth",
+        "            of the edge there -- a lossless file made from a lossy one, a high-rate file made from a CD.  A report: exit",
+        "            status 1 only for a file that fails or has dropped frames",
+        "--edge-db <dB>   With --spectrum: how far the spectrum must fall across the edge (default 30)",
+        "--min-cutoff <Hz>  With --spectrum: edges below this frequency are not reported (default 4000)",
         "-v          Show version",
         "-h          Show this help",
     ):

@@ -322,6 +322,7 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_mp3_crc.release();
     c->d_rip.release();
     c->d_stats.release();
+    c->d_spectrum.release();
     c->h_mp3_crc.release();
     if (c->file_pool && c->file_pool_free) c->file_pool_free(c->file_pool);
     c->file_pool = nullptr;

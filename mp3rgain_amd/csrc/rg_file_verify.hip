@@ -1,6 +1,6 @@
 // rg_file_verify.hip -- the file-level calls that check files instead of measuring loudness: rg_flac_verify
 // (include/mp3rgain_amd_flac.h), rg_mp3_verify (include/mp3rgain_amd_mp3verify.h), rg_rip_checksums
-// (include/mp3rgain_amd_rip.h) and rg_pcm_stats (include/mp3rgain_amd_stats.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
+// (include/mp3rgain_amd_rip.h), rg_pcm_stats (include/mp3rgain_amd_stats.h) and rg_spectrum (include/mp3rgain_amd_spectrum.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
 // command: what this library does not decode itself is not a stream it could vouch for.  A file's status lives in its record,
 // and the record of a file that failed holds nothing else.
 #include <algorithm>
@@ -9,6 +9,7 @@
 #include "rg_flac_md5.h"
 #include "rg_mp3verify.h"
 #include "rg_rip.h"
+#include "rg_spectrum.h"
 #include "rg_stats.h"
 
 using namespace rgf;
@@ -393,4 +394,89 @@ extern "C" int rg_pcm_stats(rg_ctx *c, const char *const *paths, size_t n, const
     if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
     if (n) memset(out, 0, n * sizeof *out);
     return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return stats_group(c, paths, first, cnt, o, out); });
+}
+
+// ---- rg_spectrum ----------------------------------------------------------------------------------------------------------
+// one group of the call: rg_pcm_stats' route and screen, and the two kernels of rg_spectrum.hip over the planes where the decode
+// left them, on the stream the decode ran on.  The verdict is host arithmetic on what comes back (rg_spec_fill).
+static int spectrum_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_spectrum_opts &o, rg_spectrum_result *out, double *bands) {
+    out += first;
+    if (bands) bands += first * RG_SPEC_MAX_CHANNELS * RG_SPEC_BANDS;
+    FileGroup g(c, paths, first, n);
+    int rc = g.load(LoadOpts{-1, false});
+    if (rc != RG_OK) return rc;
+    const auto mark = mark_record(g, out);
+    const auto refused = [&](size_t i, const std::string &why) { return "No spectrum (" + why + "): " + g.paths[i]; };
+    // a WAV stream the staging cannot lay out, or anything of more than 8 channels, fails alone and in front of the staging
+    const auto screen = [&](size_t i, std::string *text) -> int {
+        uint32_t channels = g.in[i].channels;
+        if (g.in[i].kind == LoadedAudio::Wav) {
+            rg_wav_info w;
+            if (rg_wav_parse(g.in[i].wav.data(), g.in[i].wav.size(), &w) != RG_OK) {
+                *text = std::string("Failed to probe format: ") + g.paths[i];
+                return RG_ERR_FORMAT;
+            }
+            if (wav_kind(w) < 0) {
+                *text = refused(i, std::to_string(w.bits_per_sample) + "-bit " + (w.sample_format == 3 ? "float" : "samples of format " + std::to_string(w.sample_format)) +
+                                       ", not 8, 16, 24 or 32-bit integer or 32-bit float PCM");
+                return RG_ERR_FORMAT;
+            }
+            channels = w.channels;
+        }
+        if (channels <= RG_SPEC_MAX_CHANNELS) return RG_OK;
+        *text = refused(i, std::to_string(channels) + " channels, more than " + std::to_string(RG_SPEC_MAX_CHANNELS));
+        return RG_ERR_FORMAT;
+    };
+    const auto work = [&]() -> int {
+        const std::vector<LoadedAudio> &in = g.in;
+        std::vector<RgSpecPlane> planes(g.slot.size() * RG_SPEC_MAX_CHANNELS + 1);
+        std::vector<size_t> rec_of, plane_of;  // record -> position in the batch, its first plane
+        std::vector<uint32_t> dropped;
+        size_t n_planes = 0;
+        for (size_t k = 0; k < g.slot.size(); ++k) {
+            const size_t i = g.slot[k];
+            const LoadedAudio &la = in[k];
+            uint32_t lost = 0;
+            if (la.kind == LoadedAudio::Flac) {
+                lost = g.counts[k].dropped;
+            } else if (la.kind != LoadedAudio::Wav) {  // an MPEG stream: the frames the route dropped, as rg_mp3_verify counts them
+                const uint32_t spf = g.descs[k].sample_rate >= 32000 ? 1152 : 576;
+                lost = la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
+            }
+            char err[256] = "";
+            const int prc = rg_spec_track_planes(i, g.descs[k], g.arena_bytes, &planes[n_planes], err, sizeof err);
+            if (prc == RG_ERR_FORMAT) {
+                mark(i, RG_ERR_FORMAT, refused(i, err));
+                continue;
+            }
+            if (prc != RG_OK) return rg_set_err(c, prc, "%s", err);
+            rec_of.push_back(k);
+            plane_of.push_back(n_planes);
+            dropped.push_back(lost);
+            n_planes += g.descs[k].channels;
+        }
+        if (rec_of.empty()) return RG_OK;
+        std::vector<RgSpecPlaneOut> po(n_planes);
+        const int drc = rg_spectrum_device(c, c->d_arena.p, planes.data(), n_planes, po.data(), c->file_stream());
+        if (drc != RG_OK) return drc;
+        for (size_t j = 0; j < rec_of.size(); ++j) {
+            const size_t k = rec_of[j];
+            rg_spec_fill(g.descs[k], dropped[j], &po[plane_of[j]], o, &out[g.slot[k]],
+                         bands ? bands + g.slot[k] * RG_SPEC_MAX_CHANNELS * RG_SPEC_BANDS : nullptr);
+        }
+        return RG_OK;
+    };
+    g.want_counts = true;
+    return g.run(screen, mark, work);
+}
+
+extern "C" int rg_spectrum(rg_ctx *c, const char *const *paths, size_t n, const rg_spectrum_opts *opts, rg_spectrum_result *out, double *bands_out) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    rg_spectrum_opts o;
+    char err[256] = "";
+    const int orc = rg_spec_options(opts, &o, err, sizeof err);
+    if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
+    if (n) memset(out, 0, n * sizeof *out);
+    if (n && bands_out) memset(bands_out, 0, n * RG_SPEC_MAX_CHANNELS * RG_SPEC_BANDS * sizeof(double));
+    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return spectrum_group(c, paths, first, cnt, o, out, bands_out); });
 }

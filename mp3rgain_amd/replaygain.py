@@ -334,6 +334,168 @@ def pcm_stats_from_record(r, error=None) -> PcmStats:
                     int(r.trail_silence_frames), int(r.flags), ch, error)
 
 
+def _spectrum_opts(edge_db, min_cutoff_hz):
+    """rg_spectrum_opts, or NULL (the header's defaults) when both are None."""
+    if edge_db is None and min_cutoff_hz is None:
+        return None
+    return C.byref(_capi.SpectrumOpts(_capi.SPEC_EDGE_DB if edge_db is None else float(edge_db),
+                                      _capi.SPEC_MIN_CUTOFF_HZ if min_cutoff_hz is None else float(min_cutoff_hz)))
+
+
+def _spectrum_bands(n):
+    return np.zeros((max(1, n), _capi.SPEC_MAX_CHANNELS, _capi.SPEC_BANDS), dtype=np.float64)
+
+
+def spectrum_arena(ctx, route: int, descs, arena, edge_db=None, min_cutoff_hz=None, bands=True):
+    """rg_spectrum_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> ([SpectrumRecord], E) with E
+    a float64 array [track, 8, 256] of band energies (None when `bands` is false).  Both options None = the header's defaults."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    out = (_capi.SpectrumRecord * max(1, n))()
+    e = _spectrum_bands(n) if bands else None
+    rc = L.rg_spectrum_arena(ctx, int(route), n, d, _spectrum_opts(edge_db, min_cutoff_hz), arena.ctypes.data if arena.size else None, arena.size, out,
+                             e.ctypes.data_as(C.POINTER(C.c_double)) if bands else None)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return list(out[:n]), (e[:n] if bands else None)
+
+
+def spectrum_kernel_shape():
+    """rg_spectrum_kernel_shape -> (frame, hop, bands, frames_per_tile)."""
+    f, h, b, t = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _capi.load().rg_spectrum_kernel_shape(C.byref(f), C.byref(h), C.byref(b), C.byref(t))
+    return f.value, h.value, b.value, t.value
+
+
+def spectrum_verdict(p, analysed_frames: int, sample_rate: int, edge_db=None, min_cutoff_hz=None):
+    """rg_spectrum_verdict on 256 band levels -> SpectrumChannel (the C record)."""
+    L = _capi.load()
+    a = np.ascontiguousarray(p, dtype=np.float64)
+    if a.shape != (_capi.SPEC_BANDS,):
+        raise ValueError("spectrum_verdict takes 256 numbers")
+    out = _capi.SpectrumChannel()
+    rc = L.rg_spectrum_verdict(a.ctypes.data_as(C.POINTER(C.c_double)), int(analysed_frames), int(sample_rate), _spectrum_opts(edge_db, min_cutoff_hz),
+                               C.byref(out))
+    if rc != 0:
+        raise ReplayGainError(rc, "rg_spectrum_verdict: a sample rate of 0, or an option that is not greater than 0")
+    return out
+
+
+@dataclass
+class ChannelSpectrum:
+    """One channel of a Spectrum (rg_spectrum_channel, include/mp3rgain_amd_spectrum.h)."""
+    cutoff_hz: float         # the upper edge of the last band in front of the edge; sample_rate / 2 when there is no edge
+    edge_db: float           # the 8 bands below the edge over the 8 above it; 0 when there is no edge
+    analysed_frames: int
+    skipped_frames: int      # frames of a float plane with a NaN or Inf
+    flags: int
+    bands: Optional[object] = None  # E[j]: 256 float64, when they were asked for
+
+    @property
+    def bandlimited(self) -> bool:
+        return bool(self.flags & _capi.SPEC_BANDLIMITED)
+
+    @property
+    def upsampled(self) -> bool:
+        return bool(self.flags & _capi.SPEC_UPSAMPLED)
+
+    @property
+    def levels_db(self):
+        """The 256 band levels in dB relative to the loudest band (None without bands; -inf for an empty band)."""
+        if self.bands is None:
+            return None
+        e = np.asarray(self.bands, dtype=np.float64)
+        top = float(e.max()) if e.size else 0.0
+        if not top > 0.0:
+            return [float("-inf")] * len(e)
+        with np.errstate(divide="ignore"):
+            return [float(x) for x in 10.0 * np.log10(e / top)]
+
+
+@dataclass
+class Spectrum:
+    """One file of Analyzer.spectrum (rg_spectrum_result): where the spectrum ends."""
+    frames: int
+    sample_rate: int
+    format: int              # rg_sample_format of the planes that were transformed
+    dropped_frames: int
+    cutoff_hz: float         # the maximum over the channels
+    flags: int
+    channels: list           # [ChannelSpectrum]
+    error: Optional["ReplayGainError"] = None  # why there are no numbers; every other field is then zero
+
+    @property
+    def bandlimited(self) -> bool:
+        return bool(self.flags & _capi.SPEC_BANDLIMITED)
+
+    @property
+    def upsampled(self) -> bool:
+        return bool(self.flags & _capi.SPEC_UPSAMPLED)
+
+    @property
+    def short(self) -> bool:
+        return bool(self.flags & _capi.SPEC_SHORT)
+
+    @property
+    def nonfinite(self) -> bool:
+        return bool(self.flags & _capi.SPEC_NONFINITE)
+
+    @property
+    def complete(self) -> bool:
+        return bool(self.flags & _capi.SPEC_COMPLETE)
+
+    @property
+    def cut_channels(self) -> list:
+        """The indices of the band-limited channels."""
+        return [k for k, c in enumerate(self.channels) if c.bandlimited]
+
+    @property
+    def lowest_cut(self) -> Optional["ChannelSpectrum"]:
+        """The band-limited channel with the lowest cutoff (the first of equals); None when no channel is band-limited.  The
+        record's own cutoff_hz is the maximum over all channels, which is Nyquist as soon as one channel has no edge."""
+        cut = [c for c in self.channels if c.bandlimited]
+        return min(cut, key=lambda c: c.cutoff_hz) if cut else None
+
+    @property
+    def edge_db(self) -> float:
+        """The edge of `lowest_cut`; 0 when no channel is band-limited."""
+        c = self.lowest_cut
+        return c.edge_db if c is not None else 0.0
+
+    @property
+    def verdicts(self) -> list:
+        """The flags as words, in a fixed order; ["ok"] when there is nothing to report."""
+        names = (("bandlimited", self.bandlimited), ("upsampled", self.upsampled), ("short", self.short), ("nonfinite", self.nonfinite),
+                 ("incomplete", self.error is None and not self.complete))
+        return [n for n, on in names if on] or ["ok"]
+
+    @property
+    def words(self) -> str:
+        """One line of plain words."""
+        if self.short or not any(c.analysed_frames for c in self.channels):
+            return "too short to analyse"
+        c, cut = self.lowest_cut, self.cut_channels
+        if c is None:
+            return "no cutoff below Nyquist"
+        some = "" if len(cut) == len(self.channels) else f" (channel{'s' if len(cut) > 1 else ''} {', '.join(str(k) for k in cut)} of {len(self.channels)})"
+        if self.upsampled:
+            top = max(x.cutoff_hz for x in self.channels if x.upsampled)
+            return f"{self.sample_rate / 1000:g} kHz file with nothing above {top / 1000:.1f} kHz{some}"
+        return f"cut off at {c.cutoff_hz / 1000:.1f} kHz, edge {c.edge_db:.0f} dB{some}"
+
+
+def spectrum_from_record(r, error=None, bands=None) -> Spectrum:
+    """A Spectrum from an rg_spectrum_result (and its [8, 256] band energies)."""
+    ch = []
+    for k in range(int(r.channels)):
+        c = r.ch[k]
+        ch.append(ChannelSpectrum(float(c.cutoff_hz), float(c.edge_db), int(c.analysed_frames), int(c.skipped_frames), int(c.flags),
+                                  None if bands is None else np.array(bands[k], dtype=np.float64)))
+    return Spectrum(int(r.frames), int(r.sample_rate), int(r.format), int(r.dropped_frames), float(r.cutoff_hz), int(r.flags), ch, error)
+
+
 @dataclass
 class FlacVerifyResult:
     """One file of Analyzer.verify_flac (rg_flac_verify_result): the decoded PCM's MD5 against STREAMINFO's signature."""
@@ -1107,6 +1269,48 @@ class Analyzer:
     @staticmethod
     def pcm_stats_kernel_shape():
         return pcm_stats_kernel_shape()
+
+    def _spectrum_call(self, files, edge_db, min_cutoff_hz, bands):
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (_capi.SpectrumRecord * max(1, n))()
+        e = _spectrum_bands(n) if bands else None
+        self._check(self._lib.rg_spectrum(self._ctx, paths, n, _spectrum_opts(edge_db, min_cutoff_hz), out,
+                                          e.ctypes.data_as(C.POINTER(C.c_double)) if bands else None))
+        return out, e
+
+    def spectrum(self, files, edge_db=None, min_cutoff_hz=None, bands: bool = False) -> list:
+        """rg_spectrum: `files` (WAV, FLAC or MPEG Layer III) decoded by the route the analysis uses and, from the PCM where it
+        lies on this GPU, per channel the long-term power spectrum in 256 bands, the frequency above which there is nothing and
+        the steepness of the edge there -> [Spectrum], with the band energies in every channel's `.bands` when `bands` is true.
+        A file that takes no part carries its ReplayGainError in `.error`."""
+        out, e = self._spectrum_call(files, edge_db, min_cutoff_hz, bands)
+        res = []
+        for i in range(len(files)):
+            err = None
+            if out[i].status != 0:
+                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
+            res.append(spectrum_from_record(out[i], err, e[i] if bands else None))
+        return res
+
+    def spectrum_raw(self, files, edge_db=None, min_cutoff_hz=None):
+        """spectrum's rg_spectrum_result array and band energies as the C call left them -> (bytes, bytes)."""
+        out, e = self._spectrum_call(files, edge_db, min_cutoff_hz, True)
+        return bytes(out)[:len(files) * C.sizeof(_capi.SpectrumRecord)], e[:len(files)].tobytes()
+
+    def spectrum_arena(self, route: int, descs, arena, edge_db=None, min_cutoff_hz=None, bands=True):
+        """rg_spectrum_arena, the seam of the spectrum kernels: the tracks `descs` describe in the host arena `arena` ->
+        ([SpectrumRecord], E); route 0 = the serial host twin in double, route 1 = the arena copied to this GPU and the kernels,
+        route 2 = the kernels' arithmetic on the host."""
+        return spectrum_arena(self._ctx, route, descs, arena, edge_db, min_cutoff_hz, bands)
+
+    @staticmethod
+    def spectrum_kernel_shape():
+        return spectrum_kernel_shape()
+
+    @staticmethod
+    def spectrum_verdict(p, analysed_frames, sample_rate, edge_db=None, min_cutoff_hz=None):
+        return spectrum_verdict(p, analysed_frames, sample_rate, edge_db, min_cutoff_hz)
 
     def verify_mp3(self, files) -> list:
         """rg_mp3_verify: every file decoded by the route the analysis uses, its dropped frames counted, and the LAME music
