@@ -549,6 +549,72 @@ pub mod replaygain {
     }
 }
 
+/// The dynamic range (DR) figure of `include/mp3rgain_amd_dr.h`: per channel of every WAV, FLAC or MP3 file the mean square and
+/// the peak of every 3-second block, the loudest fifth of the blocks and the second-highest block peak, and from them the DR
+/// value.  The definitions follow the published description of the TT DR meter and are a convention of that header, unverified
+/// against the TT meter or foobar2000.  A module of its own, as [`spectrum`] is.  `tests/test_rust_dr_layout.py` compares these
+/// declarations with the header.
+pub mod dr {
+    use super::ffi::RgCtx;
+    use std::os::raw::{c_char, c_int};
+
+    pub const DR_COMPLETE: u32 = 1;
+    pub const DR_SILENT: u32 = 2;
+    pub const DR_NONFINITE: u32 = 4;
+    pub const DR_SHORT: u32 = 8;
+    pub const DR_MAX_CHANNELS: usize = 8;
+    pub const DR_TOP_PERMILLE: u32 = 200;
+    pub const DR_MAX_BLOCK_FRAMES: u32 = 1152000;
+
+    #[derive(Clone, Copy, Debug)]
+    #[repr(C)]
+    /// `rg_dr_opts`: `block_frames` 0 = 3 * sample rate, `top_permille` 1 .. 1000; a null pointer means `{0, 200}`
+    pub struct RgDrOpts {
+        pub block_frames: u32,
+        pub top_permille: u32,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_dr_channel`
+    pub struct RgDrChannel {
+        pub dr: f64,
+        pub peak_db: f64,
+        pub rms_db: f64,
+        pub top_ms: f64,
+        pub mean_square: f64,
+        pub peak: u32,
+        pub peak2: u32,
+        pub blocks: u32,
+        pub top_blocks: u32,
+        pub nonfinite: u32,
+        pub reserved: u32,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_dr_result`
+    pub struct RgDrResult {
+        pub status: i32,
+        pub flags: u32,
+        pub frames: u64,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub format: u32,
+        pub dropped_frames: u32,
+        pub block_frames: u32,
+        pub dr: i32,
+        pub dr_mean: f64,
+        pub peak_db: f64,
+        pub rms_db: f64,
+        pub ch: [RgDrChannel; 8],
+    }
+
+    extern "C" {
+        pub fn rg_dynamic_range(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, opts: *const RgDrOpts, out: *mut RgDrResult) -> c_int;
+    }
+}
+
 /// The spectral scan of `include/mp3rgain_amd_spectrum.h`: per channel of every WAV, FLAC or MP3 file the long-term power
 /// spectrum in 256 bands, the frequency above which there is nothing and the depth of the edge there.  A module of its own:
 /// [`ffi`] stays the C ABI of `mp3rgain_amd.h` and `mp3rgain_amd_node.h` alone.  `tests/test_rust_spectrum_layout.py` compares

@@ -51,7 +51,8 @@
  *   RG_STATS_SILENT     every sample is zero, or N = 0
  *   RG_STATS_COMPLETE   dropped_frames == 0
  *
- * Not here: RMS or loudness (the R 128 path has them), the node and multi-GPU calls.  Spectral detection of lossy transcodes
+ * Not here: RMS or loudness (the R 128 path has LUFS, loudness range and true peak; the per-block RMS, the peaks and the DR value
+ * are rg_dynamic_range, mp3rgain_amd_dr.h), the node and multi-GPU calls.  Spectral detection of lossy transcodes
  * and upsampled files is rg_spectrum (mp3rgain_amd_spectrum.h).
  * Nothing is written to files.
  */

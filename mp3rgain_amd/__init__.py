@@ -14,8 +14,10 @@ from .replaygain import (  # noqa: F401
     AlbumGainResult,
     Analyzer,
     AudioFileType,
+    ChannelDynamicRange,
     ChannelSpectrum,
     ChannelStats,
+    DynamicRange,
     FlacVerifyResult,
     Node,
     PcmStats,
@@ -29,8 +31,12 @@ from .replaygain import (  # noqa: F401
     RipChecksums,
     RipOffsetSignatures,
     Spectrum,
+    album_dr,
     analyze_album,
     analyze_track,
+    dr_arena,
+    dr_kernel_shape,
+    dynamic_range_from_record,
     find_peak_amplitude,
     is_available,
     pcm_stats_arena,

@@ -373,6 +373,56 @@ SPECTRUM_SYMBOLS = [
     ("rg_spectrum_rate", _int, [_vp, _sz, _u64, _u32, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_sz)]),
 ]
 
+# include/mp3rgain_amd_dr.h (dynamic range: per-block RMS and peaks, the loudest fifth of the blocks)
+DR_COMPLETE, DR_SILENT, DR_NONFINITE, DR_SHORT = 1, 2, 4, 8
+DR_MAX_CHANNELS, DR_TOP_PERMILLE, DR_MAX_BLOCK_FRAMES = 8, 200, 1152000
+
+
+class DrOpts(C.Structure):  # rg_dr_opts
+    _fields_ = [("block_frames", C.c_uint32), ("top_permille", C.c_uint32)]
+
+
+class DrChannel(C.Structure):  # rg_dr_channel
+    _fields_ = [
+        ("dr", C.c_double),
+        ("peak_db", C.c_double),
+        ("rms_db", C.c_double),
+        ("top_ms", C.c_double),
+        ("mean_square", C.c_double),
+        ("peak", C.c_uint32),
+        ("peak2", C.c_uint32),
+        ("blocks", C.c_uint32),
+        ("top_blocks", C.c_uint32),
+        ("nonfinite", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class DrRecord(C.Structure):  # rg_dr_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("block_frames", C.c_uint32),
+        ("dr", C.c_int32),
+        ("dr_mean", C.c_double),
+        ("peak_db", C.c_double),
+        ("rms_db", C.c_double),
+        ("ch", DrChannel * DR_MAX_CHANNELS),
+    ]
+
+
+DR_SYMBOLS = [
+    ("rg_dynamic_range", _int, [_vp, _P(C.c_char_p), _sz, _P(DrOpts), _P(DrRecord)]),
+    ("rg_dr_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _P(DrOpts), _vp, _sz, _P(DrRecord)]),
+    ("rg_dr_kernel_shape", _int, [_u32, _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_dr_rate", _int, [_vp, _sz, _u64, _u32, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz), _P(_u64)]),
+]
+
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions
 NODE_OPEN = C.CFUNCTYPE(_vp, _int, _vp)
 NODE_CLOSE = C.CFUNCTYPE(None, _vp, _vp)
@@ -413,7 +463,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

@@ -74,6 +74,8 @@ class Options:  # src/main.rs:65-96
     spectrum: bool = False   # this façade only (--spectrum): where the spectrum ends, per file and channel (lossy transcodes, upsampled files)
     edge_db: Optional[float] = None  # with --spectrum (--edge-db DB): how far the spectrum must fall across the edge
     min_cutoff: Optional[float] = None  # with --spectrum (--min-cutoff HZ): edges below this frequency are not reported
+    dr: bool = False         # this façade only (--dr): the dynamic range (DR) figure per file, and the album's
+    dr_top: Optional[int] = None  # with --dr (--dr-top PERMILLE): the share of the loudest blocks that count, in per mille
     files: List[Path] = field(default_factory=list)
 
 
@@ -162,6 +164,10 @@ def parse_args(args: List[str], out, err) -> Options:
             o.edge_db = _parse_positive(need("--edge-db", "--edge-db requires an argument"), "invalid edge depth")
         elif arg == "--min-cutoff":
             o.min_cutoff = _parse_positive(need("--min-cutoff", "--min-cutoff requires an argument"), "invalid frequency")
+        elif arg == "--dr":  # not in the reference: a command of its own, like --stats
+            o.dr = True
+        elif arg == "--dr-top":
+            o.dr_top = _parse_int(need("--dr-top", "--dr-top requires an argument"), "invalid per mille value", 32, signed=False)
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -272,6 +278,17 @@ def parse_args(args: List[str], out, err) -> Options:
         raise CliError("--edge-db requires --spectrum")
     if o.min_cutoff is not None and not o.spectrum:
         raise CliError("--min-cutoff requires --spectrum")
+    if o.dr_top is not None and not o.dr:
+        raise CliError("--dr-top requires --dr")
+    if o.dr_top is not None and not 1 <= o.dr_top <= 1000:
+        raise CliError(f"--dr-top takes 1 to 1000 per mille: {o.dr_top}")
+    if o.dr:
+        others = [name for name, on in (("--verify", o.verify), ("--rip", o.rip), ("--stats", o.stats), ("--spectrum", o.spectrum), ("--r128", o.r128),
+                                        ("-x", o.max_amplitude_only), ("-r", o.track_gain), ("-a", o.album_gain), ("-u", o.undo),
+                                        ("-g", o.gain_steps is not None), ("-l", o.channel_gain is not None),
+                                        ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
+        if others:
+            raise CliError(f"--dr is a command of its own and cannot be combined with {', '.join(others)}")
     return o
 
 
@@ -507,6 +524,8 @@ class Cli:
             return self.cmd_stats()
         if o.spectrum:
             return self.cmd_spectrum()
+        if o.dr:
+            return self.cmd_dr()
         if o.max_amplitude_only:
             return self.cmd_max_amplitude()
         if o.stored_tag_mode == "delete":
@@ -835,6 +854,69 @@ class Cli:
                            + (f" (+{c.skipped_frames} skipped)" if c.skipped_frames else "") + f"  {flag_words(c)}")
         if o.output_format == "json":
             _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+        return 1 if failed else 0
+
+    # ---- --dr (not in the reference): the dynamic range figure, on the GPU ------------------------------------------------
+    def cmd_dr(self) -> int:
+        """Every file decoded by the route the analysis uses and measured on the first GPU (rg_dynamic_range): the DR figure, the
+        peak and the RMS level (with the meter's factor 2) per file and per channel, and the album's figure when more than one
+        file was given.  The figure follows the published description of the TT DR meter and is unverified against it.  A
+        report: exit status 1 only when a file fails or has dropped frames.  TSV, no header: a row per file `file, verdicts, DR,
+        DR mean, peak dB, RMS dB, frames, sample rate, channels, block frames, dropped frames`, a row per channel `file, "ch",
+        index, DR, peak dB, RMS dB, peak, second peak, blocks, top blocks, non-finite` and, for more than one file, a last row
+        `album, DR` (a failing file: `file, error text`); silence has no level: `-inf`, and null in JSON."""
+        o = self.o
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            res = an.dynamic_range(o.files, None, o.dr_top)
+        album = rgmod.album_dr(res) if len(o.files) > 1 else None
+        if self.talk:
+            self.p(f"mp3rgain dynamic range of {len(o.files)} file(s): 3-second blocks, the loudest {200 if o.dr_top is None else o.dr_top} per mille"
+                   " (after the published description of the TT DR meter; unverified against it)")
+            self.p()
+        num = lambda x: None if x == float("-inf") else x  # noqa: E731
+        results, failed = [], 0
+        for file, r in zip(o.files, res):
+            bad = r.error is not None or not r.complete
+            failed += bad
+            words = r.verdicts
+            if o.output_format == "json":
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                else:
+                    d.update(verdicts=words, dr=r.dr, dr_mean=r.dr_mean, peak_db=num(r.peak_db), rms_db=num(r.rms_db), frames=r.frames,
+                             sample_rate=r.sample_rate, block_frames=r.block_frames, dropped_frames=r.dropped_frames, silent=r.silent,
+                             short=r.short, nonfinite=r.nonfinite, complete=r.complete,
+                             channels=[{"dr": c.dr, "peak_db": num(c.peak_db), "rms_db": num(c.rms_db), "top_ms": c.top_ms,
+                                        "mean_square": c.mean_square, "peak": c.peak, "peak2": c.peak2, "blocks": c.blocks,
+                                        "top_blocks": c.top_blocks, "nonfinite": c.nonfinite} for c in r.channels])
+                results.append(d)
+            elif o.output_format == "tsv":
+                if r.error is not None:
+                    self.p(f"{_name(file)}\t{r.error}")
+                    continue
+                self.p(f"{_name(file)}\t{','.join(words)}\t{r.dr}\t{r.dr_mean:.2f}\t{r.peak_db:.2f}\t{r.rms_db:.2f}\t{r.frames}\t{r.sample_rate}\t"
+                       f"{len(r.channels)}\t{r.block_frames}\t{r.dropped_frames}")
+                for k, c in enumerate(r.channels):
+                    self.p(f"{_name(file)}\tch\t{k}\t{c.dr:.2f}\t{c.peak_db:.2f}\t{c.rms_db:.2f}\t{c.peak}\t{c.peak2}\t{c.blocks}\t{c.top_blocks}\t"
+                           f"{c.nonfinite}")
+            elif r.error is not None:
+                self.e(f"{_name(file)} - {r.error}")
+            else:
+                notes = [w for w in words if w != "ok"] + ([f"{r.dropped_frames} frames dropped"] if r.dropped_frames else [])
+                self.p(f"DR{r.dr:<3d} {r.peak_db:8.2f} dB peak {r.rms_db:8.2f} dB RMS   {_name(file)}" + (f"  [{', '.join(notes)}]" if notes else ""))
+                if not o.quiet:
+                    for k, c in enumerate(r.channels):
+                        self.p(f"    ch {k}: DR {c.dr:.2f}  peak {c.peak_db:.2f} dB  RMS {c.rms_db:.2f} dB  blocks {c.top_blocks} of {c.blocks}"
+                               + (f"  non-finite {c.nonfinite}" if c.nonfinite else ""))
+        if o.output_format == "json":
+            extra = {"album_dr": album} if len(o.files) > 1 else {}
+            _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False), **extra)
+        elif len(o.files) > 1 and o.output_format == "tsv":
+            self.p("album\t" + ("" if album is None else str(album)))
+        elif len(o.files) > 1:
+            self.p("album DR" + ("  none: no complete track" if album is None else f"{album}"))
         return 1 if failed else 0
 
     # ---- find_max_amplitude, src/lib.rs:1174-1199 ------------------------------------------------------------
@@ -1487,6 +1569,13 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "            status 1 only for a file that fails or has dropped frames",
         "--edge-db <dB>   With --spectrum: how far the spectrum must fall across the edge (default 30)",
         "--min-cutoff <Hz>  With --spectrum: edges below this frequency are not reported (default 4000)",
+        "--dr        Dynamic range (DR) on the GPU (WAV, FLAC, MP3): per file `DR<n>  peak dB  RMS dB  name`, per channel DR, peak,",
+        "            RMS and the blocks that counted, and a closing `album DR` line for more than one file.  3-second blocks, RMS",
+        "            with the factor 2, the loudest fifth of the blocks, the second-highest block peak: after the published",
+        "            description of the TT DR meter, unverified against it.  JSON fields: dr, dr_mean, peak_db, rms_db, frames,",
+        "            sample_rate, block_frames, dropped_frames, verdicts, channels[dr, peak_db, rms_db, top_ms, mean_square, peak,",
+        "            peak2, blocks, top_blocks, nonfinite], album_dr.  Exit status 1 only for a file that fails or has dropped frames",
+        "--dr-top <permille>  With --dr: the share of the loudest blocks that count (default 200)",
         "-v          Show version",
         "-h          Show this help",
     ):

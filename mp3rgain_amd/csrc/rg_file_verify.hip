@@ -1,10 +1,11 @@
 // rg_file_verify.hip -- the file-level calls that check files instead of measuring loudness: rg_flac_verify
 // (include/mp3rgain_amd_flac.h), rg_mp3_verify (include/mp3rgain_amd_mp3verify.h), rg_rip_checksums
-// (include/mp3rgain_amd_rip.h), rg_pcm_stats (include/mp3rgain_amd_stats.h) and rg_spectrum (include/mp3rgain_amd_spectrum.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
+// (include/mp3rgain_amd_rip.h), rg_pcm_stats (include/mp3rgain_amd_stats.h), rg_dynamic_range (include/mp3rgain_amd_dr.h) and rg_spectrum (include/mp3rgain_amd_spectrum.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
 // command: what this library does not decode itself is not a stream it could vouch for.  A file's status lives in its record,
 // and the record of a file that failed holds nothing else.
 #include <algorithm>
 
+#include "rg_dr.h"
 #include "rg_files.h"
 #include "rg_flac_md5.h"
 #include "rg_mp3verify.h"
@@ -394,6 +395,89 @@ extern "C" int rg_pcm_stats(rg_ctx *c, const char *const *paths, size_t n, const
     if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
     if (n) memset(out, 0, n * sizeof *out);
     return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return stats_group(c, paths, first, cnt, o, out); });
+}
+
+// ---- rg_dynamic_range -----------------------------------------------------------------------------------------------------
+// one group of the call: rg_pcm_stats' route and screen, and the kernels of rg_dr.hip over the planes where the decode left
+// them, on the stream the decode ran on, so tuning key 14 cannot show in the records.  The finish is host arithmetic on what
+// comes back (rg_dr_fill).
+static int dr_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_dr_opts &o, rg_dr_result *out) {
+    out += first;
+    FileGroup g(c, paths, first, n);
+    int rc = g.load(LoadOpts{-1, false});
+    if (rc != RG_OK) return rc;
+    const auto mark = mark_record(g, out);
+    const auto refused = [&](size_t i, const std::string &why) { return "No dynamic range (" + why + "): " + g.paths[i]; };
+    // a WAV stream the staging cannot lay out, or anything of more than 8 channels, fails alone and in front of the staging
+    const auto screen = [&](size_t i, std::string *text) -> int {
+        uint32_t channels = g.in[i].channels;
+        if (g.in[i].kind == LoadedAudio::Wav) {
+            rg_wav_info w;
+            if (rg_wav_parse(g.in[i].wav.data(), g.in[i].wav.size(), &w) != RG_OK) {
+                *text = std::string("Failed to probe format: ") + g.paths[i];
+                return RG_ERR_FORMAT;
+            }
+            if (wav_kind(w) < 0) {
+                *text = refused(i, std::to_string(w.bits_per_sample) + "-bit " + (w.sample_format == 3 ? "float" : "samples of format " + std::to_string(w.sample_format)) +
+                                       ", not 8, 16, 24 or 32-bit integer or 32-bit float PCM");
+                return RG_ERR_FORMAT;
+            }
+            channels = w.channels;
+        }
+        if (channels <= RG_DR_MAX_CHANNELS) return RG_OK;
+        *text = refused(i, std::to_string(channels) + " channels, more than " + std::to_string(RG_DR_MAX_CHANNELS));
+        return RG_ERR_FORMAT;
+    };
+    const auto work = [&]() -> int {
+        const std::vector<LoadedAudio> &in = g.in;
+        std::vector<RgDrPlane> planes(g.slot.size() * RG_DR_MAX_CHANNELS + 1);
+        std::vector<size_t> rec_of, plane_of;  // record -> position in the batch, its first plane
+        std::vector<uint32_t> dropped;
+        size_t n_planes = 0;
+        for (size_t k = 0; k < g.slot.size(); ++k) {
+            const size_t i = g.slot[k];
+            const LoadedAudio &la = in[k];
+            uint32_t lost = 0;
+            if (la.kind == LoadedAudio::Flac) {
+                lost = g.counts[k].dropped;
+            } else if (la.kind != LoadedAudio::Wav) {  // an MPEG stream: the frames the route dropped, as rg_mp3_verify counts them
+                const uint32_t spf = g.descs[k].sample_rate >= 32000 ? 1152 : 576;
+                lost = la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
+            }
+            char err[256] = "";
+            const int prc = rg_dr_track_planes(i, g.descs[k], o, true, g.arena_bytes, &planes[n_planes], err, sizeof err);
+            if (prc == RG_ERR_FORMAT) {
+                mark(i, RG_ERR_FORMAT, refused(i, err));
+                continue;
+            }
+            if (prc != RG_OK) return rg_set_err(c, prc, "%s", err);
+            rec_of.push_back(k);
+            plane_of.push_back(n_planes);
+            dropped.push_back(lost);
+            n_planes += g.descs[k].channels;
+        }
+        if (rec_of.empty()) return RG_OK;
+        std::vector<RgDrPlaneOut> po(n_planes);
+        const int drc = rg_dr_device(c, c->d_arena.p, planes.data(), n_planes, po.data(), c->file_stream());
+        if (drc != RG_OK) return drc;
+        for (size_t j = 0; j < rec_of.size(); ++j) {
+            const size_t k = rec_of[j];
+            rg_dr_fill(g.descs[k], planes[plane_of[j]].block, dropped[j], &po[plane_of[j]], &out[g.slot[k]]);
+        }
+        return RG_OK;
+    };
+    g.want_counts = true;
+    return g.run(screen, mark, work);
+}
+
+extern "C" int rg_dynamic_range(rg_ctx *c, const char *const *paths, size_t n, const rg_dr_opts *opts, rg_dr_result *out) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    rg_dr_opts o;
+    char err[256] = "";
+    const int orc = rg_dr_options(opts, &o, err, sizeof err);
+    if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
+    if (n) memset(out, 0, n * sizeof *out);
+    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return dr_group(c, paths, first, cnt, o, out); });
 }
 
 // ---- rg_spectrum ----------------------------------------------------------------------------------------------------------

@@ -359,4 +359,14 @@ struct rg_ctx;
 // `s` has been synchronised on return
 int rg_stats_device(rg_ctx *c, const unsigned char *d_arena, RgStatsPlane *planes, size_t n, const rg_pcm_stats_opts &o, rg_pcm_stats_channel *ch,
                     hipStream_t s);
+// For the rate hooks of other scans (rg_dr_rate), which time the stats pair over their own arena: the bookkeeping of a launch
+// over `n` planes in an allocation of its own (uploaded on `s`), then the launches alone, then the release.
+struct RgStatsBench {
+    unsigned char *d;
+    size_t n, map, tiles, res;
+    uint64_t fmt_tile[4];
+};
+int rg_stats_bench_setup(rg_ctx *c, RgStatsPlane *planes, size_t n, hipStream_t s, RgStatsBench *b);
+int rg_stats_bench_launch(rg_ctx *c, const unsigned char *d_arena, const RgStatsBench &b, hipStream_t s);
+void rg_stats_bench_free(RgStatsBench *b);
 #endif

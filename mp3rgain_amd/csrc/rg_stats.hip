@@ -207,6 +207,31 @@ int rg_stats_device(rg_ctx *c, const unsigned char *d_arena, RgStatsPlane *plane
     return RG_OK;
 }
 
+// ---- for other scans' rate hooks (rg_stats.h) ---------------------------------------------------------------------------------
+int rg_stats_bench_setup(rg_ctx *c, RgStatsPlane *planes, size_t n, hipStream_t s, RgStatsBench *b) {
+    const uint64_t n_tiles = rg_stats_plan(planes, n, b->fmt_tile);
+    if (n > 0x7fffffffu || n_tiles > 0x7fffffffu) return rg_set_err(c, RG_ERR_INVALID_ARG, "too many tiles for one launch");
+    const StatsLayout l = stats_layout(n, n_tiles);
+    std::vector<unsigned char> head;
+    stats_head(planes, n, l, &head);
+    RG_HIP(c, hipMalloc((void **)&b->d, l.end));
+    b->n = n;
+    b->map = l.map;
+    b->tiles = l.tiles;
+    b->res = l.res;
+    RG_HIP(c, hipMemcpyAsync(b->d, head.data(), head.size(), hipMemcpyHostToDevice, s));
+    RG_HIP(c, hipStreamSynchronize(s));  // (`head` goes away)
+    return RG_OK;
+}
+int rg_stats_bench_launch(rg_ctx *c, const unsigned char *d_arena, const RgStatsBench &b, hipStream_t s) {
+    const StatsLayout l{b.map, b.tiles, b.res, 0};
+    return stats_launch(c, d_arena, b.d, l, b.n, b.fmt_tile, rg_pcm_stats_opts{RG_STATS_MIN_CLIP_RUN, RG_STATS_MIN_ZERO_RUN}, RG_STATS_ANY_TEST != 0, s);
+}
+void rg_stats_bench_free(RgStatsBench *b) {
+    if (b->d) (void)hipFree(b->d);
+    b->d = nullptr;
+}
+
 // ---- test seam (include/mp3rgain_amd_stats.h) -------------------------------------------------------------------------------
 extern "C" int rg_pcm_stats_arena(void *ctx, int route, size_t n, const rg_track_desc *descs, const uint32_t *bits, const rg_pcm_stats_opts *opts,
                                   const void *arena, size_t arena_bytes, rg_pcm_stats_result *out) {

@@ -334,6 +334,111 @@ def pcm_stats_from_record(r, error=None) -> PcmStats:
                     int(r.trail_silence_frames), int(r.flags), ch, error)
 
 
+def _dr_opts(block_frames, top_permille):
+    """rg_dr_opts, or NULL (the header's defaults) when both are None."""
+    if block_frames is None and top_permille is None:
+        return None
+    return C.byref(_capi.DrOpts(0 if block_frames is None else int(block_frames),
+                                _capi.DR_TOP_PERMILLE if top_permille is None else int(top_permille)))
+
+
+def dr_arena(ctx, route: int, descs, arena, block_frames=None, top_permille=None):
+    """rg_dr_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> [DrRecord].  Both options None =
+    the header's defaults (3-second blocks, the loudest 200 per mille)."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    out = (_capi.DrRecord * max(1, n))()
+    rc = L.rg_dr_arena(ctx, int(route), n, d, _dr_opts(block_frames, top_permille), arena.ctypes.data if arena.size else None, arena.size, out)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return list(out[:n])
+
+
+def dr_kernel_shape(fmt: int):
+    """rg_dr_kernel_shape of one rg_sample_format -> (step_samples, piece_samples, fold_lanes, select_bins)."""
+    c, t, f, b = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc = _capi.load().rg_dr_kernel_shape(int(fmt), C.byref(c), C.byref(t), C.byref(f), C.byref(b))
+    if rc != 0:
+        raise ReplayGainError(rc, f"rg_dr_kernel_shape: format {fmt}")
+    return c.value, t.value, f.value, b.value
+
+
+@dataclass
+class ChannelDynamicRange:
+    """One channel of a DynamicRange (rg_dr_channel, include/mp3rgain_amd_dr.h)."""
+    dr: float                # 20 log10((peak2 / s) / sqrt(top_ms)); 0 when either is 0
+    peak_db: float           # -inf for a channel of zeros
+    rms_db: float
+    top_ms: float            # the mean of the loudest blocks' mean squares (with the factor 2)
+    mean_square: float
+    peak: int                # in units of q
+    peak2: int               # the second-highest block peak
+    blocks: int
+    top_blocks: int
+    nonfinite: int
+
+
+@dataclass
+class DynamicRange:
+    """One file of Analyzer.dynamic_range (rg_dr_result).  The figure follows the published description of the TT DR meter
+    and is a convention of include/mp3rgain_amd_dr.h: nobody has checked it against the TT meter or foobar2000."""
+    frames: int
+    sample_rate: int
+    format: int              # rg_sample_format of the planes that were scanned
+    dropped_frames: int
+    block_frames: int
+    flags: int
+    dr: int                  # llrint(dr_mean)
+    dr_mean: float
+    peak_db: float
+    rms_db: float
+    channels: list           # [ChannelDynamicRange]
+    error: Optional["ReplayGainError"] = None  # why there are no numbers; every other field is then zero
+
+    @property
+    def complete(self) -> bool:
+        return bool(self.flags & _capi.DR_COMPLETE)
+
+    @property
+    def silent(self) -> bool:
+        return bool(self.flags & _capi.DR_SILENT)
+
+    @property
+    def nonfinite(self) -> bool:
+        return bool(self.flags & _capi.DR_NONFINITE)
+
+    @property
+    def short(self) -> bool:
+        return bool(self.flags & _capi.DR_SHORT)
+
+    @property
+    def verdicts(self) -> list:
+        """The flags as words, in a fixed order; ["ok"] when there is nothing to report."""
+        names = (("silent", self.silent), ("short", self.short), ("nonfinite", self.nonfinite),
+                 ("incomplete", self.error is None and not self.complete))
+        return [n for n, on in names if on] or ["ok"]
+
+
+def dynamic_range_from_record(r, error=None) -> DynamicRange:
+    """A DynamicRange from an rg_dr_result."""
+    ch = []
+    for k in range(int(r.channels)):
+        c = r.ch[k]
+        ch.append(ChannelDynamicRange(float(c.dr), float(c.peak_db), float(c.rms_db), float(c.top_ms), float(c.mean_square), int(c.peak),
+                                      int(c.peak2), int(c.blocks), int(c.top_blocks), int(c.nonfinite)))
+    return DynamicRange(int(r.frames), int(r.sample_rate), int(r.format), int(r.dropped_frames), int(r.block_frames), int(r.flags), int(r.dr),
+                        float(r.dr_mean), float(r.peak_db), float(r.rms_db), ch, error)
+
+
+def album_dr(records) -> Optional[int]:
+    """The album's figure: llrint (half to even) of the mean of the integer `dr` of the tracks that are complete and have no
+    error; None when there is no such track.  A convention, like the rest of include/mp3rgain_amd_dr.h."""
+    vals = [r.dr for r in records if r.error is None and r.complete]
+    return int(round(sum(vals) / len(vals))) if vals else None
+
+
 def _spectrum_opts(edge_db, min_cutoff_hz):
     """rg_spectrum_opts, or NULL (the header's defaults) when both are None."""
     if edge_db is None and min_cutoff_hz is None:
@@ -1269,6 +1374,42 @@ class Analyzer:
     @staticmethod
     def pcm_stats_kernel_shape():
         return pcm_stats_kernel_shape()
+
+    def _dr_call(self, files, block_frames, top_permille):
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (_capi.DrRecord * max(1, n))()
+        self._check(self._lib.rg_dynamic_range(self._ctx, paths, n, _dr_opts(block_frames, top_permille), out))
+        return out
+
+    def dynamic_range(self, files, block_frames=None, top_permille=None) -> list:
+        """rg_dynamic_range: `files` (WAV, FLAC or MPEG Layer III) decoded by the route the analysis uses and, from the PCM where
+        it lies on this GPU, per channel the mean square and the peak of every 3-second block, the loudest fifth of the blocks
+        and the second-highest block peak, and from them the DR figure -> [DynamicRange].  A file that takes no part carries its
+        ReplayGainError in `.error`."""
+        out = self._dr_call(files, block_frames, top_permille)
+        res = []
+        for i in range(len(files)):
+            err = None
+            if out[i].status != 0:
+                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
+            res.append(dynamic_range_from_record(out[i], err))
+        return res
+
+    def dynamic_range_raw(self, files, block_frames=None, top_permille=None) -> bytes:
+        """dynamic_range's rg_dr_result array as the C call left it (tests compare routes byte for byte)."""
+        out = self._dr_call(files, block_frames, top_permille)
+        return bytes(out)[:len(files) * C.sizeof(_capi.DrRecord)]
+
+    def dr_arena(self, route: int, descs, arena, block_frames=None, top_permille=None):
+        """rg_dr_arena, the seam of the DR kernels: the tracks `descs` describe in the host arena `arena` -> [DrRecord]; route 0
+        = the serial host twin, route 1 = the arena copied to this GPU and the kernels, route 2 = the kernels' cutting and fold
+        arithmetic on the host."""
+        return dr_arena(self._ctx, route, descs, arena, block_frames, top_permille)
+
+    @staticmethod
+    def dr_kernel_shape(fmt: int):
+        return dr_kernel_shape(fmt)
 
     def _spectrum_call(self, files, edge_db, min_cutoff_hz, bands):
         n = len(files)
