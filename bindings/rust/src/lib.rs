@@ -549,6 +549,93 @@ pub mod replaygain {
     }
 }
 
+/// The lossy ancestry scan of `include/mp3rgain_amd_ancestry.h`: is this PCM a decoded MPEG Layer III stream?  Every view of a
+/// WAV, FLAC or MP3 file (each channel; mid and side of a stereo file) goes through the MP3 encoder's hybrid filterbank at all
+/// 576 alignments, and on the stream's granule grid a large share of the spectral lines falls to zero.  The verdict is a
+/// convention of that header, tried on this project's own encoder only and held to no other ancestry checker; finely coded
+/// streams, short-block passages, other codecs and audio processed after decoding are not found.  A module of its own, as
+/// [`dr`] is.  `tests/test_rust_ancestry_layout.py` compares these declarations with the header.
+pub mod ancestry {
+    use super::ffi::RgCtx;
+    use std::os::raw::{c_char, c_int};
+
+    pub const ANC_COMPLETE: u32 = 1;
+    pub const ANC_MP3_GRID: u32 = 2;
+    pub const ANC_MIDSIDE: u32 = 4;
+    pub const ANC_NONFINITE: u32 = 8;
+    pub const ANC_SHORT: u32 = 16;
+    pub const ANC_SILENT: u32 = 32;
+    pub const ANC_MAX_CHANNELS: usize = 8;
+    pub const ANC_MAX_VIEWS: usize = 10;
+    pub const ANC_ALIGNMENTS: u32 = 576;
+    pub const ANC_VIEW_MID: u32 = 8;
+    pub const ANC_VIEW_SIDE: u32 = 9;
+    pub const ANC_SEGMENTS: u32 = 16;
+    pub const ANC_GRANULES: u32 = 32;
+    /// `RG_ANC_NO_VIEW`: `best_view` of a record without a flagged view
+    pub const ANC_NO_VIEW: u32 = 0xFFFF_FFFF;
+    /// `RG_ANC_Z_MIN`, `RG_ANC_ISO_MIN`, `RG_ANC_ACTIVE_FLOOR`: what a zero in the options means
+    pub const ANC_Z_MIN: f64 = 19.01;
+    pub const ANC_ISO_MIN: f64 = 1.675;
+    pub const ANC_ACTIVE_FLOOR: f32 = 0.00462963;
+
+    #[derive(Clone, Copy, Debug)]
+    #[repr(C)]
+    /// `rg_ancestry_opts`: `segments` 0 = the whole plane as one segment; zeros in the last three mean the defaults; a null pointer means 16 segments of 32 granules
+    pub struct RgAncestryOpts {
+        pub segments: u32,
+        pub granules: u32,
+        pub z_min: f64,
+        pub iso_min: f64,
+        pub active_floor: f32,
+        pub reserved: u32,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_ancestry_view`
+    pub struct RgAncestryView {
+        pub ratio: f64,
+        pub second: f64,
+        pub p0: f64,
+        pub z: f64,
+        pub iso: f64,
+        pub small: u64,
+        pub active: u64,
+        pub active_total: u64,
+        pub offset: u32,
+        pub kind: u32,
+        pub flagged: u32,
+        pub nonfinite: u32,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_ancestry_result`
+    pub struct RgAncestryResult {
+        pub status: i32,
+        pub flags: u32,
+        pub frames: u64,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub format: u32,
+        pub dropped_frames: u32,
+        pub views: u32,
+        pub grid_offset: u32,
+        pub segments: u32,
+        pub granules: u32,
+        pub best_view: u32,
+        pub reserved: u32,
+        pub z: f64,
+        pub iso: f64,
+        pub view: [RgAncestryView; 10],
+    }
+
+    extern "C" {
+        pub fn rg_ancestry(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, opts: *const RgAncestryOpts, out: *mut RgAncestryResult) -> c_int;
+    }
+}
+
 /// The dynamic range (DR) figure of `include/mp3rgain_amd_dr.h`: per channel of every WAV, FLAC or MP3 file the mean square and
 /// the peak of every 3-second block, the loudest fifth of the blocks and the second-highest block peak, and from them the DR
 /// value.  The definitions follow the published description of the TT DR meter and are a convention of that header, unverified

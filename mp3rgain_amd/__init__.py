@@ -12,6 +12,8 @@ from .mp3verify import Mp3VerifyResult  # noqa: F401
 from .replaygain import (  # noqa: F401
     REPLAYGAIN_REFERENCE_DB,
     AlbumGainResult,
+    Ancestry,
+    AncestryView,
     Analyzer,
     AudioFileType,
     ChannelDynamicRange,
@@ -32,6 +34,9 @@ from .replaygain import (  # noqa: F401
     RipOffsetSignatures,
     Spectrum,
     album_dr,
+    ancestry_arena,
+    ancestry_from_record,
+    ancestry_kernel_shape,
     analyze_album,
     analyze_track,
     dr_arena,

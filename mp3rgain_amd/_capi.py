@@ -423,6 +423,63 @@ DR_SYMBOLS = [
     ("rg_dr_rate", _int, [_vp, _sz, _u64, _u32, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz), _P(_u64)]),
 ]
 
+# include/mp3rgain_amd_ancestry.h (lossy ancestry: an MP3 granule grid in PCM)
+ANC_COMPLETE, ANC_MP3_GRID, ANC_MIDSIDE, ANC_NONFINITE, ANC_SHORT, ANC_SILENT = 1, 2, 4, 8, 16, 32
+ANC_MAX_CHANNELS, ANC_MAX_VIEWS, ANC_ALIGNMENTS, ANC_VIEW_MID, ANC_VIEW_SIDE, ANC_NO_VIEW = 8, 10, 576, 8, 9, 0xFFFFFFFF
+ANC_SEGMENTS, ANC_GRANULES = 16, 32
+ANC_Z_MIN, ANC_ISO_MIN, ANC_ACTIVE_FLOOR = 19.01, 1.675, 0.00462963
+
+
+class AncestryOpts(C.Structure):  # rg_ancestry_opts
+    _fields_ = [("segments", C.c_uint32), ("granules", C.c_uint32), ("z_min", C.c_double), ("iso_min", C.c_double),
+                ("active_floor", C.c_float), ("reserved", C.c_uint32)]
+
+
+class AncestryView(C.Structure):  # rg_ancestry_view
+    _fields_ = [
+        ("ratio", C.c_double),
+        ("second", C.c_double),
+        ("p0", C.c_double),
+        ("z", C.c_double),
+        ("iso", C.c_double),
+        ("small", C.c_uint64),
+        ("active", C.c_uint64),
+        ("active_total", C.c_uint64),
+        ("offset", C.c_uint32),
+        ("kind", C.c_uint32),
+        ("flagged", C.c_uint32),
+        ("nonfinite", C.c_uint32),
+    ]
+
+
+class AncestryRecord(C.Structure):  # rg_ancestry_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("views", C.c_uint32),
+        ("grid_offset", C.c_uint32),
+        ("segments", C.c_uint32),
+        ("granules", C.c_uint32),
+        ("best_view", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("z", C.c_double),
+        ("iso", C.c_double),
+        ("view", AncestryView * ANC_MAX_VIEWS),
+    ]
+
+
+ANCESTRY_SYMBOLS = [
+    ("rg_ancestry", _int, [_vp, _P(C.c_char_p), _sz, _P(AncestryOpts), _P(AncestryRecord)]),
+    ("rg_ancestry_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _P(AncestryOpts), _vp, _sz, _P(AncestryRecord), _P(_u64)]),
+    ("rg_ancestry_kernel_shape", _int, [_P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_ancestry_rate", _int, [_vp, _sz, _u64, _P(AncestryOpts), _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_sz), _P(_dbl)]),
+]
+
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions
 NODE_OPEN = C.CFUNCTYPE(_vp, _int, _vp)
 NODE_CLOSE = C.CFUNCTYPE(None, _vp, _vp)
@@ -463,7 +520,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + ANCESTRY_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

@@ -76,6 +76,9 @@ class Options:  # src/main.rs:65-96
     min_cutoff: Optional[float] = None  # with --spectrum (--min-cutoff HZ): edges below this frequency are not reported
     dr: bool = False         # this façade only (--dr): the dynamic range (DR) figure per file, and the album's
     dr_top: Optional[int] = None  # with --dr (--dr-top PERMILLE): the share of the loudest blocks that count, in per mille
+    ancestry: bool = False   # this façade only (--ancestry): is this PCM a decoded MP3?  The granule grid, per file and view
+    ancestry_segments: Optional[int] = None  # with --ancestry (--ancestry-segments S): segments per file, 0 = the whole file
+    ancestry_granules: Optional[int] = None  # with --ancestry (--ancestry-granules G): granules per segment
     files: List[Path] = field(default_factory=list)
 
 
@@ -168,6 +171,12 @@ def parse_args(args: List[str], out, err) -> Options:
             o.dr = True
         elif arg == "--dr-top":
             o.dr_top = _parse_int(need("--dr-top", "--dr-top requires an argument"), "invalid per mille value", 32, signed=False)
+        elif arg == "--ancestry":  # not in the reference: a command of its own, like --stats
+            o.ancestry = True
+        elif arg == "--ancestry-segments":
+            o.ancestry_segments = _parse_int(need("--ancestry-segments", "--ancestry-segments requires an argument"), "invalid segment count", 32, signed=False)
+        elif arg == "--ancestry-granules":
+            o.ancestry_granules = _parse_int(need("--ancestry-granules", "--ancestry-granules requires an argument"), "invalid granule count", 32, signed=False)
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -289,6 +298,19 @@ def parse_args(args: List[str], out, err) -> Options:
                                         ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
         if others:
             raise CliError(f"--dr is a command of its own and cannot be combined with {', '.join(others)}")
+    if o.ancestry_segments is not None and not o.ancestry:
+        raise CliError("--ancestry-segments requires --ancestry")
+    if o.ancestry_granules is not None and not o.ancestry:
+        raise CliError("--ancestry-granules requires --ancestry")
+    if o.ancestry_granules == 0:
+        raise CliError("--ancestry-granules takes at least 1")
+    if o.ancestry:
+        others = [name for name, on in (("--verify", o.verify), ("--rip", o.rip), ("--stats", o.stats), ("--spectrum", o.spectrum), ("--dr", o.dr),
+                                        ("--r128", o.r128), ("-x", o.max_amplitude_only), ("-r", o.track_gain), ("-a", o.album_gain), ("-u", o.undo),
+                                        ("-g", o.gain_steps is not None), ("-l", o.channel_gain is not None),
+                                        ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
+        if others:
+            raise CliError(f"--ancestry is a command of its own and cannot be combined with {', '.join(others)}")
     return o
 
 
@@ -526,6 +548,8 @@ class Cli:
             return self.cmd_spectrum()
         if o.dr:
             return self.cmd_dr()
+        if o.ancestry:
+            return self.cmd_ancestry()
         if o.max_amplitude_only:
             return self.cmd_max_amplitude()
         if o.stored_tag_mode == "delete":
@@ -917,6 +941,66 @@ class Cli:
             self.p("album\t" + ("" if album is None else str(album)))
         elif len(o.files) > 1:
             self.p("album DR" + ("  none: no complete track" if album is None else f"{album}"))
+        return 1 if failed else 0
+
+    # ---- --ancestry (not in the reference): is this PCM a decoded MP3?  On the GPU ------------------------------------------
+    def cmd_ancestry(self) -> int:
+        """Every file decoded by the route the analysis uses and, on the first GPU (rg_ancestry), put through the MP3 encoder's
+        filterbank at all 576 alignments: per file `mp3 grid at +R (z, xISO[, mid/side])` or `no grid found` and the name, per
+        view the numbers.  The verdict is a convention of this project, tried on its own encoder's streams only; "no grid
+        found" proves nothing (finely coded streams, short blocks, other codecs, processed audio are not found).  A report:
+        exit status 1 only when a file fails or has dropped frames.  TSV, no header: a row per file `file, verdicts, grid
+        offset (empty without a grid), z, iso, best view, frames, sample rate, channels, segments, granules, dropped frames`, a
+        row per view `file, "view", name, offset, ratio, second, p0, z, iso, small, active, flagged, non-finite` (a failing
+        file: `file, error text`); an infinite iso is `inf`, and null in JSON."""
+        o = self.o
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            res = an.ancestry(o.files, o.ancestry_segments, o.ancestry_granules)
+        if self.talk:
+            self.p(f"mp3rgain ancestry scan of {len(o.files)} file(s): an MP3 granule grid at any of 576 alignments"
+                   " (a convention of this project, held to no other checker; no grid found is no proof of lossless origin)")
+            self.p()
+        num = lambda x: None if x in (float("inf"), float("-inf")) else x  # noqa: E731
+        results, failed = [], 0
+        for file, r in zip(o.files, res):
+            bad = r.error is not None or not r.complete
+            failed += bad
+            words = r.verdicts
+            if o.output_format == "json":
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                else:
+                    d.update(verdicts=words, mp3_grid=r.mp3_grid, grid_offset=r.grid_offset if r.mp3_grid else None, z=r.z, iso=num(r.iso),
+                             midside=r.midside, best_view=None if r.best_view is None else r.views[r.best_view].name, frames=r.frames,
+                             sample_rate=r.sample_rate, segments=r.segments, granules=r.granules, dropped_frames=r.dropped_frames, silent=r.silent,
+                             short=r.short, nonfinite=r.nonfinite, complete=r.complete,
+                             views=[{"view": v.name, "offset": v.offset, "ratio": v.ratio, "second": v.second, "p0": v.p0, "z": v.z, "iso": num(v.iso),
+                                     "small": v.small, "active": v.active, "active_total": v.active_total, "flagged": v.flagged,
+                                     "nonfinite": v.nonfinite} for v in r.views])
+                results.append(d)
+            elif o.output_format == "tsv":
+                if r.error is not None:
+                    self.p(f"{_name(file)}\t{r.error}")
+                    continue
+                self.p(f"{_name(file)}\t{','.join(words)}\t{r.grid_offset if r.mp3_grid else ''}\t{r.z:.2f}\t{r.iso:.3f}\t"
+                       f"{'' if r.best_view is None else r.views[r.best_view].name}\t{r.frames}\t{r.sample_rate}\t{sum(1 for v in r.views if v.kind < 8)}\t"
+                       f"{r.segments}\t{r.granules}\t{r.dropped_frames}")
+                for v in r.views:
+                    self.p(f"{_name(file)}\tview\t{v.name}\t{v.offset}\t{v.ratio:.5f}\t{v.second:.5f}\t{v.p0:.5f}\t{v.z:.2f}\t{v.iso:.3f}\t{v.small}\t"
+                           f"{v.active}\t{int(v.flagged)}\t{v.nonfinite}")
+            elif r.error is not None:
+                self.e(f"{_name(file)} - {r.error}")
+            else:
+                notes = [w for w in words if w not in ("ok", "mp3-grid", "mid/side")] + ([f"{r.dropped_frames} frames dropped"] if r.dropped_frames else [])
+                self.p(f"{r.summary}   {_name(file)}" + (f"  [{', '.join(notes)}]" if notes else ""))
+                if not o.quiet:
+                    for v in r.views:
+                        self.p(f"    {v.name}: +{v.offset}  {100.0 * v.ratio:.1f} % small (next {100.0 * v.second:.1f} %, others {100.0 * v.p0:.1f} %)"
+                               f"  z {v.z:.1f}  x{v.iso:.2f}" + ("  *" if v.flagged else "") + (f"  non-finite {v.nonfinite}" if v.nonfinite else ""))
+        if o.output_format == "json":
+            _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
         return 1 if failed else 0
 
     # ---- find_max_amplitude, src/lib.rs:1174-1199 ------------------------------------------------------------
@@ -1576,6 +1660,16 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "            sample_rate, block_frames, dropped_frames, verdicts, channels[dr, peak_db, rms_db, top_ms, mean_square, peak,",
         "            peak2, blocks, top_blocks, nonfinite], album_dr.  Exit status 1 only for a file that fails or has dropped frames",
         "--dr-top <permille>  With --dr: the share of the loudest blocks that count (default 200)",
+        "--ancestry  Lossy ancestry scan on the GPU (WAV, FLAC, MP3): is this PCM a decoded MP3?  The audio goes through the MP3",
+        "            encoder's filterbank at all 576 alignments, per channel and, for stereo, mid and side; on the stream's granule",
+        "            grid a large share of the lines falls to zero.  Per file `mp3 grid at +R (z, xISO[, mid/side])` or `no grid",
+        "            found`, per view the numbers.  A convention of this project, tried on its own encoder's streams and held to no",
+        "            other checker; not found: finely coded streams (a mono stream of 320 kb/s), short-block passages, AAC / Vorbis /",
+        "            Opus, audio resampled or re-dithered after decoding.  JSON fields: mp3_grid, grid_offset, z, iso, midside,",
+        "            best_view, segments, granules, dropped_frames, verdicts, views[view, offset, ratio, second, p0, z, iso, small,",
+        "            active, active_total, flagged, nonfinite].  Exit status 1 only for a file that fails or has dropped frames",
+        "--ancestry-segments <S>  With --ancestry: segments per file, spread evenly (default 16; 0 = the whole file)",
+        "--ancestry-granules <G>  With --ancestry: granules of 576 samples per segment (default 32)",
         "-v          Show version",
         "-h          Show this help",
     ):

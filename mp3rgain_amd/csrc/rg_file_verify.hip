@@ -5,6 +5,7 @@
 // and the record of a file that failed holds nothing else.
 #include <algorithm>
 
+#include "rg_ancestry.h"
 #include "rg_dr.h"
 #include "rg_files.h"
 #include "rg_flac_md5.h"
@@ -478,6 +479,92 @@ extern "C" int rg_dynamic_range(rg_ctx *c, const char *const *paths, size_t n, c
     if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
     if (n) memset(out, 0, n * sizeof *out);
     return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return dr_group(c, paths, first, cnt, o, out); });
+}
+
+// ---- rg_ancestry ----------------------------------------------------------------------------------------------------------
+// one group of the call: rg_pcm_stats' route and screen, and the kernels of rg_ancestry.hip over the planes where the decode
+// left them, on the stream the decode ran on, so tuning key 14 cannot show in the records.  The verdict is host arithmetic on
+// the counts that come back (rg_anc_fill).
+static int ancestry_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_ancestry_opts &o, rg_ancestry_result *out) {
+    out += first;
+    FileGroup g(c, paths, first, n);
+    int rc = g.load(LoadOpts{-1, false});
+    if (rc != RG_OK) return rc;
+    const auto mark = mark_record(g, out);
+    const auto refused = [&](size_t i, const std::string &why) { return "No ancestry scan (" + why + "): " + g.paths[i]; };
+    // a WAV stream the staging cannot lay out, or anything of more than 8 channels, fails alone and in front of the staging
+    const auto screen = [&](size_t i, std::string *text) -> int {
+        uint32_t channels = g.in[i].channels;
+        if (g.in[i].kind == LoadedAudio::Wav) {
+            rg_wav_info w;
+            if (rg_wav_parse(g.in[i].wav.data(), g.in[i].wav.size(), &w) != RG_OK) {
+                *text = std::string("Failed to probe format: ") + g.paths[i];
+                return RG_ERR_FORMAT;
+            }
+            if (wav_kind(w) < 0) {
+                *text = refused(i, std::to_string(w.bits_per_sample) + "-bit " + (w.sample_format == 3 ? "float" : "samples of format " + std::to_string(w.sample_format)) +
+                                       ", not 8, 16, 24 or 32-bit integer or 32-bit float PCM");
+                return RG_ERR_FORMAT;
+            }
+            channels = w.channels;
+        }
+        if (channels <= RG_ANC_MAX_CHANNELS) return RG_OK;
+        *text = refused(i, std::to_string(channels) + " channels, more than " + std::to_string(RG_ANC_MAX_CHANNELS));
+        return RG_ERR_FORMAT;
+    };
+    const auto work = [&]() -> int {
+        const std::vector<LoadedAudio> &in = g.in;
+        std::vector<RgAncView> views(g.slot.size() * RG_ANC_MAX_VIEWS + 1);
+        std::vector<RgAncJob> jobs;
+        struct Rec {
+            size_t k, view;
+            uint32_t n_views, S, G, dropped;
+        };
+        std::vector<Rec> recs;
+        size_t n_views = 0;
+        for (size_t k = 0; k < g.slot.size(); ++k) {
+            const size_t i = g.slot[k];
+            const LoadedAudio &la = in[k];
+            uint32_t lost = 0;
+            if (la.kind == LoadedAudio::Flac) {
+                lost = g.counts[k].dropped;
+            } else if (la.kind != LoadedAudio::Wav) {  // an MPEG stream: the frames the route dropped, as rg_mp3_verify counts them
+                const uint32_t spf = g.descs[k].sample_rate >= 32000 ? 1152 : 576;
+                lost = la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
+            }
+            char err[256] = "";
+            Rec r{k, n_views, 0, 0, 0, lost};
+            const int prc = rg_anc_track_views(i, g.descs[k], g.arena_bytes, &views[n_views], &r.n_views, err, sizeof err);
+            if (prc == RG_ERR_FORMAT) {
+                mark(i, RG_ERR_FORMAT, refused(i, err));
+                continue;
+            }
+            if (prc != RG_OK) return rg_set_err(c, prc, "%s", err);
+            for (uint32_t v = 0; v < r.n_views; ++v) rg_anc_jobs(g.descs[k].frames, o, (uint32_t)(n_views + v), &jobs, &r.S, &r.G);
+            recs.push_back(r);
+            n_views += r.n_views;
+        }
+        if (recs.empty()) return RG_OK;
+        const size_t per_view = 2 * RG_ANC_ALIGNMENTS;
+        std::vector<uint64_t> cnt(n_views * per_view), nonfinite(n_views);
+        const int drc = rg_anc_device(c, c->d_arena.p, views.data(), n_views, jobs, o.active_floor, cnt.data(), nonfinite.data(), c->file_stream());
+        if (drc != RG_OK) return drc;
+        for (const Rec &r : recs)
+            rg_anc_fill(g.descs[r.k], o, r.S, r.G, r.dropped, r.n_views, &views[r.view], &cnt[r.view * per_view], &nonfinite[r.view], &out[g.slot[r.k]]);
+        return RG_OK;
+    };
+    g.want_counts = true;
+    return g.run(screen, mark, work);
+}
+
+extern "C" int rg_ancestry(rg_ctx *c, const char *const *paths, size_t n, const rg_ancestry_opts *opts, rg_ancestry_result *out) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    rg_ancestry_opts o;
+    char err[256] = "";
+    const int orc = rg_anc_options(opts, &o, err, sizeof err);
+    if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
+    if (n) memset(out, 0, n * sizeof *out);
+    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return ancestry_group(c, paths, first, cnt, o, out); });
 }
 
 // ---- rg_spectrum ----------------------------------------------------------------------------------------------------------

@@ -439,6 +439,132 @@ def album_dr(records) -> Optional[int]:
     return int(round(sum(vals) / len(vals))) if vals else None
 
 
+def _ancestry_opts(segments, granules, z_min, iso_min, active_floor):
+    """rg_ancestry_opts, or NULL (the header's defaults) when all are None.  segments = 0 is the whole plane as one segment."""
+    if segments is None and granules is None and z_min is None and iso_min is None and active_floor is None:
+        return None
+    return C.byref(_capi.AncestryOpts(_capi.ANC_SEGMENTS if segments is None else int(segments),
+                                      _capi.ANC_GRANULES if granules is None else int(granules),
+                                      0.0 if z_min is None else float(z_min), 0.0 if iso_min is None else float(iso_min),
+                                      0.0 if active_floor is None else float(active_floor), 0))
+
+
+def ancestry_arena(ctx, route: int, descs, arena, segments=None, granules=None, z_min=None, iso_min=None, active_floor=None, counts=True):
+    """rg_ancestry_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> ([AncestryRecord], counts),
+    counts a uint64 array [track][view][0 = small, 1 = active][576] (None when `counts` is false)."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    out = (_capi.AncestryRecord * max(1, n))()
+    cnt = np.zeros((max(1, n), _capi.ANC_MAX_VIEWS, 2, _capi.ANC_ALIGNMENTS), dtype=np.uint64) if counts else None
+    rc = L.rg_ancestry_arena(ctx, int(route), n, d, _ancestry_opts(segments, granules, z_min, iso_min, active_floor),
+                             arena.ctypes.data if arena.size else None, arena.size, out,
+                             cnt.ctypes.data_as(C.POINTER(C.c_uint64)) if counts else None)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return list(out[:n]), (cnt[:n] if counts else None)
+
+
+def ancestry_kernel_shape():
+    """rg_ancestry_kernel_shape -> (phases, tile_granules, lanes, lds_bytes)."""
+    a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc = _capi.load().rg_ancestry_kernel_shape(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    if rc != 0:
+        raise ReplayGainError(rc, "rg_ancestry_kernel_shape")
+    return a.value, b.value, c.value, d.value
+
+
+@dataclass
+class AncestryView:
+    """One view of an Ancestry (rg_ancestry_view, include/mp3rgain_amd_ancestry.h)."""
+    kind: int                # the channel's index, 8 = mid, 9 = side
+    offset: int              # r*: the alignment with the largest share of small lines
+    ratio: float             # small / active there
+    second: float            # the next-best ratio
+    p0: float                # the pooled ratio of all other alignments
+    z: float
+    iso: float               # ratio / second
+    small: int
+    active: int
+    active_total: int
+    flagged: bool
+    nonfinite: int
+
+    @property
+    def name(self) -> str:
+        return {_capi.ANC_VIEW_MID: "mid", _capi.ANC_VIEW_SIDE: "side"}.get(self.kind, f"ch{self.kind}")
+
+
+@dataclass
+class Ancestry:
+    """One file of Analyzer.ancestry (rg_ancestry_result).  The verdict is a convention of include/mp3rgain_amd_ancestry.h,
+    tried on this project's own encoder only and held to no other ancestry checker; "no grid found" proves nothing."""
+    frames: int
+    sample_rate: int
+    format: int
+    dropped_frames: int
+    flags: int
+    segments: int
+    granules: int
+    grid_offset: int
+    best_view: Optional[int]
+    z: float
+    iso: float
+    views: list              # [AncestryView]
+    error: Optional["ReplayGainError"] = None  # why there are no numbers; every other field is then zero
+
+    @property
+    def complete(self) -> bool:
+        return bool(self.flags & _capi.ANC_COMPLETE)
+
+    @property
+    def mp3_grid(self) -> bool:
+        return bool(self.flags & _capi.ANC_MP3_GRID)
+
+    @property
+    def midside(self) -> bool:
+        return bool(self.flags & _capi.ANC_MIDSIDE)
+
+    @property
+    def nonfinite(self) -> bool:
+        return bool(self.flags & _capi.ANC_NONFINITE)
+
+    @property
+    def short(self) -> bool:
+        return bool(self.flags & _capi.ANC_SHORT)
+
+    @property
+    def silent(self) -> bool:
+        return bool(self.flags & _capi.ANC_SILENT)
+
+    @property
+    def verdicts(self) -> list:
+        """The flags as words, in a fixed order; ["ok"] when there is nothing to report."""
+        names = (("mp3-grid", self.mp3_grid), ("mid/side", self.midside), ("silent", self.silent), ("short", self.short),
+                 ("nonfinite", self.nonfinite), ("incomplete", self.error is None and not self.complete))
+        return [n for n, on in names if on] or ["ok"]
+
+    @property
+    def summary(self) -> str:
+        """`mp3 grid at +R (z 30.1, x2.35, mid/side)` or `no grid found`."""
+        if not self.mp3_grid:
+            return "no grid found"
+        return f"mp3 grid at +{self.grid_offset} (z {self.z:.1f}, x{self.iso:.2f}{', mid/side' if self.midside else ''})"
+
+
+def ancestry_from_record(r, error=None) -> Ancestry:
+    """An Ancestry from an rg_ancestry_result."""
+    views = []
+    for k in range(int(r.views)):
+        v = r.view[k]
+        views.append(AncestryView(int(v.kind), int(v.offset), float(v.ratio), float(v.second), float(v.p0), float(v.z), float(v.iso),
+                                  int(v.small), int(v.active), int(v.active_total), bool(v.flagged), int(v.nonfinite)))
+    best = None if int(r.best_view) == _capi.ANC_NO_VIEW or error is not None else int(r.best_view)
+    return Ancestry(int(r.frames), int(r.sample_rate), int(r.format), int(r.dropped_frames), int(r.flags), int(r.segments), int(r.granules),
+                    int(r.grid_offset), best, float(r.z), float(r.iso), views, error)
+
+
 def _spectrum_opts(edge_db, min_cutoff_hz):
     """rg_spectrum_opts, or NULL (the header's defaults) when both are None."""
     if edge_db is None and min_cutoff_hz is None:
@@ -1410,6 +1536,42 @@ class Analyzer:
     @staticmethod
     def dr_kernel_shape(fmt: int):
         return dr_kernel_shape(fmt)
+
+    def _ancestry_call(self, files, segments, granules, z_min, iso_min, active_floor):
+        n = len(files)
+        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        out = (_capi.AncestryRecord * max(1, n))()
+        self._check(self._lib.rg_ancestry(self._ctx, paths, n, _ancestry_opts(segments, granules, z_min, iso_min, active_floor), out))
+        return out
+
+    def ancestry(self, files, segments=None, granules=None, z_min=None, iso_min=None, active_floor=None) -> list:
+        """rg_ancestry: `files` (WAV, FLAC or MPEG Layer III) decoded by the route the analysis uses and, from the PCM where it
+        lies on this GPU, put through the MP3 encoder's hybrid filterbank at all 576 alignments, per channel (and mid and side of
+        a stereo file): the alignment at which the most lines fall to zero, how far it stands out, and whether that is an MP3
+        granule grid -> [Ancestry].  A file that takes no part carries its ReplayGainError in `.error`."""
+        out = self._ancestry_call(files, segments, granules, z_min, iso_min, active_floor)
+        res = []
+        for i in range(len(files)):
+            err = None
+            if out[i].status != 0:
+                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
+            res.append(ancestry_from_record(out[i], err))
+        return res
+
+    def ancestry_raw(self, files, segments=None, granules=None, z_min=None, iso_min=None, active_floor=None) -> bytes:
+        """ancestry's rg_ancestry_result array as the C call left it (tests compare routes byte for byte)."""
+        out = self._ancestry_call(files, segments, granules, z_min, iso_min, active_floor)
+        return bytes(out)[:len(files) * C.sizeof(_capi.AncestryRecord)]
+
+    def ancestry_arena(self, route: int, descs, arena, segments=None, granules=None, z_min=None, iso_min=None, active_floor=None, counts=True):
+        """rg_ancestry_arena, the seam of the ancestry kernels: the tracks `descs` describe in the host arena `arena` ->
+        ([AncestryRecord], counts); route 0 = the serial host twin, route 1 = the arena copied to this GPU and the kernels,
+        route 2 = the kernels' cutting on the host."""
+        return ancestry_arena(self._ctx, route, descs, arena, segments, granules, z_min, iso_min, active_floor, counts)
+
+    @staticmethod
+    def ancestry_kernel_shape():
+        return ancestry_kernel_shape()
 
     def _spectrum_call(self, files, edge_db, min_cutoff_hz, bands):
         n = len(files)
