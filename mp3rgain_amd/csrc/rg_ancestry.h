@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/mp3rgain_amd_ancestry.h"
+#include "rg_pcm_plane.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -59,7 +60,6 @@ struct RgAncJob {         // one tile of one segment of one view; 32 workgroups,
 RG_ANC_HD float rg_anc_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
 // ---- samples ---------------------------------------------------------------------------------------------------------------
-RG_ANC_HD uint32_t rg_anc_bps(uint32_t format) { return format == RG_FMT_S16_PLANAR ? 2u : 4u; }
 RG_ANC_HD bool rg_anc_nonfinite(uint32_t bits) { return (bits & 0x7F800000u) == 0x7F800000u; }
 RG_ANC_HD float rg_anc_plane_sample(const unsigned char *arena, uint64_t off, uint32_t format, uint32_t k) {
     if (format == RG_FMT_S16_PLANAR) {

@@ -23,6 +23,7 @@
 
 #include "rg_ctx.h"
 #include "rg_ancestry.h"
+#include "rg_pcm_seam.h"
 
 __global__ __launch_bounds__(RG_ANC_LANES) void rg_anc_tile_kernel(const unsigned char *__restrict__ arena, const RgAncTables *__restrict__ tables,
                                                                    const RgAncView *__restrict__ views, const RgAncJob *__restrict__ jobs, float floor_,
@@ -229,52 +230,46 @@ int rg_anc_device(rg_ctx *c, const unsigned char *d_arena, const RgAncView *view
 // ---- test seam (include/mp3rgain_amd_ancestry.h) -----------------------------------------------------------------------------
 extern "C" int rg_ancestry_arena(void *ctx, int route, size_t n, const rg_track_desc *descs, const rg_ancestry_opts *opts, const void *arena,
                                  size_t arena_bytes, rg_ancestry_result *out, uint64_t *counts) {
-    rg_ctx *c = static_cast<rg_ctx *>(ctx);
-    char err[256] = "";
-    if (!c && route == 1) return RG_ERR_INVALID_ARG;  // the host routes need no context (their error text: rg_last_error(NULL))
-    if (route < 0 || route > 2)
-        return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_ancestry_arena: route %d (0 = serial host twin, 1 = kernels, 2 = the kernels' cutting on the host)", route);
-    if (n && (!descs || !out || (arena_bytes && !arena))) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_ancestry_arena: null array");
-    try {
-        if (route != 1) {
-            const int rc = rg_anc_arena_host(route, n, descs, opts, arena, arena_bytes, out, counts, err, sizeof err);
-            return rc == RG_OK ? RG_OK : rg_set_err(c, rc, "%s", err);
-        }
-        rg_ancestry_opts o;
-        int rc = rg_anc_options(opts, &o, err, sizeof err);
-        if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
-        std::vector<RgAncView> views(n * RG_ANC_MAX_VIEWS + 1);
-        std::vector<RgAncJob> jobs;
-        std::vector<uint32_t> first(n + 1), nv(n + 1), S(n + 1), G(n + 1);
-        size_t n_views = 0;
-        for (size_t i = 0; i < n; ++i) {
-            rc = rg_anc_track_views(i, descs[i], arena_bytes, &views[n_views], &nv[i], err, sizeof err);
-            if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
-            first[i] = (uint32_t)n_views;
-            for (uint32_t v = 0; v < nv[i]; ++v) rg_anc_jobs(descs[i].frames, o, (uint32_t)n_views + v, &jobs, &S[i], &G[i]);
-            n_views += nv[i];
-        }
-        rc = rg_bind_device(c);
+    rg_ancestry_opts o;
+    std::vector<RgAncView> views;
+    std::vector<RgAncJob> jobs;
+    struct Track {
+        uint32_t first, nv, S, G;  // its first view and how many, its cut
+    };
+    std::vector<Track> tracks;
+    size_t n_views = 0;
+    const auto host = [&](char *err, size_t err_len) { return rg_anc_arena_host(route, n, descs, opts, arena, arena_bytes, out, counts, err, err_len); };
+    const auto plan = [&](char *err, size_t err_len) -> int {
+        int rc = rg_anc_options(opts, &o, err, err_len);
         if (rc != RG_OK) return rc;
-        RG_HIP(c, rg_sync_slots(c, c->n_slots));
-        RG_HIP(c, c->d_arena.reserve(((arena_bytes + 15) & ~(size_t)15) + 16));
-        hipStream_t s = c->slots[0].stream;
-        if (arena_bytes) RG_HIP(c, hipMemcpyAsync(c->d_arena.p, arena, arena_bytes, hipMemcpyHostToDevice, s));
+        views = std::vector<RgAncView>(n * RG_ANC_MAX_VIEWS + 1);
+        tracks = std::vector<Track>(n + 1);
+        for (size_t i = 0; i < n; ++i) {
+            Track &t = tracks[i];
+            rc = rg_anc_track_views(i, descs[i], arena_bytes, &views[n_views], &t.nv, err, err_len);
+            if (rc != RG_OK) return rc;
+            t.first = (uint32_t)n_views;
+            for (uint32_t v = 0; v < t.nv; ++v) rg_anc_jobs(descs[i].frames, o, (uint32_t)n_views + v, &jobs, &t.S, &t.G);
+            n_views += t.nv;
+        }
+        return RG_OK;
+    };
+    const auto device = [&](rg_ctx *c, hipStream_t s) -> int {
         const size_t per_view = 2 * RG_ANC_ALIGNMENTS;
         std::vector<uint64_t> cnt((n_views ? n_views : 1) * per_view), nonfinite(n_views ? n_views : 1);
-        rc = rg_anc_device(c, c->d_arena.p, views.data(), n_views, jobs, o.active_floor, cnt.data(), nonfinite.data(), s);
+        const int rc = rg_anc_device(c, c->d_arena.p, views.data(), n_views, jobs, o.active_floor, cnt.data(), nonfinite.data(), s);
         if (rc != RG_OK) return rc;
         for (size_t i = 0; i < n; ++i) {
-            rg_anc_fill(descs[i], o, S[i], G[i], 0, nv[i], &views[first[i]], &cnt[first[i] * per_view], &nonfinite[first[i]], &out[i]);
+            const Track &t = tracks[i];
+            rg_anc_fill(descs[i], o, t.S, t.G, 0, t.nv, &views[t.first], &cnt[t.first * per_view], &nonfinite[t.first], &out[i]);
             if (counts) {
                 memset(counts + i * RG_ANC_MAX_VIEWS * per_view, 0, RG_ANC_MAX_VIEWS * per_view * sizeof(uint64_t));
-                memcpy(counts + i * RG_ANC_MAX_VIEWS * per_view, &cnt[first[i] * per_view], nv[i] * per_view * sizeof(uint64_t));
+                memcpy(counts + i * RG_ANC_MAX_VIEWS * per_view, &cnt[t.first * per_view], t.nv * per_view * sizeof(uint64_t));
             }
         }
         return RG_OK;
-    } catch (const std::bad_alloc &) {
-        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
-    }
+    };
+    return rg_pcm_arena_seam(ctx, route, "rg_ancestry_arena", "the kernels' cutting", n, descs, out, arena, arena_bytes, host, plan, device);
 }
 
 // ---- measurement hook (tools/ancestry_rate.py) -------------------------------------------------------------------------------

@@ -59,32 +59,14 @@ int rg_anc_options(const rg_ancestry_opts *opts, rg_ancestry_opts *out, char *er
 }
 
 int rg_anc_track_views(size_t i, const rg_track_desc &t, size_t arena_bytes, RgAncView *views, uint32_t *n_views, char *err, size_t err_len) {
-    if (t.format != RG_FMT_F32_PLANAR && t.format != RG_FMT_S16_PLANAR && t.format != RG_FMT_S32_PLANAR) {
-        snprintf(err, err_len, "track %zu: format %u is not a planar PCM format", i, (unsigned)t.format);
-        return RG_ERR_FORMAT;
-    }
-    if (t.channels < 1 || t.channels > RG_ANC_MAX_CHANNELS) {
-        snprintf(err, err_len, "track %zu: %u channel(s), the ancestry scan takes 1 to %u", i, (unsigned)t.channels, RG_ANC_MAX_CHANNELS);
-        return RG_ERR_FORMAT;
-    }
-    if (t.frames >= ((uint64_t)1 << 32)) {
-        snprintf(err, err_len, "track %zu: %llu frames, the ancestry scan takes fewer than 2^32", i, (unsigned long long)t.frames);
-        return RG_ERR_FORMAT;
-    }
-    const uint32_t bps = rg_anc_bps(t.format);
-    if (t.offset_bytes % bps) {
-        snprintf(err, err_len, "track %zu: offset %llu is not sample-aligned", i, (unsigned long long)t.offset_bytes);
-        return RG_ERR_INVALID_ARG;
-    }
-    if (t.offset_bytes > arena_bytes || t.frames > (arena_bytes - t.offset_bytes) / ((size_t)bps * t.channels)) {
-        snprintf(err, err_len, "track %zu: its planes reach beyond the arena (%zu bytes)", i, arena_bytes);
-        return RG_ERR_INVALID_ARG;
-    }
+    int rc = rg_pcm_check_format(i, t, RG_ANC_MAX_CHANNELS, "the ancestry scan takes", err, err_len);
+    if (rc == RG_OK) rc = rg_pcm_check_place(i, t, arena_bytes, err, err_len);
+    if (rc != RG_OK) return rc;
     uint32_t n = 0;
     for (uint32_t c = 0; c < t.channels; ++c) {
         RgAncView &v = views[n++];
         memset(&v, 0, sizeof v);
-        v.off_a = v.off_b = t.offset_bytes + (uint64_t)c * t.frames * bps;
+        v.off_a = v.off_b = rg_pcm_plane_off(t, c);
         v.n = (uint32_t)t.frames;
         v.format = t.format;
     }
@@ -114,11 +96,7 @@ void rg_anc_jobs(uint64_t N, const rg_ancestry_opts &o, uint32_t view, std::vect
 uint64_t rg_anc_count_nonfinite(const unsigned char *arena, const RgAncView &v) {
     if (v.format != RG_FMT_F32_PLANAR || v.mix) return 0;
     uint64_t cnt = 0;
-    for (uint32_t k = 0; k < v.n; ++k) {
-        uint32_t u;
-        memcpy(&u, arena + v.off_a + 4ull * k, 4);
-        cnt += rg_anc_nonfinite(u) ? 1u : 0u;
-    }
+    for (uint32_t k = 0; k < v.n; ++k) cnt += rg_anc_nonfinite(rg_pcm_raw_at(arena + v.off_a, v.format, k)) ? 1u : 0u;
     return cnt;
 }
 
@@ -248,16 +226,9 @@ void rg_anc_fill(const rg_track_desc &t, const rg_ancestry_opts &o, uint32_t S, 
 
 int rg_anc_arena_host(int route, size_t n, const rg_track_desc *descs, const rg_ancestry_opts *opts, const void *arena, size_t arena_bytes,
                       rg_ancestry_result *out, uint64_t *counts, char *err, size_t err_len) {
-    if (route != 0 && route != 2) {
-        snprintf(err, err_len, "rg_ancestry_arena: route %d is not a host route (0 = serial twin, 2 = the kernels' cutting)", route);
-        return RG_ERR_INVALID_ARG;
-    }
-    if (n && (!descs || !out || (arena_bytes && !arena))) {
-        snprintf(err, err_len, "rg_ancestry_arena: null array");
-        return RG_ERR_INVALID_ARG;
-    }
     rg_ancestry_opts o;
-    int rc = rg_anc_options(opts, &o, err, err_len);
+    int rc = rg_pcm_check_host_route("rg_ancestry_arena", "the kernels' cutting", route, n, descs, out, arena, arena_bytes, err, err_len);
+    if (rc == RG_OK) rc = rg_anc_options(opts, &o, err, err_len);
     if (rc != RG_OK) return rc;
     std::vector<RgAncView> views(n * RG_ANC_MAX_VIEWS + 1);
     std::vector<uint32_t> nv(n + 1);

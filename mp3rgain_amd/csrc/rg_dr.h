@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "../../include/mp3rgain_amd_dr.h"
+#include "rg_pcm_plane.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -60,9 +61,8 @@ struct RgDrPlaneOut {       // the raw numbers of a plane: the same bits on ever
 };  // 40 bytes
 
 // ---- samples ---------------------------------------------------------------------------------------------------------------
-RG_DR_HD uint32_t rg_dr_bps(uint32_t format) { return format == RG_FMT_S16_PLANAR ? 2u : 4u; }
-RG_DR_HD uint32_t rg_dr_step_samples(uint32_t format) { return 16u / rg_dr_bps(format); }
-RG_DR_HD uint32_t rg_dr_piece_samples(uint32_t format) { return RG_DR_PIECE_BYTES / rg_dr_bps(format); }
+RG_DR_HD uint32_t rg_dr_step_samples(uint32_t format) { return 16u / rg_pcm_bps(format); }
+RG_DR_HD uint32_t rg_dr_piece_samples(uint32_t format) { return RG_DR_PIECE_BYTES / rg_pcm_bps(format); }
 // s^2
 RG_DR_HD double rg_dr_scale2(uint32_t format) {
     return format == RG_FMT_S16_PLANAR ? 1073741824.0 : (format == RG_FMT_S32_PLANAR ? 4611686018427387904.0 : 70368744177664.0);

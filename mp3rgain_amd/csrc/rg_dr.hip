@@ -28,6 +28,7 @@
 
 #include "rg_ctx.h"
 #include "rg_dr.h"
+#include "rg_pcm_seam.h"
 #include "rg_stats.h"
 
 // sample j of a vector as the stored pattern, S16 sign-extended
@@ -257,35 +258,24 @@ int rg_dr_device(rg_ctx *c, const unsigned char *d_arena, RgDrPlane *planes, siz
 // ---- test seam (include/mp3rgain_amd_dr.h) ---------------------------------------------------------------------------------
 extern "C" int rg_dr_arena(void *ctx, int route, size_t n, const rg_track_desc *descs, const rg_dr_opts *opts, const void *arena, size_t arena_bytes,
                            rg_dr_result *out) {
-    rg_ctx *c = static_cast<rg_ctx *>(ctx);
-    char err[256] = "";
-    if (!c && route == 1) return RG_ERR_INVALID_ARG;  // the host routes need no context (their error text: rg_last_error(NULL))
-    if (route < 0 || route > 2)
-        return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_dr_arena: route %d (0 = serial host twin, 1 = kernels, 2 = folded on the host)", route);
-    if (n && (!descs || !out || (arena_bytes && !arena))) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_dr_arena: null array");
-    try {
-        if (route != 1) {
-            const int rc = rg_dr_arena_host(route, n, descs, opts, arena, arena_bytes, out, err, sizeof err);
-            return rc == RG_OK ? RG_OK : rg_set_err(c, rc, "%s", err);
-        }
+    std::vector<RgDrPlane> planes;
+    size_t n_planes = 0;
+    const auto host = [&](char *err, size_t err_len) { return rg_dr_arena_host(route, n, descs, opts, arena, arena_bytes, out, err, err_len); };
+    const auto plan = [&](char *err, size_t err_len) -> int {
         rg_dr_opts o;
-        int rc = rg_dr_options(opts, &o, err, sizeof err);
-        if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
-        std::vector<RgDrPlane> planes(n * RG_DR_MAX_CHANNELS + 1);
-        size_t n_planes = 0;
+        int rc = rg_dr_options(opts, &o, err, err_len);
+        if (rc != RG_OK) return rc;
+        planes = std::vector<RgDrPlane>(n * RG_DR_MAX_CHANNELS + 1);
         for (size_t i = 0; i < n; ++i) {
-            rc = rg_dr_track_planes(i, descs[i], o, false, arena_bytes, &planes[n_planes], err, sizeof err);
-            if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
+            rc = rg_dr_track_planes(i, descs[i], o, false, arena_bytes, &planes[n_planes], err, err_len);
+            if (rc != RG_OK) return rc;
             n_planes += descs[i].channels;
         }
-        rc = rg_bind_device(c);
-        if (rc != RG_OK) return rc;
-        RG_HIP(c, rg_sync_slots(c, c->n_slots));
-        RG_HIP(c, c->d_arena.reserve(((arena_bytes + 15) & ~(size_t)15) + 16));  // whole 16-byte words: the aligned cover
-        hipStream_t s = c->slots[0].stream;
-        if (arena_bytes) RG_HIP(c, hipMemcpyAsync(c->d_arena.p, arena, arena_bytes, hipMemcpyHostToDevice, s));
+        return RG_OK;
+    };
+    const auto device = [&](rg_ctx *c, hipStream_t s) -> int {
         std::vector<RgDrPlaneOut> po(n_planes ? n_planes : 1);
-        rc = rg_dr_device(c, c->d_arena.p, planes.data(), n_planes, po.data(), s);
+        const int rc = rg_dr_device(c, c->d_arena.p, planes.data(), n_planes, po.data(), s);
         if (rc != RG_OK) return rc;
         size_t at = 0;
         for (size_t i = 0; i < n; ++i) {
@@ -293,9 +283,8 @@ extern "C" int rg_dr_arena(void *ctx, int route, size_t n, const rg_track_desc *
             at += descs[i].channels;
         }
         return RG_OK;
-    } catch (const std::bad_alloc &) {
-        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
-    }
+    };
+    return rg_pcm_arena_seam(ctx, route, "rg_dr_arena", "folded", n, descs, out, arena, arena_bytes, host, plan, device);
 }
 
 // ---- measurement hook (tools/dr_rate.py) -----------------------------------------------------------------------------------
@@ -355,7 +344,7 @@ extern "C" int rg_dr_rate(void *ctx, size_t n, uint64_t frames, uint32_t format,
         return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_dr_rate: bad arguments");
     int rc = rg_bind_device(c);
     if (rc != RG_OK) return rc;
-    const uint32_t bps = rg_dr_bps(format);
+    const uint32_t bps = rg_pcm_bps(format);
     const size_t track_bytes = (size_t)frames * 2 * bps, stride = (track_bytes + 15) & ~(size_t)15, total = n * stride;
     if (bytes) *bytes = (uint64_t)n * track_bytes;
     unsigned char *d_arena = nullptr, *d = nullptr;
@@ -378,7 +367,7 @@ extern "C" int rg_dr_rate(void *ctx, size_t n, uint64_t frames, uint32_t format,
             t.format = (uint16_t)format;
             uint32_t reported;
             if (rg_dr_track_planes(i, t, o, false, total, &planes[2 * i], err, sizeof err) != RG_OK ||
-                rg_stats_track_planes(i, t, rg_stats_width(format), total, &splanes[2 * i], &reported, err, sizeof err) != RG_OK)
+                rg_stats_track_planes(i, t, rg_pcm_width(format), total, &splanes[2 * i], &reported, err, sizeof err) != RG_OK)
                 return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_dr_rate: %s", err);
         }
         uint64_t fmt_piece[4], n_blocks;

@@ -28,37 +28,20 @@ int rg_dr_options(const rg_dr_opts *opts, rg_dr_opts *out, char *err, size_t err
 
 int rg_dr_track_planes(size_t i, const rg_track_desc &t, const rg_dr_opts &o, bool rate_is_format, size_t arena_bytes, RgDrPlane *planes, char *err,
                        size_t err_len) {
-    if (t.format != RG_FMT_F32_PLANAR && t.format != RG_FMT_S16_PLANAR && t.format != RG_FMT_S32_PLANAR) {
-        snprintf(err, err_len, "track %zu: format %u is not a planar PCM format", i, (unsigned)t.format);
-        return RG_ERR_FORMAT;
-    }
-    if (t.channels < 1 || t.channels > RG_DR_MAX_CHANNELS) {
-        snprintf(err, err_len, "track %zu: %u channel(s), the dynamic range takes 1 to %u", i, (unsigned)t.channels, RG_DR_MAX_CHANNELS);
-        return RG_ERR_FORMAT;
-    }
-    if (t.frames >= ((uint64_t)1 << 32)) {
-        snprintf(err, err_len, "track %zu: %llu frames, the dynamic range takes fewer than 2^32", i, (unsigned long long)t.frames);
-        return RG_ERR_FORMAT;
-    }
+    int rc = rg_pcm_check_format(i, t, RG_DR_MAX_CHANNELS, "the dynamic range takes", err, err_len);
+    if (rc != RG_OK) return rc;
     const uint64_t block = o.block_frames ? o.block_frames : (uint64_t)3 * t.sample_rate;
     if (block < 1 || block > RG_DR_MAX_BLOCK_FRAMES) {
         snprintf(err, err_len, "track %zu: a block of %llu frames (sample rate %u) is not in 1 .. %u", i, (unsigned long long)block, t.sample_rate,
                  RG_DR_MAX_BLOCK_FRAMES);
         return rate_is_format && !o.block_frames ? RG_ERR_FORMAT : RG_ERR_INVALID_ARG;
     }
-    const uint32_t bps = rg_dr_bps(t.format);
-    if (t.offset_bytes % bps) {
-        snprintf(err, err_len, "track %zu: offset %llu is not sample-aligned", i, (unsigned long long)t.offset_bytes);
-        return RG_ERR_INVALID_ARG;
-    }
-    if (t.offset_bytes > arena_bytes || t.frames > (arena_bytes - t.offset_bytes) / ((size_t)bps * t.channels)) {
-        snprintf(err, err_len, "track %zu: its planes reach beyond the arena (%zu bytes)", i, arena_bytes);
-        return RG_ERR_INVALID_ARG;
-    }
+    rc = rg_pcm_check_place(i, t, arena_bytes, err, err_len);
+    if (rc != RG_OK) return rc;
     for (uint32_t c = 0; c < t.channels; ++c) {
         RgDrPlane &p = planes[c];
         memset(&p, 0, sizeof p);
-        p.off = t.offset_bytes + (uint64_t)c * t.frames * bps;
+        p.off = rg_pcm_plane_off(t, c);
         p.n = (uint32_t)t.frames;
         p.block = (uint32_t)block;
         p.n_blocks = (uint32_t)((t.frames + block - 1) / block);
@@ -88,18 +71,6 @@ uint64_t rg_dr_plan(RgDrPlane *planes, size_t n, uint64_t fmt_piece[4], uint64_t
     return pieces;
 }
 
-// sample k of a plane as the stored pattern, S16 sign-extended (planes are only sample-aligned)
-static inline uint32_t raw_at(const unsigned char *plane, uint32_t format, uint64_t k) {
-    if (format == RG_FMT_S16_PLANAR) {
-        int16_t s;
-        memcpy(&s, plane + 2 * k, 2);
-        return (uint32_t)(int32_t)s;
-    }
-    uint32_t u;
-    memcpy(&u, plane + 4 * k, 4);
-    return u;
-}
-
 // ---- route 0: the definitions ------------------------------------------------------------------------------------------------
 RgDrPlaneOut rg_dr_serial_host(const unsigned char *arena, const RgDrPlane &p) {
     const unsigned char *plane = arena + p.off;
@@ -115,7 +86,7 @@ RgDrPlaneOut rg_dr_serial_host(const unsigned char *arena, const RgDrPlane &p) {
         unsigned __int128 E = 0;
         uint64_t peak = 0;
         for (uint64_t j = at; j < at + n; ++j) {
-            const uint32_t raw = raw_at(plane, p.format, j);
+            const uint32_t raw = rg_pcm_raw_at(plane, p.format, j);
             int64_t q;
             if (p.format == RG_FMT_F32_PLANAR) {
                 float x;
@@ -169,7 +140,7 @@ RgDrPlaneOut rg_dr_serial_host(const unsigned char *arena, const RgDrPlane &p) {
 template <int FMT>
 static RgDrPiece piece_sums(const unsigned char *plane, uint64_t first, uint32_t n) {
     RgDrPiece acc = rg_dr_empty();
-    for (uint32_t j = 0; j < n; ++j) rg_dr_take<FMT>(raw_at(plane, FMT, first + j), &acc);
+    for (uint32_t j = 0; j < n; ++j) rg_dr_take<FMT>(rg_pcm_raw_at(plane, FMT, first + j), &acc);
     return acc;
 }
 
@@ -257,16 +228,9 @@ void rg_dr_fill(const rg_track_desc &t, uint32_t block, uint32_t dropped_frames,
 
 int rg_dr_arena_host(int route, size_t n, const rg_track_desc *descs, const rg_dr_opts *opts, const void *arena, size_t arena_bytes, rg_dr_result *out,
                      char *err, size_t err_len) {
-    if (route != 0 && route != 2) {
-        snprintf(err, err_len, "rg_dr_arena: route %d is not a host route (0 = serial twin, 2 = folded)", route);
-        return RG_ERR_INVALID_ARG;
-    }
-    if (n && (!descs || !out || (arena_bytes && !arena))) {
-        snprintf(err, err_len, "rg_dr_arena: null array");
-        return RG_ERR_INVALID_ARG;
-    }
     rg_dr_opts o;
-    int rc = rg_dr_options(opts, &o, err, err_len);
+    int rc = rg_pcm_check_host_route("rg_dr_arena", "folded", route, n, descs, out, arena, arena_bytes, err, err_len);
+    if (rc == RG_OK) rc = rg_dr_options(opts, &o, err, err_len);
     if (rc != RG_OK) return rc;
     std::vector<RgDrPlane> planes(n * RG_DR_MAX_CHANNELS + 1);
     size_t n_planes = 0;

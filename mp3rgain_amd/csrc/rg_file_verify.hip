@@ -1,6 +1,8 @@
 // rg_file_verify.hip -- the file-level calls that check files instead of measuring loudness: rg_flac_verify
 // (include/mp3rgain_amd_flac.h), rg_mp3_verify (include/mp3rgain_amd_mp3verify.h), rg_rip_checksums
-// (include/mp3rgain_amd_rip.h), rg_pcm_stats (include/mp3rgain_amd_stats.h), rg_dynamic_range (include/mp3rgain_amd_dr.h) and rg_spectrum (include/mp3rgain_amd_spectrum.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
+// (include/mp3rgain_amd_rip.h), and the four PCM scans, which share one group driver (pcm_scan_group): rg_pcm_stats
+// (include/mp3rgain_amd_stats.h), rg_dynamic_range (include/mp3rgain_amd_dr.h), rg_ancestry (include/mp3rgain_amd_ancestry.h) and
+// rg_spectrum (include/mp3rgain_amd_spectrum.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
 // command: what this library does not decode itself is not a stream it could vouch for.  A file's status lives in its record,
 // and the record of a file that failed holds nothing else.
 #include <algorithm>
@@ -304,350 +306,238 @@ extern "C" int rg_rip_offset_signatures(rg_ctx *c, const char *const *paths, siz
     });
 }
 
-// ---- rg_pcm_stats ---------------------------------------------------------------------------------------------------------
-// one group of the call.  The route is rg_rip_checksums', except that every stream the library decodes itself is kept: all the
+// ---- the PCM scans: rg_pcm_stats, rg_dynamic_range, rg_ancestry, rg_spectrum ---------------------------------------------
+// One group of such a call.  The route is rg_rip_checksums', except that every stream the library decodes itself is kept: all the
 // WAV kinds the staging lays out, FLAC of any width and channel count up to 8, and MPEG Layer III as the f32 the decoder left in
-// the arena.  Whatever route put a track's PCM there, the two kernels of rg_stats.hip read it there, on the stream the decode
-// ran on, so tuning key 14 cannot show in the records.
-static int stats_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_pcm_stats_opts &o, rg_pcm_stats_result *out) {
-    out += first;
-    FileGroup g(c, paths, first, n);
-    int rc = g.load(LoadOpts{-1, false});
+// the arena.  Whatever route put a track's PCM there, the scan's kernels read it there, on the stream the decode ran on, so
+// tuning key 14 cannot show in the records.  A scan is its noun ("PCM stats"), its channel limit, and two functions:
+// add(k, i, err) appends the planes or views of batch entry k, file i of the group, or says why not in err[kPcmErrLen];
+// finish() launches over what was added and fills the records.
+constexpr size_t kPcmErrLen = 256;
+namespace {
+struct PcmRec {  // a track that was added, for a scan that keeps no more
+    size_t k, plane;  // position in the batch, its first plane
+};
+}  // namespace
+
+static std::string pcm_refused(const FileGroup &g, const char *noun, size_t i, const std::string &why) {
+    return std::string("No ") + noun + " (" + why + "): " + g.paths[i];
+}
+
+// a WAV stream the staging cannot lay out, or anything of more than `max_channels` channels, fails alone and in front of the staging
+static int pcm_screen(const FileGroup &g, size_t i, uint32_t max_channels, const char *noun, std::string *text) {
+    uint32_t channels = g.in[i].channels;
+    if (g.in[i].kind == LoadedAudio::Wav) {
+        rg_wav_info w;
+        if (rg_wav_parse(g.in[i].wav.data(), g.in[i].wav.size(), &w) != RG_OK) {
+            *text = std::string("Failed to probe format: ") + g.paths[i];
+            return RG_ERR_FORMAT;
+        }
+        if (wav_kind(w) < 0) {
+            *text = pcm_refused(g, noun, i, std::to_string(w.bits_per_sample) + "-bit " + (w.sample_format == 3 ? "float" : "samples of format " + std::to_string(w.sample_format)) +
+                                                ", not 8, 16, 24 or 32-bit integer or 32-bit float PCM");
+            return RG_ERR_FORMAT;
+        }
+        channels = w.channels;
+    }
+    if (channels <= max_channels) return RG_OK;
+    *text = pcm_refused(g, noun, i, std::to_string(channels) + " channels, more than " + std::to_string(max_channels));
+    return RG_ERR_FORMAT;
+}
+
+// the frames the route dropped from batch entry k of a staged group (with counts): FLAC frames as the decoder counted them, MPEG
+// frames as rg_mp3_verify counts them
+static uint32_t dropped_frames(const FileGroup &g, size_t k) {
+    const LoadedAudio &la = g.in[k];
+    if (la.kind == LoadedAudio::Wav) return 0;
+    if (la.kind == LoadedAudio::Flac) return g.counts[k].dropped;
+    const uint32_t spf = g.descs[k].sample_rate >= 32000 ? 1152 : 576;
+    return la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
+}
+
+// `out`: the group's records.  A track add() refuses with RG_ERR_FORMAT fails alone; any other status fails the call.
+template <typename Record, typename Add, typename Finish>
+static int pcm_scan_group(FileGroup &g, const char *noun, uint32_t max_channels, Record *out, Add add, Finish finish) {
+    const int rc = g.load(LoadOpts{-1, false});
     if (rc != RG_OK) return rc;
     const auto mark = mark_record(g, out);
-    const auto refused = [&](size_t i, const std::string &why) { return "No PCM stats (" + why + "): " + g.paths[i]; };
-    const auto too_wide = [&](size_t i, uint32_t channels) {
-        return refused(i, std::to_string(channels) + " channels, more than " + std::to_string(RG_STATS_MAX_CHANNELS));
-    };
-    // a WAV stream the staging cannot lay out, or anything of more than 8 channels, fails alone and in front of the staging
-    const auto screen = [&](size_t i, std::string *text) -> int {
-        uint32_t channels = g.in[i].channels;
-        if (g.in[i].kind == LoadedAudio::Wav) {
-            rg_wav_info w;
-            if (rg_wav_parse(g.in[i].wav.data(), g.in[i].wav.size(), &w) != RG_OK) {
-                *text = std::string("Failed to probe format: ") + g.paths[i];
-                return RG_ERR_FORMAT;
-            }
-            if (wav_kind(w) < 0) {
-                *text = refused(i, std::to_string(w.bits_per_sample) + "-bit " + (w.sample_format == 3 ? "float" : "samples of format " + std::to_string(w.sample_format)) +
-                                       ", not 8, 16, 24 or 32-bit integer or 32-bit float PCM");
-                return RG_ERR_FORMAT;
-            }
-            channels = w.channels;
-        }
-        if (channels <= RG_STATS_MAX_CHANNELS) return RG_OK;
-        *text = too_wide(i, channels);
-        return RG_ERR_FORMAT;
-    };
+    const auto screen = [&](size_t i, std::string *text) { return pcm_screen(g, i, max_channels, noun, text); };
     const auto work = [&]() -> int {
-        const std::vector<LoadedAudio> &in = g.in;
-        std::vector<RgStatsPlane> planes(g.slot.size() * RG_STATS_MAX_CHANNELS + 1);
-        std::vector<size_t> rec_of, plane_of;  // record -> position in the batch, its first plane
-        std::vector<uint32_t> reported, dropped;
-        size_t n_planes = 0;
         for (size_t k = 0; k < g.slot.size(); ++k) {
             const size_t i = g.slot[k];
-            const LoadedAudio &la = in[k];
-            uint32_t bits = rg_stats_width(g.descs[k].format), lost = 0;
-            if (la.kind == LoadedAudio::Wav) {
-                rg_wav_info w;
-                (void)rg_wav_parse(la.wav.data(), la.wav.size(), &w);  // (the screen has parsed this stream)
-                bits = w.bits_per_sample;
-            } else if (la.kind == LoadedAudio::Flac) {
-                bits = la.flac_bps;
-                lost = g.counts[k].dropped;
-            } else {  // an MPEG stream: the frames the route dropped, as rg_mp3_verify counts them
-                const uint32_t spf = g.descs[k].sample_rate >= 32000 ? 1152 : 576;
-                lost = la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
-            }
-            uint32_t rep = 0;
-            char err[256] = "";
-            const int prc = rg_stats_track_planes(i, g.descs[k], bits, g.arena_bytes, &planes[n_planes], &rep, err, sizeof err);
-            if (prc == RG_ERR_FORMAT) {
-                mark(i, RG_ERR_FORMAT, refused(i, err));
-                continue;
-            }
-            if (prc != RG_OK) return rg_set_err(c, prc, "%s", err);
-            rec_of.push_back(k);
-            plane_of.push_back(n_planes);
-            reported.push_back(rep);
-            dropped.push_back(lost);
-            n_planes += g.descs[k].channels;
+            char err[kPcmErrLen] = "";
+            const int prc = add(k, i, err);
+            if (prc == RG_ERR_FORMAT)
+                mark(i, RG_ERR_FORMAT, pcm_refused(g, noun, i, err));
+            else if (prc != RG_OK)
+                return rg_set_err(g.c, prc, "%s", err);
         }
-        if (rec_of.empty()) return RG_OK;
-        std::vector<rg_pcm_stats_channel> ch(n_planes);
-        const int drc = rg_stats_device(c, c->d_arena.p, planes.data(), n_planes, o, ch.data(), c->file_stream());
-        if (drc != RG_OK) return drc;
-        for (size_t j = 0; j < rec_of.size(); ++j) {
-            const size_t k = rec_of[j];
-            rg_stats_fill(g.descs[k], reported[j], dropped[j], &ch[plane_of[j]], &out[g.slot[k]]);
-        }
-        return RG_OK;
+        return finish();
     };
     g.want_counts = true;
     return g.run(screen, mark, work);
+}
+
+// the call around the groups: the options checked by `options`, the records (and `also`, when there is one) zeroed, then
+// group(first, cnt, o) for each group of the list
+template <typename Opts, typename Record, typename Options, typename Group>
+static int pcm_scan_call(rg_ctx *c, const char *const *paths, size_t n, const Opts *opts, Record *out, Options options, Group group, void *also = nullptr,
+                         size_t also_bytes = 0) {
+    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
+    Opts o;
+    char err[256] = "";
+    const int orc = options(opts, &o, err, sizeof err);
+    if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
+    if (n) memset(out, 0, n * sizeof *out);
+    if (also && also_bytes) memset(also, 0, also_bytes);
+    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return group(first, cnt, o); });
+}
+
+// ---- rg_pcm_stats: the two kernels of rg_stats.hip ------------------------------------------------------------------------
+static int stats_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_pcm_stats_opts &o, rg_pcm_stats_result *out) {
+    FileGroup g(c, paths, first, n);
+    out += first;
+    struct Rec {
+        size_t k, plane;  // position in the batch, its first plane
+        uint32_t bits;    // as the record reports them
+    };
+    std::vector<Rec> recs;
+    std::vector<RgStatsPlane> planes(n * RG_STATS_MAX_CHANNELS + 1);
+    size_t n_planes = 0;
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        const LoadedAudio &la = g.in[k];
+        uint32_t bits = rg_pcm_width(g.descs[k].format);
+        if (la.kind == LoadedAudio::Wav) {
+            rg_wav_info w;
+            (void)rg_wav_parse(la.wav.data(), la.wav.size(), &w);  // (the screen has parsed this stream)
+            bits = w.bits_per_sample;
+        } else if (la.kind == LoadedAudio::Flac) {
+            bits = la.flac_bps;
+        }
+        Rec r{k, n_planes, 0};
+        const int rc = rg_stats_track_planes(i, g.descs[k], bits, g.arena_bytes, &planes[n_planes], &r.bits, err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        recs.push_back(r);
+        n_planes += g.descs[k].channels;
+        return RG_OK;
+    };
+    const auto finish = [&]() -> int {
+        if (recs.empty()) return RG_OK;
+        std::vector<rg_pcm_stats_channel> ch(n_planes);
+        const int rc = rg_stats_device(c, c->d_arena.p, planes.data(), n_planes, o, ch.data(), c->file_stream());
+        if (rc != RG_OK) return rc;
+        for (const Rec &r : recs) rg_stats_fill(g.descs[r.k], r.bits, dropped_frames(g, r.k), &ch[r.plane], &out[g.slot[r.k]]);
+        return RG_OK;
+    };
+    return pcm_scan_group(g, "PCM stats", RG_STATS_MAX_CHANNELS, out, add, finish);
 }
 
 extern "C" int rg_pcm_stats(rg_ctx *c, const char *const *paths, size_t n, const rg_pcm_stats_opts *opts, rg_pcm_stats_result *out) {
-    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
-    rg_pcm_stats_opts o;
-    char err[256] = "";
-    const int orc = rg_stats_options(opts, &o, err, sizeof err);
-    if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
-    if (n) memset(out, 0, n * sizeof *out);
-    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return stats_group(c, paths, first, cnt, o, out); });
+    return pcm_scan_call(c, paths, n, opts, out, rg_stats_options,
+                         [&](size_t first, size_t cnt, const rg_pcm_stats_opts &o) { return stats_group(c, paths, first, cnt, o, out); });
 }
 
-// ---- rg_dynamic_range -----------------------------------------------------------------------------------------------------
-// one group of the call: rg_pcm_stats' route and screen, and the kernels of rg_dr.hip over the planes where the decode left
-// them, on the stream the decode ran on, so tuning key 14 cannot show in the records.  The finish is host arithmetic on what
-// comes back (rg_dr_fill).
+// ---- rg_dynamic_range: the kernels of rg_dr.hip; the finish is host arithmetic on what comes back (rg_dr_fill) -------------
 static int dr_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_dr_opts &o, rg_dr_result *out) {
-    out += first;
     FileGroup g(c, paths, first, n);
-    int rc = g.load(LoadOpts{-1, false});
-    if (rc != RG_OK) return rc;
-    const auto mark = mark_record(g, out);
-    const auto refused = [&](size_t i, const std::string &why) { return "No dynamic range (" + why + "): " + g.paths[i]; };
-    // a WAV stream the staging cannot lay out, or anything of more than 8 channels, fails alone and in front of the staging
-    const auto screen = [&](size_t i, std::string *text) -> int {
-        uint32_t channels = g.in[i].channels;
-        if (g.in[i].kind == LoadedAudio::Wav) {
-            rg_wav_info w;
-            if (rg_wav_parse(g.in[i].wav.data(), g.in[i].wav.size(), &w) != RG_OK) {
-                *text = std::string("Failed to probe format: ") + g.paths[i];
-                return RG_ERR_FORMAT;
-            }
-            if (wav_kind(w) < 0) {
-                *text = refused(i, std::to_string(w.bits_per_sample) + "-bit " + (w.sample_format == 3 ? "float" : "samples of format " + std::to_string(w.sample_format)) +
-                                       ", not 8, 16, 24 or 32-bit integer or 32-bit float PCM");
-                return RG_ERR_FORMAT;
-            }
-            channels = w.channels;
-        }
-        if (channels <= RG_DR_MAX_CHANNELS) return RG_OK;
-        *text = refused(i, std::to_string(channels) + " channels, more than " + std::to_string(RG_DR_MAX_CHANNELS));
-        return RG_ERR_FORMAT;
-    };
-    const auto work = [&]() -> int {
-        const std::vector<LoadedAudio> &in = g.in;
-        std::vector<RgDrPlane> planes(g.slot.size() * RG_DR_MAX_CHANNELS + 1);
-        std::vector<size_t> rec_of, plane_of;  // record -> position in the batch, its first plane
-        std::vector<uint32_t> dropped;
-        size_t n_planes = 0;
-        for (size_t k = 0; k < g.slot.size(); ++k) {
-            const size_t i = g.slot[k];
-            const LoadedAudio &la = in[k];
-            uint32_t lost = 0;
-            if (la.kind == LoadedAudio::Flac) {
-                lost = g.counts[k].dropped;
-            } else if (la.kind != LoadedAudio::Wav) {  // an MPEG stream: the frames the route dropped, as rg_mp3_verify counts them
-                const uint32_t spf = g.descs[k].sample_rate >= 32000 ? 1152 : 576;
-                lost = la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
-            }
-            char err[256] = "";
-            const int prc = rg_dr_track_planes(i, g.descs[k], o, true, g.arena_bytes, &planes[n_planes], err, sizeof err);
-            if (prc == RG_ERR_FORMAT) {
-                mark(i, RG_ERR_FORMAT, refused(i, err));
-                continue;
-            }
-            if (prc != RG_OK) return rg_set_err(c, prc, "%s", err);
-            rec_of.push_back(k);
-            plane_of.push_back(n_planes);
-            dropped.push_back(lost);
-            n_planes += g.descs[k].channels;
-        }
-        if (rec_of.empty()) return RG_OK;
-        std::vector<RgDrPlaneOut> po(n_planes);
-        const int drc = rg_dr_device(c, c->d_arena.p, planes.data(), n_planes, po.data(), c->file_stream());
-        if (drc != RG_OK) return drc;
-        for (size_t j = 0; j < rec_of.size(); ++j) {
-            const size_t k = rec_of[j];
-            rg_dr_fill(g.descs[k], planes[plane_of[j]].block, dropped[j], &po[plane_of[j]], &out[g.slot[k]]);
-        }
+    out += first;
+    std::vector<PcmRec> recs;
+    std::vector<RgDrPlane> planes(n * RG_DR_MAX_CHANNELS + 1);
+    size_t n_planes = 0;
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        const int rc = rg_dr_track_planes(i, g.descs[k], o, true, g.arena_bytes, &planes[n_planes], err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        recs.push_back(PcmRec{k, n_planes});
+        n_planes += g.descs[k].channels;
         return RG_OK;
     };
-    g.want_counts = true;
-    return g.run(screen, mark, work);
+    const auto finish = [&]() -> int {
+        if (recs.empty()) return RG_OK;
+        std::vector<RgDrPlaneOut> po(n_planes);
+        const int rc = rg_dr_device(c, c->d_arena.p, planes.data(), n_planes, po.data(), c->file_stream());
+        if (rc != RG_OK) return rc;
+        for (const PcmRec &r : recs) rg_dr_fill(g.descs[r.k], planes[r.plane].block, dropped_frames(g, r.k), &po[r.plane], &out[g.slot[r.k]]);
+        return RG_OK;
+    };
+    return pcm_scan_group(g, "dynamic range", RG_DR_MAX_CHANNELS, out, add, finish);
 }
 
 extern "C" int rg_dynamic_range(rg_ctx *c, const char *const *paths, size_t n, const rg_dr_opts *opts, rg_dr_result *out) {
-    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
-    rg_dr_opts o;
-    char err[256] = "";
-    const int orc = rg_dr_options(opts, &o, err, sizeof err);
-    if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
-    if (n) memset(out, 0, n * sizeof *out);
-    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return dr_group(c, paths, first, cnt, o, out); });
+    return pcm_scan_call(c, paths, n, opts, out, rg_dr_options, [&](size_t first, size_t cnt, const rg_dr_opts &o) { return dr_group(c, paths, first, cnt, o, out); });
 }
 
-// ---- rg_ancestry ----------------------------------------------------------------------------------------------------------
-// one group of the call: rg_pcm_stats' route and screen, and the kernels of rg_ancestry.hip over the planes where the decode
-// left them, on the stream the decode ran on, so tuning key 14 cannot show in the records.  The verdict is host arithmetic on
-// the counts that come back (rg_anc_fill).
+// ---- rg_ancestry: the kernels of rg_ancestry.hip; the verdict is host arithmetic on the counts that come back (rg_anc_fill) --
 static int ancestry_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_ancestry_opts &o, rg_ancestry_result *out) {
-    out += first;
     FileGroup g(c, paths, first, n);
-    int rc = g.load(LoadOpts{-1, false});
-    if (rc != RG_OK) return rc;
-    const auto mark = mark_record(g, out);
-    const auto refused = [&](size_t i, const std::string &why) { return "No ancestry scan (" + why + "): " + g.paths[i]; };
-    // a WAV stream the staging cannot lay out, or anything of more than 8 channels, fails alone and in front of the staging
-    const auto screen = [&](size_t i, std::string *text) -> int {
-        uint32_t channels = g.in[i].channels;
-        if (g.in[i].kind == LoadedAudio::Wav) {
-            rg_wav_info w;
-            if (rg_wav_parse(g.in[i].wav.data(), g.in[i].wav.size(), &w) != RG_OK) {
-                *text = std::string("Failed to probe format: ") + g.paths[i];
-                return RG_ERR_FORMAT;
-            }
-            if (wav_kind(w) < 0) {
-                *text = refused(i, std::to_string(w.bits_per_sample) + "-bit " + (w.sample_format == 3 ? "float" : "samples of format " + std::to_string(w.sample_format)) +
-                                       ", not 8, 16, 24 or 32-bit integer or 32-bit float PCM");
-                return RG_ERR_FORMAT;
-            }
-            channels = w.channels;
-        }
-        if (channels <= RG_ANC_MAX_CHANNELS) return RG_OK;
-        *text = refused(i, std::to_string(channels) + " channels, more than " + std::to_string(RG_ANC_MAX_CHANNELS));
-        return RG_ERR_FORMAT;
+    out += first;
+    struct Rec {
+        size_t k, view;  // position in the batch, its first view
+        uint32_t n_views, S, G;
     };
-    const auto work = [&]() -> int {
-        const std::vector<LoadedAudio> &in = g.in;
-        std::vector<RgAncView> views(g.slot.size() * RG_ANC_MAX_VIEWS + 1);
-        std::vector<RgAncJob> jobs;
-        struct Rec {
-            size_t k, view;
-            uint32_t n_views, S, G, dropped;
-        };
-        std::vector<Rec> recs;
-        size_t n_views = 0;
-        for (size_t k = 0; k < g.slot.size(); ++k) {
-            const size_t i = g.slot[k];
-            const LoadedAudio &la = in[k];
-            uint32_t lost = 0;
-            if (la.kind == LoadedAudio::Flac) {
-                lost = g.counts[k].dropped;
-            } else if (la.kind != LoadedAudio::Wav) {  // an MPEG stream: the frames the route dropped, as rg_mp3_verify counts them
-                const uint32_t spf = g.descs[k].sample_rate >= 32000 ? 1152 : 576;
-                lost = la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
-            }
-            char err[256] = "";
-            Rec r{k, n_views, 0, 0, 0, lost};
-            const int prc = rg_anc_track_views(i, g.descs[k], g.arena_bytes, &views[n_views], &r.n_views, err, sizeof err);
-            if (prc == RG_ERR_FORMAT) {
-                mark(i, RG_ERR_FORMAT, refused(i, err));
-                continue;
-            }
-            if (prc != RG_OK) return rg_set_err(c, prc, "%s", err);
-            for (uint32_t v = 0; v < r.n_views; ++v) rg_anc_jobs(g.descs[k].frames, o, (uint32_t)(n_views + v), &jobs, &r.S, &r.G);
-            recs.push_back(r);
-            n_views += r.n_views;
-        }
+    std::vector<Rec> recs;
+    std::vector<RgAncView> views(n * RG_ANC_MAX_VIEWS + 1);
+    std::vector<RgAncJob> jobs;
+    size_t n_views = 0;
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        Rec r{k, n_views, 0, 0, 0};
+        const int rc = rg_anc_track_views(i, g.descs[k], g.arena_bytes, &views[n_views], &r.n_views, err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        for (uint32_t v = 0; v < r.n_views; ++v) rg_anc_jobs(g.descs[k].frames, o, (uint32_t)(n_views + v), &jobs, &r.S, &r.G);
+        recs.push_back(r);
+        n_views += r.n_views;
+        return RG_OK;
+    };
+    const auto finish = [&]() -> int {
         if (recs.empty()) return RG_OK;
         const size_t per_view = 2 * RG_ANC_ALIGNMENTS;
         std::vector<uint64_t> cnt(n_views * per_view), nonfinite(n_views);
-        const int drc = rg_anc_device(c, c->d_arena.p, views.data(), n_views, jobs, o.active_floor, cnt.data(), nonfinite.data(), c->file_stream());
-        if (drc != RG_OK) return drc;
+        const int rc = rg_anc_device(c, c->d_arena.p, views.data(), n_views, jobs, o.active_floor, cnt.data(), nonfinite.data(), c->file_stream());
+        if (rc != RG_OK) return rc;
         for (const Rec &r : recs)
-            rg_anc_fill(g.descs[r.k], o, r.S, r.G, r.dropped, r.n_views, &views[r.view], &cnt[r.view * per_view], &nonfinite[r.view], &out[g.slot[r.k]]);
+            rg_anc_fill(g.descs[r.k], o, r.S, r.G, dropped_frames(g, r.k), r.n_views, &views[r.view], &cnt[r.view * per_view], &nonfinite[r.view],
+                        &out[g.slot[r.k]]);
         return RG_OK;
     };
-    g.want_counts = true;
-    return g.run(screen, mark, work);
+    return pcm_scan_group(g, "ancestry scan", RG_ANC_MAX_CHANNELS, out, add, finish);
 }
 
 extern "C" int rg_ancestry(rg_ctx *c, const char *const *paths, size_t n, const rg_ancestry_opts *opts, rg_ancestry_result *out) {
-    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
-    rg_ancestry_opts o;
-    char err[256] = "";
-    const int orc = rg_anc_options(opts, &o, err, sizeof err);
-    if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
-    if (n) memset(out, 0, n * sizeof *out);
-    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return ancestry_group(c, paths, first, cnt, o, out); });
+    return pcm_scan_call(c, paths, n, opts, out, rg_anc_options,
+                         [&](size_t first, size_t cnt, const rg_ancestry_opts &o) { return ancestry_group(c, paths, first, cnt, o, out); });
 }
 
-// ---- rg_spectrum ----------------------------------------------------------------------------------------------------------
-// one group of the call: rg_pcm_stats' route and screen, and the two kernels of rg_spectrum.hip over the planes where the decode
-// left them, on the stream the decode ran on.  The verdict is host arithmetic on what comes back (rg_spec_fill).
+// ---- rg_spectrum: the two kernels of rg_spectrum.hip; the verdict is host arithmetic on what comes back (rg_spec_fill) -------
 static int spectrum_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_spectrum_opts &o, rg_spectrum_result *out, double *bands) {
-    out += first;
-    if (bands) bands += first * RG_SPEC_MAX_CHANNELS * RG_SPEC_BANDS;
+    const size_t per_file = RG_SPEC_MAX_CHANNELS * RG_SPEC_BANDS;
     FileGroup g(c, paths, first, n);
-    int rc = g.load(LoadOpts{-1, false});
-    if (rc != RG_OK) return rc;
-    const auto mark = mark_record(g, out);
-    const auto refused = [&](size_t i, const std::string &why) { return "No spectrum (" + why + "): " + g.paths[i]; };
-    // a WAV stream the staging cannot lay out, or anything of more than 8 channels, fails alone and in front of the staging
-    const auto screen = [&](size_t i, std::string *text) -> int {
-        uint32_t channels = g.in[i].channels;
-        if (g.in[i].kind == LoadedAudio::Wav) {
-            rg_wav_info w;
-            if (rg_wav_parse(g.in[i].wav.data(), g.in[i].wav.size(), &w) != RG_OK) {
-                *text = std::string("Failed to probe format: ") + g.paths[i];
-                return RG_ERR_FORMAT;
-            }
-            if (wav_kind(w) < 0) {
-                *text = refused(i, std::to_string(w.bits_per_sample) + "-bit " + (w.sample_format == 3 ? "float" : "samples of format " + std::to_string(w.sample_format)) +
-                                       ", not 8, 16, 24 or 32-bit integer or 32-bit float PCM");
-                return RG_ERR_FORMAT;
-            }
-            channels = w.channels;
-        }
-        if (channels <= RG_SPEC_MAX_CHANNELS) return RG_OK;
-        *text = refused(i, std::to_string(channels) + " channels, more than " + std::to_string(RG_SPEC_MAX_CHANNELS));
-        return RG_ERR_FORMAT;
-    };
-    const auto work = [&]() -> int {
-        const std::vector<LoadedAudio> &in = g.in;
-        std::vector<RgSpecPlane> planes(g.slot.size() * RG_SPEC_MAX_CHANNELS + 1);
-        std::vector<size_t> rec_of, plane_of;  // record -> position in the batch, its first plane
-        std::vector<uint32_t> dropped;
-        size_t n_planes = 0;
-        for (size_t k = 0; k < g.slot.size(); ++k) {
-            const size_t i = g.slot[k];
-            const LoadedAudio &la = in[k];
-            uint32_t lost = 0;
-            if (la.kind == LoadedAudio::Flac) {
-                lost = g.counts[k].dropped;
-            } else if (la.kind != LoadedAudio::Wav) {  // an MPEG stream: the frames the route dropped, as rg_mp3_verify counts them
-                const uint32_t spf = g.descs[k].sample_rate >= 32000 ? 1152 : 576;
-                lost = la.kind == LoadedAudio::Staged ? (uint32_t)((la.walked_frames - std::min(la.walked_frames, la.frames)) / spf) : la.mp3_skipped;
-            }
-            char err[256] = "";
-            const int prc = rg_spec_track_planes(i, g.descs[k], g.arena_bytes, &planes[n_planes], err, sizeof err);
-            if (prc == RG_ERR_FORMAT) {
-                mark(i, RG_ERR_FORMAT, refused(i, err));
-                continue;
-            }
-            if (prc != RG_OK) return rg_set_err(c, prc, "%s", err);
-            rec_of.push_back(k);
-            plane_of.push_back(n_planes);
-            dropped.push_back(lost);
-            n_planes += g.descs[k].channels;
-        }
-        if (rec_of.empty()) return RG_OK;
-        std::vector<RgSpecPlaneOut> po(n_planes);
-        const int drc = rg_spectrum_device(c, c->d_arena.p, planes.data(), n_planes, po.data(), c->file_stream());
-        if (drc != RG_OK) return drc;
-        for (size_t j = 0; j < rec_of.size(); ++j) {
-            const size_t k = rec_of[j];
-            rg_spec_fill(g.descs[k], dropped[j], &po[plane_of[j]], o, &out[g.slot[k]],
-                         bands ? bands + g.slot[k] * RG_SPEC_MAX_CHANNELS * RG_SPEC_BANDS : nullptr);
-        }
+    out += first;
+    if (bands) bands += first * per_file;
+    std::vector<PcmRec> recs;
+    std::vector<RgSpecPlane> planes(n * RG_SPEC_MAX_CHANNELS + 1);
+    size_t n_planes = 0;
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        const int rc = rg_spec_track_planes(i, g.descs[k], g.arena_bytes, &planes[n_planes], err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        recs.push_back(PcmRec{k, n_planes});
+        n_planes += g.descs[k].channels;
         return RG_OK;
     };
-    g.want_counts = true;
-    return g.run(screen, mark, work);
+    const auto finish = [&]() -> int {
+        if (recs.empty()) return RG_OK;
+        std::vector<RgSpecPlaneOut> po(n_planes);
+        const int rc = rg_spectrum_device(c, c->d_arena.p, planes.data(), n_planes, po.data(), c->file_stream());
+        if (rc != RG_OK) return rc;
+        for (const PcmRec &r : recs)
+            rg_spec_fill(g.descs[r.k], dropped_frames(g, r.k), &po[r.plane], o, &out[g.slot[r.k]], bands ? bands + g.slot[r.k] * per_file : nullptr);
+        return RG_OK;
+    };
+    return pcm_scan_group(g, "spectrum", RG_SPEC_MAX_CHANNELS, out, add, finish);
 }
 
 extern "C" int rg_spectrum(rg_ctx *c, const char *const *paths, size_t n, const rg_spectrum_opts *opts, rg_spectrum_result *out, double *bands_out) {
-    if (!c || (n && (!paths || !out))) return RG_ERR_INVALID_ARG;
-    rg_spectrum_opts o;
-    char err[256] = "";
-    const int orc = rg_spec_options(opts, &o, err, sizeof err);
-    if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
-    if (n) memset(out, 0, n * sizeof *out);
-    if (n && bands_out) memset(bands_out, 0, n * RG_SPEC_MAX_CHANNELS * RG_SPEC_BANDS * sizeof(double));
-    return for_each_group(c, paths, n, [&](size_t first, size_t cnt) { return spectrum_group(c, paths, first, cnt, o, out, bands_out); });
+    return pcm_scan_call(
+        c, paths, n, opts, out, rg_spec_options,
+        [&](size_t first, size_t cnt, const rg_spectrum_opts &o) { return spectrum_group(c, paths, first, cnt, o, out, bands_out); }, bands_out,
+        n * RG_SPEC_MAX_CHANNELS * RG_SPEC_BANDS * sizeof(double));
 }
+

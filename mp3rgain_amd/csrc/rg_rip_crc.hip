@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "rg_ctx.h"
+#include "rg_pcm_seam.h"
 #include "rg_rip.h"
 
 // LDS image of one plane's stretch: dword d of the aligned cover at d + (d >> 4)
@@ -190,36 +191,24 @@ int rg_rip_kernels(rg_ctx *c, const unsigned char *d_arena, const RgRipTrack *re
 // ---- test seam (include/mp3rgain_amd_rip.h) ---------------------------------------------------------------------------------
 extern "C" int rg_rip_checksums_arena(void *ctx, int route, size_t n, const rg_track_desc *descs, const uint32_t *track_flags, const void *arena,
                                       size_t arena_bytes, rg_rip_result *out) {
-    rg_ctx *c = static_cast<rg_ctx *>(ctx);
-    char err[256] = "";
-    if (!c && route == 1) return RG_ERR_INVALID_ARG;  // the host routes need no context (their error text: rg_last_error(NULL))
-    if (route < 0 || route > 2)
-        return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_rip_checksums_arena: route %d (0 = serial host twin, 1 = kernels, 2 = folded on the host)", route);
-    if (n && (!descs || !out || (arena_bytes && !arena))) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_rip_checksums_arena: null array");
-    try {
-        if (route != 1) {
-            const int rc = rg_rip_arena_host(route, n, descs, track_flags, arena, arena_bytes, out, err, sizeof err);
-            return rc == RG_OK ? RG_OK : rg_set_err(c, rc, "%s", err);
-        }
-        std::vector<RgRipTrack> recs(n ? n : 1);
-        std::vector<RgRipSums> sums(n ? n : 1);
+    std::vector<RgRipTrack> recs;
+    const auto host = [&](char *err, size_t err_len) { return rg_rip_arena_host(route, n, descs, track_flags, arena, arena_bytes, out, err, err_len); };
+    const auto plan = [&](char *err, size_t err_len) -> int {
+        recs = std::vector<RgRipTrack>(n ? n : 1);
         for (size_t i = 0; i < n; ++i) {
-            const int rc = rg_rip_track_record(i, descs[i], track_flags ? track_flags[i] : 0u, arena_bytes, &recs[i], err, sizeof err);
-            if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
+            const int rc = rg_rip_track_record(i, descs[i], track_flags ? track_flags[i] : 0u, arena_bytes, &recs[i], err, err_len);
+            if (rc != RG_OK) return rc;
         }
-        int rc = rg_bind_device(c);
-        if (rc != RG_OK) return rc;
-        RG_HIP(c, rg_sync_slots(c, c->n_slots));
-        RG_HIP(c, c->d_arena.reserve(((arena_bytes + 15) & ~(size_t)15) + 16));  // whole 16-byte words: the staging's aligned cover
-        hipStream_t s = c->slots[0].stream;
-        if (arena_bytes) RG_HIP(c, hipMemcpyAsync(c->d_arena.p, arena, arena_bytes, hipMemcpyHostToDevice, s));
-        rc = rg_rip_device(c, c->d_arena.p, recs.data(), n, sums.data(), s);
+        return RG_OK;
+    };
+    const auto device = [&](rg_ctx *c, hipStream_t s) -> int {
+        std::vector<RgRipSums> sums(n ? n : 1);
+        const int rc = rg_rip_device(c, c->d_arena.p, recs.data(), n, sums.data(), s);
         if (rc != RG_OK) return rc;
         for (size_t i = 0; i < n; ++i) rg_rip_fill(sums[i], descs[i].frames, descs[i].sample_rate, 0, &out[i]);
         return RG_OK;
-    } catch (const std::bad_alloc &) {
-        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
-    }
+    };
+    return rg_pcm_arena_seam(ctx, route, "rg_rip_checksums_arena", "folded", n, descs, out, arena, arena_bytes, host, plan, device);
 }
 
 // ---- measurement hook (tools/rip_crc_rate.py) -------------------------------------------------------------------------------

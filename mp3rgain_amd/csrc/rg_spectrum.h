@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "../../include/mp3rgain_amd_spectrum.h"
+#include "rg_pcm_plane.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -59,7 +60,6 @@ struct RgSpecPlaneOut {
     uint32_t reserved[2];
 };  // 2064 bytes
 
-RG_SPEC_HD uint32_t rg_spec_width(uint32_t format) { return format == RG_FMT_S16_PLANAR ? 16u : 32u; }
 RG_SPEC_HD uint32_t rg_spec_frames(uint64_t n) { return n < RG_SPEC_FRAME ? 0u : (uint32_t)((n - RG_SPEC_FRAME) / RG_SPEC_HOP + 1u); }
 
 // `raw`: the stored pattern, an S16 sample sign-extended to 32 bits

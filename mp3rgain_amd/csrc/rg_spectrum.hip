@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "rg_ctx.h"
+#include "rg_pcm_seam.h"
 #include "rg_spectrum.h"
 
 #define RG_SPEC_ROW 18u    // complex per row of 16 in the exchange buffer
@@ -244,36 +245,24 @@ int rg_spectrum_device(rg_ctx *c, const unsigned char *d_arena, RgSpecPlane *pla
 // ---- test seam (include/mp3rgain_amd_spectrum.h) ---------------------------------------------------------------------------
 extern "C" int rg_spectrum_arena(void *ctx, int route, size_t n, const rg_track_desc *descs, const rg_spectrum_opts *opts, const void *arena,
                                  size_t arena_bytes, rg_spectrum_result *out, double *bands_out) {
-    rg_ctx *c = static_cast<rg_ctx *>(ctx);
-    char err[256] = "";
-    if (!c && route == 1) return RG_ERR_INVALID_ARG;  // the host routes need no context (their error text: rg_last_error(NULL))
-    if (route < 0 || route > 2)
-        return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_spectrum_arena: route %d (0 = serial host twin, 1 = kernels, 2 = the kernels' arithmetic on the host)",
-                          route);
-    if (n && (!descs || !out || (arena_bytes && !arena))) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_spectrum_arena: null array");
-    try {
-        if (route != 1) {
-            const int rc = rg_spec_arena_host(route, n, descs, opts, arena, arena_bytes, out, bands_out, err, sizeof err);
-            return rc == RG_OK ? RG_OK : rg_set_err(c, rc, "%s", err);
-        }
-        rg_spectrum_opts o;
-        int rc = rg_spec_options(opts, &o, err, sizeof err);
-        if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
-        std::vector<RgSpecPlane> planes(n * RG_SPEC_MAX_CHANNELS + 1);
-        size_t n_planes = 0;
+    rg_spectrum_opts o;
+    std::vector<RgSpecPlane> planes;
+    size_t n_planes = 0;
+    const auto host = [&](char *err, size_t err_len) { return rg_spec_arena_host(route, n, descs, opts, arena, arena_bytes, out, bands_out, err, err_len); };
+    const auto plan = [&](char *err, size_t err_len) -> int {
+        int rc = rg_spec_options(opts, &o, err, err_len);
+        if (rc != RG_OK) return rc;
+        planes = std::vector<RgSpecPlane>(n * RG_SPEC_MAX_CHANNELS + 1);
         for (size_t i = 0; i < n; ++i) {
-            rc = rg_spec_track_planes(i, descs[i], arena_bytes, &planes[n_planes], err, sizeof err);
-            if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
+            rc = rg_spec_track_planes(i, descs[i], arena_bytes, &planes[n_planes], err, err_len);
+            if (rc != RG_OK) return rc;
             n_planes += descs[i].channels;
         }
-        rc = rg_bind_device(c);
-        if (rc != RG_OK) return rc;
-        RG_HIP(c, rg_sync_slots(c, c->n_slots));
-        RG_HIP(c, c->d_arena.reserve(((arena_bytes + 15) & ~(size_t)15) + 16));
-        hipStream_t s = c->slots[0].stream;
-        if (arena_bytes) RG_HIP(c, hipMemcpyAsync(c->d_arena.p, arena, arena_bytes, hipMemcpyHostToDevice, s));
+        return RG_OK;
+    };
+    const auto device = [&](rg_ctx *c, hipStream_t s) -> int {
         std::vector<RgSpecPlaneOut> po(n_planes ? n_planes : 1);
-        rc = rg_spectrum_device(c, c->d_arena.p, planes.data(), n_planes, po.data(), s);
+        const int rc = rg_spectrum_device(c, c->d_arena.p, planes.data(), n_planes, po.data(), s);
         if (rc != RG_OK) return rc;
         if (!n_planes) RG_HIP(c, hipStreamSynchronize(s));
         size_t at = 0;
@@ -282,9 +271,8 @@ extern "C" int rg_spectrum_arena(void *ctx, int route, size_t n, const rg_track_
             at += descs[i].channels;
         }
         return RG_OK;
-    } catch (const std::bad_alloc &) {
-        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
-    }
+    };
+    return rg_pcm_arena_seam(ctx, route, "rg_spectrum_arena", "the kernels' arithmetic", n, descs, out, arena, arena_bytes, host, plan, device);
 }
 
 // ---- measurement hook (tools/spectrum_rate.py) ------------------------------------------------------------------------------
@@ -308,7 +296,7 @@ extern "C" int rg_spectrum_rate(void *ctx, size_t n, uint64_t frames, uint32_t f
         return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_spectrum_rate: bad arguments");
     int rc = rg_bind_device(c);
     if (rc != RG_OK) return rc;
-    const uint32_t bps = rg_spec_width(format) / 8;
+    const uint32_t bps = rg_pcm_width(format) / 8;
     const size_t track_bytes = (size_t)frames * 2 * bps, stride = (track_bytes + 15) & ~(size_t)15, total = n * stride;
     unsigned char *d_arena = nullptr, *d = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;

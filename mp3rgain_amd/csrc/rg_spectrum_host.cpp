@@ -40,31 +40,13 @@ int rg_spec_options(const rg_spectrum_opts *opts, rg_spectrum_opts *out, char *e
 }
 
 int rg_spec_track_planes(size_t i, const rg_track_desc &t, size_t arena_bytes, RgSpecPlane *planes, char *err, size_t err_len) {
-    if (t.format != RG_FMT_F32_PLANAR && t.format != RG_FMT_S16_PLANAR && t.format != RG_FMT_S32_PLANAR) {
-        snprintf(err, err_len, "track %zu: format %u is not a planar PCM format", i, (unsigned)t.format);
-        return RG_ERR_FORMAT;
-    }
-    if (t.channels < 1 || t.channels > RG_SPEC_MAX_CHANNELS) {
-        snprintf(err, err_len, "track %zu: %u channel(s), the spectrum takes 1 to %u", i, (unsigned)t.channels, RG_SPEC_MAX_CHANNELS);
-        return RG_ERR_FORMAT;
-    }
-    if (t.frames >= ((uint64_t)1 << 32)) {
-        snprintf(err, err_len, "track %zu: %llu frames, the spectrum takes fewer than 2^32", i, (unsigned long long)t.frames);
-        return RG_ERR_FORMAT;
-    }
-    const uint32_t bps = rg_spec_width(t.format) / 8;
-    if (t.offset_bytes % bps) {
-        snprintf(err, err_len, "track %zu: offset %llu is not sample-aligned", i, (unsigned long long)t.offset_bytes);
-        return RG_ERR_INVALID_ARG;
-    }
-    if (t.offset_bytes > arena_bytes || t.frames > (arena_bytes - t.offset_bytes) / ((size_t)bps * t.channels)) {
-        snprintf(err, err_len, "track %zu: its planes reach beyond the arena (%zu bytes)", i, arena_bytes);
-        return RG_ERR_INVALID_ARG;
-    }
+    int rc = rg_pcm_check_format(i, t, RG_SPEC_MAX_CHANNELS, "the spectrum takes", err, err_len);
+    if (rc == RG_OK) rc = rg_pcm_check_place(i, t, arena_bytes, err, err_len);
+    if (rc != RG_OK) return rc;
     for (uint32_t c = 0; c < t.channels; ++c) {
         RgSpecPlane &p = planes[c];
         memset(&p, 0, sizeof p);
-        p.off = t.offset_bytes + (uint64_t)c * t.frames * bps;
+        p.off = rg_pcm_plane_off(t, c);
         p.n = (uint32_t)t.frames;
         p.frames = rg_spec_frames(t.frames);
         p.format = t.format;
@@ -88,19 +70,8 @@ uint64_t rg_spec_plan(RgSpecPlane *planes, size_t n, uint64_t fmt_tile[4]) {
     return tiles;
 }
 
-// sample k of a plane as the stored pattern, S16 sign-extended (planes are only sample-aligned)
-static inline uint32_t raw_at(const unsigned char *plane, uint32_t format, uint64_t k) {
-    if (format == RG_FMT_S16_PLANAR) {
-        int16_t s;
-        memcpy(&s, plane + 2 * k, 2);
-        return (uint32_t)(int32_t)s;
-    }
-    uint32_t u;
-    memcpy(&u, plane + 4 * k, 4);
-    return u;
-}
 static inline float value_at(const unsigned char *plane, uint32_t format, uint64_t k, bool *nonfinite) {
-    const uint32_t raw = raw_at(plane, format, k);
+    const uint32_t raw = rg_pcm_raw_at(plane, format, k);
     switch (format) {
         case RG_FMT_F32_PLANAR: *nonfinite = rg_spec_nonfinite<RG_FMT_F32_PLANAR>(raw); return rg_spec_value<RG_FMT_F32_PLANAR>(raw);
         case RG_FMT_S16_PLANAR: *nonfinite = false; return rg_spec_value<RG_FMT_S16_PLANAR>(raw);
@@ -182,8 +153,8 @@ static void tile_host(const unsigned char *plane, uint32_t f0, uint32_t nf, doub
         const uint64_t base = (uint64_t)(f0 + pr) * RG_SPEC_HOP;
         bool bad_a = false, bad_b = false;
         for (uint32_t n = 0; n < RG_SPEC_FRAME; ++n) {
-            bad_a |= rg_spec_nonfinite<FMT>(raw_at(plane, FMT, base + n));
-            if (has_b) bad_b |= rg_spec_nonfinite<FMT>(raw_at(plane, FMT, base + RG_SPEC_HOP + n));
+            bad_a |= rg_spec_nonfinite<FMT>(rg_pcm_raw_at(plane, FMT, base + n));
+            if (has_b) bad_b |= rg_spec_nonfinite<FMT>(rg_pcm_raw_at(plane, FMT, base + RG_SPEC_HOP + n));
         }
         const bool use_a = !bad_a, use_b = has_b && !bad_b;
         RgSpecC v[16];
@@ -191,8 +162,8 @@ static void tile_host(const unsigned char *plane, uint32_t f0, uint32_t nf, doub
             for (uint32_t n2 = 0; n2 < 16; ++n2) {
                 const uint32_t n = 256 * n2 + t;
                 const float w = tb.window[n];
-                v[n2].x = use_a ? rg_spec_value<FMT>(raw_at(plane, FMT, base + n)) * w : 0.0f;
-                v[n2].y = use_b ? rg_spec_value<FMT>(raw_at(plane, FMT, base + RG_SPEC_HOP + n)) * w : 0.0f;
+                v[n2].x = use_a ? rg_spec_value<FMT>(rg_pcm_raw_at(plane, FMT, base + n)) * w : 0.0f;
+                v[n2].y = use_b ? rg_spec_value<FMT>(rg_pcm_raw_at(plane, FMT, base + RG_SPEC_HOP + n)) * w : 0.0f;
             }
             rg_spec_pass1(v, t, tb.tw1);
             for (uint32_t k0 = 0; k0 < 16; ++k0) x[k0 * 256 + t] = v[k0];
@@ -319,16 +290,9 @@ void rg_spec_fill(const rg_track_desc &t, uint32_t dropped_frames, const RgSpecP
 
 int rg_spec_arena_host(int route, size_t n, const rg_track_desc *descs, const rg_spectrum_opts *opts, const void *arena, size_t arena_bytes,
                        rg_spectrum_result *out, double *bands_out, char *err, size_t err_len) {
-    if (route != 0 && route != 2) {
-        snprintf(err, err_len, "rg_spectrum_arena: route %d is not a host route (0 = serial twin, 2 = the kernels' arithmetic)", route);
-        return RG_ERR_INVALID_ARG;
-    }
-    if (n && (!descs || !out || (arena_bytes && !arena))) {
-        snprintf(err, err_len, "rg_spectrum_arena: null array");
-        return RG_ERR_INVALID_ARG;
-    }
     rg_spectrum_opts o;
-    int rc = rg_spec_options(opts, &o, err, err_len);
+    int rc = rg_pcm_check_host_route("rg_spectrum_arena", "the kernels' arithmetic", route, n, descs, out, arena, arena_bytes, err, err_len);
+    if (rc == RG_OK) rc = rg_spec_options(opts, &o, err, err_len);
     if (rc != RG_OK) return rc;
     std::vector<RgSpecPlane> planes(n * RG_SPEC_MAX_CHANNELS + 1);
     size_t n_planes = 0;

@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "../../include/mp3rgain_amd_stats.h"
+#include "rg_pcm_plane.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -74,9 +75,8 @@ RG_STATS_HD float rg_stats_as_float(uint32_t u) {
 // finite floats in their own order as int32 (-0.0 sorts below +0.0), and back
 RG_STATS_HD int32_t rg_stats_fkey(uint32_t bits) { return (int32_t)(bits & 0x80000000u ? bits ^ 0x7FFFFFFFu : bits); }
 RG_STATS_HD float rg_stats_funkey(int32_t key) { return rg_stats_as_float(key < 0 ? (uint32_t)key ^ 0x7FFFFFFFu : (uint32_t)key); }
-RG_STATS_HD uint32_t rg_stats_width(uint32_t format) { return format == RG_FMT_S16_PLANAR ? 16u : 32u; }
 RG_STATS_HD int32_t rg_stats_full_scale(uint32_t format, uint32_t bits) {  // P
-    const uint32_t w = rg_stats_width(format);
+    const uint32_t w = rg_pcm_width(format);
     return (int32_t)((((uint32_t)1 << (bits - 1)) - 1u) << (w - bits));
 }
 RG_STATS_HD int32_t rg_stats_minus_full_scale(uint32_t format) { return format == RG_FMT_S16_PLANAR ? -32768 : INT32_MIN; }  // M
@@ -296,7 +296,7 @@ RG_STATS_HD rg_pcm_stats_channel rg_stats_finish(const RgStatsPart &all, uint32_
     }
     c.sum = all.sum;
     c.or_mask = all.or_mask;
-    c.effective_bits = all.or_mask ? rg_stats_width(format) - (uint32_t)__builtin_ctz(all.or_mask) : 0u;
+    c.effective_bits = all.or_mask ? rg_pcm_width(format) - (uint32_t)__builtin_ctz(all.or_mask) : 0u;
     c.clipped = all.clipped;
     RgStatsRuns r = all.clip;
     if (n && r.pre == n) {

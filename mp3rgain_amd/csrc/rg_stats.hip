@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "rg_ctx.h"
+#include "rg_pcm_seam.h"
 #include "rg_rip.h"
 #include "rg_stats.h"
 
@@ -235,37 +236,26 @@ void rg_stats_bench_free(RgStatsBench *b) {
 // ---- test seam (include/mp3rgain_amd_stats.h) -------------------------------------------------------------------------------
 extern "C" int rg_pcm_stats_arena(void *ctx, int route, size_t n, const rg_track_desc *descs, const uint32_t *bits, const rg_pcm_stats_opts *opts,
                                   const void *arena, size_t arena_bytes, rg_pcm_stats_result *out) {
-    rg_ctx *c = static_cast<rg_ctx *>(ctx);
-    char err[256] = "";
-    if (!c && route == 1) return RG_ERR_INVALID_ARG;  // the host routes need no context (their error text: rg_last_error(NULL))
-    if (route < 0 || route > 2)
-        return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_pcm_stats_arena: route %d (0 = serial host twin, 1 = kernels, 2 = folded on the host)", route);
-    if (n && (!descs || !out || (arena_bytes && !arena))) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_pcm_stats_arena: null array");
-    try {
-        if (route != 1) {
-            const int rc = rg_stats_arena_host(route, n, descs, bits, opts, arena, arena_bytes, out, err, sizeof err);
-            return rc == RG_OK ? RG_OK : rg_set_err(c, rc, "%s", err);
-        }
-        rg_pcm_stats_opts o;
-        int rc = rg_stats_options(opts, &o, err, sizeof err);
-        if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
-        std::vector<RgStatsPlane> planes(n * RG_STATS_MAX_CHANNELS + 1);
-        std::vector<uint32_t> reported(n ? n : 1);
-        size_t n_planes = 0;
+    rg_pcm_stats_opts o;
+    std::vector<RgStatsPlane> planes;
+    std::vector<uint32_t> reported;
+    size_t n_planes = 0;
+    const auto host = [&](char *err, size_t err_len) { return rg_stats_arena_host(route, n, descs, bits, opts, arena, arena_bytes, out, err, err_len); };
+    const auto plan = [&](char *err, size_t err_len) -> int {
+        int rc = rg_stats_options(opts, &o, err, err_len);
+        if (rc != RG_OK) return rc;
+        planes = std::vector<RgStatsPlane>(n * RG_STATS_MAX_CHANNELS + 1);
+        reported = std::vector<uint32_t>(n ? n : 1);
         for (size_t i = 0; i < n; ++i) {
-            rc = rg_stats_track_planes(i, descs[i], bits ? bits[i] : rg_stats_width(descs[i].format), arena_bytes, &planes[n_planes], &reported[i], err,
-                                       sizeof err);
-            if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
+            rc = rg_stats_track_planes(i, descs[i], bits ? bits[i] : rg_pcm_width(descs[i].format), arena_bytes, &planes[n_planes], &reported[i], err, err_len);
+            if (rc != RG_OK) return rc;
             n_planes += descs[i].channels;
         }
-        rc = rg_bind_device(c);
-        if (rc != RG_OK) return rc;
-        RG_HIP(c, rg_sync_slots(c, c->n_slots));
-        RG_HIP(c, c->d_arena.reserve(((arena_bytes + 15) & ~(size_t)15) + 16));  // whole 16-byte words: the staging's aligned cover
-        hipStream_t s = c->slots[0].stream;
-        if (arena_bytes) RG_HIP(c, hipMemcpyAsync(c->d_arena.p, arena, arena_bytes, hipMemcpyHostToDevice, s));
+        return RG_OK;
+    };
+    const auto device = [&](rg_ctx *c, hipStream_t s) -> int {
         std::vector<rg_pcm_stats_channel> ch(n_planes ? n_planes : 1);
-        rc = rg_stats_device(c, c->d_arena.p, planes.data(), n_planes, o, ch.data(), s);
+        const int rc = rg_stats_device(c, c->d_arena.p, planes.data(), n_planes, o, ch.data(), s);
         if (rc != RG_OK) return rc;
         size_t at = 0;
         for (size_t i = 0; i < n; ++i) {
@@ -273,9 +263,8 @@ extern "C" int rg_pcm_stats_arena(void *ctx, int route, size_t n, const rg_track
             at += descs[i].channels;
         }
         return RG_OK;
-    } catch (const std::bad_alloc &) {
-        return rg_set_err(c, RG_ERR_NOMEM, "out of memory");
-    }
+    };
+    return rg_pcm_arena_seam(ctx, route, "rg_pcm_stats_arena", "folded", n, descs, out, arena, arena_bytes, host, plan, device);
 }
 
 // ---- measurement hook (tools/pcm_stats_rate.py) -----------------------------------------------------------------------------
@@ -300,7 +289,7 @@ extern "C" int rg_pcm_stats_rate(void *ctx, size_t n, uint64_t frames, uint32_t 
         return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_pcm_stats_rate: bad arguments");
     int rc = rg_bind_device(c);
     if (rc != RG_OK) return rc;
-    const uint32_t bps = rg_stats_width(format) / 8;
+    const uint32_t bps = rg_pcm_width(format) / 8;
     const size_t track_bytes = (size_t)frames * 2 * bps, stride = (track_bytes + 15) & ~(size_t)15, total = n * stride;
     const rg_pcm_stats_opts o{RG_STATS_MIN_CLIP_RUN, RG_STATS_MIN_ZERO_RUN};
     unsigned char *d_arena = nullptr, *d = nullptr;
@@ -319,7 +308,7 @@ extern "C" int rg_pcm_stats_rate(void *ctx, size_t n, uint64_t frames, uint32_t 
             t.channels = 2;
             t.format = (uint16_t)format;
             uint32_t reported;
-            if (rg_stats_track_planes(i, t, rg_stats_width(format), total, &planes[2 * i], &reported, err, sizeof err) != RG_OK ||
+            if (rg_stats_track_planes(i, t, rg_pcm_width(format), total, &planes[2 * i], &reported, err, sizeof err) != RG_OK ||
                 (rip_ms && rg_rip_track_record(i, t, (i == 0 ? RG_RIP_FIRST_TRACK : 0u) | (i + 1 == n ? RG_RIP_LAST_TRACK : 0u), total, &recs[i], err,
                                                sizeof err) != RG_OK))
                 return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_pcm_stats_rate: %s", err);

@@ -19,36 +19,20 @@ int rg_stats_options(const rg_pcm_stats_opts *opts, rg_pcm_stats_opts *out, char
 
 int rg_stats_track_planes(size_t i, const rg_track_desc &t, uint32_t bits, size_t arena_bytes, RgStatsPlane *planes, uint32_t *bits_out, char *err,
                           size_t err_len) {
-    if (t.format != RG_FMT_F32_PLANAR && t.format != RG_FMT_S16_PLANAR && t.format != RG_FMT_S32_PLANAR) {
-        snprintf(err, err_len, "track %zu: format %u is not a planar PCM format", i, (unsigned)t.format);
-        return RG_ERR_FORMAT;
-    }
-    if (t.channels < 1 || t.channels > RG_STATS_MAX_CHANNELS) {
-        snprintf(err, err_len, "track %zu: %u channel(s), pcm stats take 1 to %u", i, (unsigned)t.channels, RG_STATS_MAX_CHANNELS);
-        return RG_ERR_FORMAT;
-    }
-    if (t.frames >= ((uint64_t)1 << 32)) {
-        snprintf(err, err_len, "track %zu: %llu frames, pcm stats take fewer than 2^32", i, (unsigned long long)t.frames);
-        return RG_ERR_FORMAT;
-    }
-    const uint32_t w = rg_stats_width(t.format), bps = w / 8;
+    int rc = rg_pcm_check_format(i, t, RG_STATS_MAX_CHANNELS, "pcm stats take", err, err_len);
+    if (rc != RG_OK) return rc;
+    const uint32_t w = rg_pcm_width(t.format);
     const bool is_float = t.format == RG_FMT_F32_PLANAR;
     if (!is_float && (bits < 1 || bits > w)) {
         snprintf(err, err_len, "track %zu: %u bits in a %u-bit container", i, bits, w);
         return RG_ERR_INVALID_ARG;
     }
-    if (t.offset_bytes % bps) {
-        snprintf(err, err_len, "track %zu: offset %llu is not sample-aligned", i, (unsigned long long)t.offset_bytes);
-        return RG_ERR_INVALID_ARG;
-    }
-    if (t.offset_bytes > arena_bytes || t.frames > (arena_bytes - t.offset_bytes) / ((size_t)bps * t.channels)) {
-        snprintf(err, err_len, "track %zu: its planes reach beyond the arena (%zu bytes)", i, arena_bytes);
-        return RG_ERR_INVALID_ARG;
-    }
+    rc = rg_pcm_check_place(i, t, arena_bytes, err, err_len);
+    if (rc != RG_OK) return rc;
     for (uint32_t c = 0; c < t.channels; ++c) {
         RgStatsPlane &p = planes[c];
         memset(&p, 0, sizeof p);
-        p.off = t.offset_bytes + (uint64_t)c * t.frames * bps;
+        p.off = rg_pcm_plane_off(t, c);
         p.n = (uint32_t)t.frames;
         p.run = 1;
         p.format = t.format;
@@ -75,18 +59,6 @@ uint64_t rg_stats_plan(RgStatsPlane *planes, size_t n, uint64_t fmt_tile[4]) {
     }
     fmt_tile[3] = tiles;
     return tiles;
-}
-
-// sample k of a plane as the stored pattern, S16 sign-extended (planes are only sample-aligned)
-static inline uint32_t raw_at(const unsigned char *plane, uint32_t format, uint64_t k) {
-    if (format == RG_FMT_S16_PLANAR) {
-        int16_t s;
-        memcpy(&s, plane + 2 * k, 2);
-        return (uint32_t)(int32_t)s;
-    }
-    uint32_t u;
-    memcpy(&u, plane + 4 * k, 4);
-    return u;
 }
 
 // ---- route 0: the definitions ------------------------------------------------------------------------------------------------
@@ -119,7 +91,7 @@ rg_pcm_stats_channel rg_stats_serial_host(const unsigned char *arena, const RgSt
         if (zero_len > c.longest_zero_run) c.longest_zero_run = (uint32_t)zero_len;
     };
     for (uint64_t k = 0; k < N; ++k) {
-        const uint32_t raw = raw_at(plane, p.format, k);
+        const uint32_t raw = rg_pcm_raw_at(plane, p.format, k);
         int cls = 0;
         bool zero = false;
         if (is_float) {
@@ -170,7 +142,7 @@ rg_pcm_stats_channel rg_stats_serial_host(const unsigned char *arena, const RgSt
     if (c.or_mask) {
         uint32_t low = 0;
         while (!((c.or_mask >> low) & 1u)) ++low;
-        c.effective_bits = rg_stats_width(p.format) - low;
+        c.effective_bits = rg_pcm_width(p.format) - low;
     }
     return c;
 }
@@ -190,7 +162,7 @@ static void tile_parts(const unsigned char *plane, const RgStatsPlane &p, const 
         uint32_t a;
         const uint32_t n = rg_stats_lane_chunk(wlen, lane, &a);
         const uint64_t k0 = (uint64_t)wstart + a;
-        rg_stats_chunk<FMT, ANY>([&](uint32_t j) { return raw_at(plane, FMT, k0 + j); }, n, p.P, p.M, o.min_clip_run, o.min_zero_run, &v[lane]);
+        rg_stats_chunk<FMT, ANY>([&](uint32_t j) { return rg_pcm_raw_at(plane, FMT, k0 + j); }, n, p.P, p.M, o.min_clip_run, o.min_zero_run, &v[lane]);
     }
 }
 
@@ -255,22 +227,15 @@ void rg_stats_fill(const rg_track_desc &t, uint32_t bits_reported, uint32_t drop
 
 int rg_stats_arena_host(int route, size_t n, const rg_track_desc *descs, const uint32_t *bits, const rg_pcm_stats_opts *opts, const void *arena,
                         size_t arena_bytes, rg_pcm_stats_result *out, char *err, size_t err_len) {
-    if (route != 0 && route != 2) {
-        snprintf(err, err_len, "rg_pcm_stats_arena: route %d is not a host route (0 = serial twin, 2 = folded)", route);
-        return RG_ERR_INVALID_ARG;
-    }
-    if (n && (!descs || !out || (arena_bytes && !arena))) {
-        snprintf(err, err_len, "rg_pcm_stats_arena: null array");
-        return RG_ERR_INVALID_ARG;
-    }
     rg_pcm_stats_opts o;
-    int rc = rg_stats_options(opts, &o, err, err_len);
+    int rc = rg_pcm_check_host_route("rg_pcm_stats_arena", "folded", route, n, descs, out, arena, arena_bytes, err, err_len);
+    if (rc == RG_OK) rc = rg_stats_options(opts, &o, err, err_len);
     if (rc != RG_OK) return rc;
     std::vector<RgStatsPlane> planes(n * RG_STATS_MAX_CHANNELS + 1);
     std::vector<uint32_t> reported(n ? n : 1);
     size_t n_planes = 0;
     for (size_t i = 0; i < n; ++i) {
-        rc = rg_stats_track_planes(i, descs[i], bits ? bits[i] : rg_stats_width(descs[i].format), arena_bytes, &planes[n_planes], &reported[i], err, err_len);
+        rc = rg_stats_track_planes(i, descs[i], bits ? bits[i] : rg_pcm_width(descs[i].format), arena_bytes, &planes[n_planes], &reported[i], err, err_len);
         if (rc != RG_OK) return rc;
         n_planes += descs[i].channels;
     }

@@ -939,6 +939,21 @@ class Analyzer:
         if rc != _capi.RG_OK:
             raise ReplayGainError(rc, self._lib.rg_last_error(self._ctx).decode())
 
+    @staticmethod
+    def _file_args(files, record):
+        """What a per-file call takes -> (`files` as a c_char_p array, zeroed records of ctypes type `record`), one entry per
+        file and never fewer than one."""
+        n = max(1, len(files))
+        return (C.c_char_p * n)(*[os.fsencode(os.fspath(f)) for f in files]), (record * n)()
+
+    def _file_records(self, out, n):
+        """(record, its ReplayGainError or None) for each of the `n` files of the per-file call that has just filled `out`."""
+        for i in range(n):
+            err = None
+            if out[i].status != 0:
+                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
+            yield out[i], err
+
     @property
     def handle(self):
         return self._ctx
@@ -1348,30 +1363,20 @@ class Analyzer:
         signature -> [FlacVerifyResult]; a file that cannot be decoded carries its ReplayGainError in `.error`."""
         from . import flacdec
 
-        L = flacdec._lib()
         n = len(files)
-        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
-        out = (flacdec.FlacVerifyRecord * max(1, n))()
-        self._check(L.rg_flac_verify(self._ctx, paths, n, out))
-        res = []
-        for i in range(n):
-            r = out[i]
-            err = None
-            if r.status != 0:
-                err = ReplayGainError(int(r.status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
-            res.append(FlacVerifyResult(bool(r.flags & flacdec.VERIFY_HAS_SIGNATURE), bool(r.flags & flacdec.VERIFY_MD5_MATCH),
-                                        bool(r.flags & flacdec.VERIFY_LENGTH_MATCH), bool(r.flags & flacdec.VERIFY_COMPLETE),
-                                        int(r.frames), int(r.total_samples), int(r.audio_frames), int(r.dropped_frames),
-                                        bytes(r.md5_stream), bytes(r.md5_decoded), err))
-        return res
+        paths, out = self._file_args(files, flacdec.FlacVerifyRecord)
+        self._check(flacdec._lib().rg_flac_verify(self._ctx, paths, n, out))
+        return [FlacVerifyResult(bool(r.flags & flacdec.VERIFY_HAS_SIGNATURE), bool(r.flags & flacdec.VERIFY_MD5_MATCH),
+                                 bool(r.flags & flacdec.VERIFY_LENGTH_MATCH), bool(r.flags & flacdec.VERIFY_COMPLETE),
+                                 int(r.frames), int(r.total_samples), int(r.audio_frames), int(r.dropped_frames),
+                                 bytes(r.md5_stream), bytes(r.md5_decoded), err) for r, err in self._file_records(out, n)]
 
     def verify_flac_raw(self, files) -> bytes:
         """verify_flac's rg_flac_verify_result array as the C call left it (tests compare routes byte for byte)."""
         from . import flacdec
 
         n = len(files)
-        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
-        out = (flacdec.FlacVerifyRecord * max(1, n))()
+        paths, out = self._file_args(files, flacdec.FlacVerifyRecord)
         self._check(flacdec._lib().rg_flac_verify(self._ctx, paths, n, out))
         return bytes(out)[:n * C.sizeof(flacdec.FlacVerifyRecord)]
 
@@ -1389,24 +1394,17 @@ class Analyzer:
 
     def _rip_call(self, files, disc, flags):
         n = len(files)
-        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        paths, out = self._file_args(files, _capi.RipRecord)
         fl = self._rip_flags(n, disc, flags)
-        out = (_capi.RipRecord * max(1, n))()
         self._check(self._lib.rg_rip_checksums(self._ctx, paths, n, (C.c_uint32 * max(1, n))(*fl), out))
         return out, fl
 
     def _rip_results(self, out, fl, n):
-        res = []
-        for i in range(n):
-            r = out[i]
-            err = None
-            if r.status != 0:
-                err = ReplayGainError(int(r.status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
-            res.append(RipChecksums(int(r.crc32), int(r.crc32_nonnull), int(r.arv1), int(r.arv2), int(r.frames), int(r.null_samples),
-                                    int(r.sample_rate), int(r.dropped_frames), bool(r.flags & _capi.RIP_CD_RATE),
-                                    bool(r.flags & _capi.RIP_CD_FRAMES), bool(r.flags & _capi.RIP_COMPLETE),
-                                    bool(fl[i] & _capi.RIP_FIRST_TRACK), bool(fl[i] & _capi.RIP_LAST_TRACK), err))
-        return res
+        return [RipChecksums(int(r.crc32), int(r.crc32_nonnull), int(r.arv1), int(r.arv2), int(r.frames), int(r.null_samples),
+                             int(r.sample_rate), int(r.dropped_frames), bool(r.flags & _capi.RIP_CD_RATE),
+                             bool(r.flags & _capi.RIP_CD_FRAMES), bool(r.flags & _capi.RIP_COMPLETE),
+                             bool(f & _capi.RIP_FIRST_TRACK), bool(f & _capi.RIP_LAST_TRACK), err)
+                for (r, err), f in zip(self._file_records(out, n), fl)]
 
     def rip_checksums(self, files, disc: bool = True, flags=None) -> list:
         """rg_rip_checksums: `files` (16-bit stereo WAV or FLAC) decoded by the route the analysis uses and, from the PCM where
@@ -1424,9 +1422,8 @@ class Analyzer:
 
     def _rip_offsets_call(self, files, disc, flags, radius):
         n = len(files)
-        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
+        paths, out = self._file_args(files, _capi.RipRecord)
         fl = self._rip_flags(n, disc, flags)
-        out = (_capi.RipRecord * max(1, n))()
         width = 2 * max(0, min(int(radius), _capi.RIP_OFFSET_MAX)) + 1
         v1, v2 = np.full((n, width), 0xA5A5A5A5, dtype=np.uint32), np.full((n, width), 0xA5A5A5A5, dtype=np.uint32)
         u32p = C.POINTER(C.c_uint32)
@@ -1466,10 +1463,8 @@ class Analyzer:
         return rip_checksums_arena(self._ctx, route, descs, flags, arena)
 
     def _pcm_stats_call(self, files, min_clip_run, min_zero_run):
-        n = len(files)
-        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
-        out = (_capi.PcmStatsRecord * max(1, n))()
-        self._check(self._lib.rg_pcm_stats(self._ctx, paths, n, _stats_opts(min_clip_run, min_zero_run), out))
+        paths, out = self._file_args(files, _capi.PcmStatsRecord)
+        self._check(self._lib.rg_pcm_stats(self._ctx, paths, len(files), _stats_opts(min_clip_run, min_zero_run), out))
         return out
 
     def pcm_stats(self, files, min_clip_run: int = _capi.STATS_MIN_CLIP_RUN, min_zero_run: int = _capi.STATS_MIN_ZERO_RUN) -> list:
@@ -1478,13 +1473,7 @@ class Analyzer:
         sum, the bits in use, minimum and maximum -> [PcmStats].  A file that takes no part carries its ReplayGainError in
         `.error`."""
         out = self._pcm_stats_call(files, min_clip_run, min_zero_run)
-        res = []
-        for i in range(len(files)):
-            err = None
-            if out[i].status != 0:
-                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
-            res.append(pcm_stats_from_record(out[i], err))
-        return res
+        return [pcm_stats_from_record(r, err) for r, err in self._file_records(out, len(files))]
 
     def pcm_stats_raw(self, files, min_clip_run=None, min_zero_run=None) -> bytes:
         """pcm_stats' rg_pcm_stats_result array as the C call left it (tests compare routes byte for byte)."""
@@ -1502,10 +1491,8 @@ class Analyzer:
         return pcm_stats_kernel_shape()
 
     def _dr_call(self, files, block_frames, top_permille):
-        n = len(files)
-        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
-        out = (_capi.DrRecord * max(1, n))()
-        self._check(self._lib.rg_dynamic_range(self._ctx, paths, n, _dr_opts(block_frames, top_permille), out))
+        paths, out = self._file_args(files, _capi.DrRecord)
+        self._check(self._lib.rg_dynamic_range(self._ctx, paths, len(files), _dr_opts(block_frames, top_permille), out))
         return out
 
     def dynamic_range(self, files, block_frames=None, top_permille=None) -> list:
@@ -1514,13 +1501,7 @@ class Analyzer:
         and the second-highest block peak, and from them the DR figure -> [DynamicRange].  A file that takes no part carries its
         ReplayGainError in `.error`."""
         out = self._dr_call(files, block_frames, top_permille)
-        res = []
-        for i in range(len(files)):
-            err = None
-            if out[i].status != 0:
-                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
-            res.append(dynamic_range_from_record(out[i], err))
-        return res
+        return [dynamic_range_from_record(r, err) for r, err in self._file_records(out, len(files))]
 
     def dynamic_range_raw(self, files, block_frames=None, top_permille=None) -> bytes:
         """dynamic_range's rg_dr_result array as the C call left it (tests compare routes byte for byte)."""
@@ -1538,10 +1519,8 @@ class Analyzer:
         return dr_kernel_shape(fmt)
 
     def _ancestry_call(self, files, segments, granules, z_min, iso_min, active_floor):
-        n = len(files)
-        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
-        out = (_capi.AncestryRecord * max(1, n))()
-        self._check(self._lib.rg_ancestry(self._ctx, paths, n, _ancestry_opts(segments, granules, z_min, iso_min, active_floor), out))
+        paths, out = self._file_args(files, _capi.AncestryRecord)
+        self._check(self._lib.rg_ancestry(self._ctx, paths, len(files), _ancestry_opts(segments, granules, z_min, iso_min, active_floor), out))
         return out
 
     def ancestry(self, files, segments=None, granules=None, z_min=None, iso_min=None, active_floor=None) -> list:
@@ -1550,13 +1529,7 @@ class Analyzer:
         a stereo file): the alignment at which the most lines fall to zero, how far it stands out, and whether that is an MP3
         granule grid -> [Ancestry].  A file that takes no part carries its ReplayGainError in `.error`."""
         out = self._ancestry_call(files, segments, granules, z_min, iso_min, active_floor)
-        res = []
-        for i in range(len(files)):
-            err = None
-            if out[i].status != 0:
-                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
-            res.append(ancestry_from_record(out[i], err))
-        return res
+        return [ancestry_from_record(r, err) for r, err in self._file_records(out, len(files))]
 
     def ancestry_raw(self, files, segments=None, granules=None, z_min=None, iso_min=None, active_floor=None) -> bytes:
         """ancestry's rg_ancestry_result array as the C call left it (tests compare routes byte for byte)."""
@@ -1575,8 +1548,7 @@ class Analyzer:
 
     def _spectrum_call(self, files, edge_db, min_cutoff_hz, bands):
         n = len(files)
-        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
-        out = (_capi.SpectrumRecord * max(1, n))()
+        paths, out = self._file_args(files, _capi.SpectrumRecord)
         e = _spectrum_bands(n) if bands else None
         self._check(self._lib.rg_spectrum(self._ctx, paths, n, _spectrum_opts(edge_db, min_cutoff_hz), out,
                                           e.ctypes.data_as(C.POINTER(C.c_double)) if bands else None))
@@ -1588,13 +1560,7 @@ class Analyzer:
         the steepness of the edge there -> [Spectrum], with the band energies in every channel's `.bands` when `bands` is true.
         A file that takes no part carries its ReplayGainError in `.error`."""
         out, e = self._spectrum_call(files, edge_db, min_cutoff_hz, bands)
-        res = []
-        for i in range(len(files)):
-            err = None
-            if out[i].status != 0:
-                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
-            res.append(spectrum_from_record(out[i], err, e[i] if bands else None))
-        return res
+        return [spectrum_from_record(r, err, e[i] if bands else None) for i, (r, err) in enumerate(self._file_records(out, len(files)))]
 
     def spectrum_raw(self, files, edge_db=None, min_cutoff_hz=None):
         """spectrum's rg_spectrum_result array and band energies as the C call left them -> (bytes, bytes)."""
@@ -1621,25 +1587,16 @@ class Analyzer:
         bare MPEG Layer III stream or cannot be opened carries its ReplayGainError in `.error`."""
         from . import mp3verify
 
-        n = len(files)
-        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
-        out = (mp3verify.Mp3VerifyRecord * max(1, n))()
-        self._check(mp3verify._lib().rg_mp3_verify(self._ctx, paths, n, out))
-        res = []
-        for i in range(n):
-            err = None
-            if out[i].status != 0:
-                err = ReplayGainError(int(out[i].status), self._lib.rg_tracks_error(self._ctx, i).decode("utf-8", "replace"))
-            res.append(mp3verify.result_of(out[i], err))
-        return res
+        paths, out = self._file_args(files, mp3verify.Mp3VerifyRecord)
+        self._check(mp3verify._lib().rg_mp3_verify(self._ctx, paths, len(files), out))
+        return [mp3verify.result_of(r, err) for r, err in self._file_records(out, len(files))]
 
     def verify_mp3_raw(self, files) -> bytes:
         """verify_mp3's rg_mp3_verify_result array as the C call left it (tests compare routes byte for byte)."""
         from . import mp3verify
 
         n = len(files)
-        paths = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in files])
-        out = (mp3verify.Mp3VerifyRecord * max(1, n))()
+        paths, out = self._file_args(files, mp3verify.Mp3VerifyRecord)
         self._check(mp3verify._lib().rg_mp3_verify(self._ctx, paths, n, out))
         return bytes(out)[:n * C.sizeof(mp3verify.Mp3VerifyRecord)]
 
