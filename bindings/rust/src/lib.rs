@@ -549,6 +549,86 @@ pub mod replaygain {
     }
 }
 
+/// The duplicate finder of `include/mp3rgain_amd_fingerprint.h`: which of these WAV, FLAC or MP3 files are the same recording?  A
+/// sub-band-difference fingerprint per file (a 32-bit code per 512 samples) and a match of every pair of files at every lag within
+/// a radius, both on the GPU.  The fingerprint is a convention of that header, compatible with no other fingerprint, and its
+/// threshold was measured on this project's own synthetic material only; matching across sample rates, rates from 96 kHz up,
+/// time-stretched or pitch-shifted copies and excerpts offset by more than the radius are not found.  A module of its own, as
+/// [`ancestry`] is.  `tests/test_rust_fingerprint_layout.py` compares these declarations with the header.
+pub mod fingerprint {
+    use super::ffi::RgCtx;
+    use std::os::raw::{c_char, c_int};
+
+    pub const FP_SHORT: u32 = 1;
+    pub const FP_RATE: u32 = 2;
+    pub const FP_NONFINITE: u32 = 4;
+    pub const FP_COMPLETE: u32 = 8;
+    pub const FP_PAIR_COMPARED: u32 = 1;
+    pub const FP_PAIR_MATCH: u32 = 2;
+    pub const FP_PAIR_SKIPPED: u32 = 4;
+    pub const FP_PAIR_PROBE_J: u32 = 8;
+    pub const FP_MAX_CHANNELS: usize = 8;
+    pub const FP_FRAME: u32 = 4096;
+    pub const FP_HOP: u32 = 512;
+    pub const FP_BANDS: u32 = 33;
+    /// `RG_FP_BLOCK`, `RG_FP_PROBES`, `RG_FP_RADIUS`, `RG_FP_MAX_BER_PERMILLE`: what a zero in the options means
+    pub const FP_BLOCK: u32 = 256;
+    pub const FP_PROBES: u32 = 8;
+    pub const FP_RADIUS: u32 = 512;
+    pub const FP_MAX_BER_PERMILLE: u32 = 316;
+    pub const FP_MAX_BLOCK: u32 = 4096;
+    pub const FP_MAX_PROBES: u32 = 64;
+    pub const FP_MAX_RADIUS: u32 = 2047;
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_fingerprint_opts`: a zero field means its default; a null pointer means all defaults
+    pub struct RgFingerprintOpts {
+        pub block: u32,
+        pub probes: u32,
+        pub radius: u32,
+        pub max_ber_permille: u32,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_fingerprint_result`
+    pub struct RgFingerprintResult {
+        pub status: i32,
+        pub flags: u32,
+        pub frames: u64,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub format: u32,
+        pub dropped_frames: u32,
+        pub fp_frames: u32,
+        pub codes: u32,
+        pub nonfinite_frames: u32,
+        pub group: u32,
+        pub matches: u32,
+        pub reserved: u32,
+        pub codes_at: u64,
+        pub frames_at: u64,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_fingerprint_pair`: a matching pair, files `i < j`; `lag` in codes of 512 samples, of the longer file against the shorter
+    pub struct RgFingerprintPair {
+        pub i: u32,
+        pub j: u32,
+        pub errors: u32,
+        pub bits: u32,
+        pub lag: i32,
+        pub flags: u32,
+    }
+
+    extern "C" {
+        pub fn rg_same_recording(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, opts: *const RgFingerprintOpts, out: *mut RgFingerprintResult,
+                                 pairs: *mut RgFingerprintPair, max_pairs: usize, n_pairs: *mut usize, codes_out: *mut u32, codes_cap: usize) -> c_int;
+    }
+}
+
 /// The lossy ancestry scan of `include/mp3rgain_amd_ancestry.h`: is this PCM a decoded MPEG Layer III stream?  Every view of a
 /// WAV, FLAC or MP3 file (each channel; mid and side of a stereo file) goes through the MP3 encoder's hybrid filterbank at all
 /// 576 alignments, and on the stream's granule grid a large share of the spectral lines falls to zero.  The verdict is a

@@ -20,6 +20,7 @@ from .replaygain import (  # noqa: F401
     ChannelSpectrum,
     ChannelStats,
     DynamicRange,
+    Fingerprint,
     FlacVerifyResult,
     Node,
     PcmStats,
@@ -32,6 +33,7 @@ from .replaygain import (  # noqa: F401
     ReplayGainResult,
     RipChecksums,
     RipOffsetSignatures,
+    SamePair,
     Spectrum,
     album_dr,
     ancestry_arena,
@@ -43,6 +45,13 @@ from .replaygain import (  # noqa: F401
     dr_kernel_shape,
     dynamic_range_from_record,
     find_peak_amplitude,
+    fingerprint_arena,
+    fingerprint_codes,
+    fingerprint_edges,
+    fingerprint_from_record,
+    fingerprint_groups,
+    fingerprint_kernel_shape,
+    fingerprint_match_codes,
     is_available,
     pcm_stats_arena,
     pcm_stats_kernel_shape,

@@ -480,6 +480,58 @@ ANCESTRY_SYMBOLS = [
     ("rg_ancestry_rate", _int, [_vp, _sz, _u64, _P(AncestryOpts), _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_sz), _P(_dbl)]),
 ]
 
+# include/mp3rgain_amd_fingerprint.h (duplicate recordings: fingerprints and the pair match)
+FP_SHORT, FP_RATE, FP_NONFINITE, FP_COMPLETE = 1, 2, 4, 8
+FP_PAIR_COMPARED, FP_PAIR_MATCH, FP_PAIR_SKIPPED, FP_PAIR_PROBE_J = 1, 2, 4, 8
+FP_MAX_CHANNELS, FP_FRAME, FP_HOP, FP_BANDS = 8, 4096, 512, 33
+FP_BLOCK, FP_PROBES, FP_RADIUS, FP_MAX_BER_PERMILLE = 256, 8, 512, 316
+FP_MAX_BLOCK, FP_MAX_PROBES, FP_MAX_RADIUS = 4096, 64, 2047
+
+
+class FingerprintOpts(C.Structure):  # rg_fingerprint_opts
+    _fields_ = [("block", C.c_uint32), ("probes", C.c_uint32), ("radius", C.c_uint32), ("max_ber_permille", C.c_uint32)]
+
+
+class FingerprintRecord(C.Structure):  # rg_fingerprint_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("fp_frames", C.c_uint32),
+        ("codes", C.c_uint32),
+        ("nonfinite_frames", C.c_uint32),
+        ("group", C.c_uint32),
+        ("matches", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("codes_at", C.c_uint64),
+        ("frames_at", C.c_uint64),
+    ]
+
+
+class FingerprintPairRecord(C.Structure):  # rg_fingerprint_pair_record
+    _fields_ = [("errors", C.c_uint32), ("bits", C.c_uint32), ("lag", C.c_int32), ("flags", C.c_uint32)]
+
+
+class FingerprintPair(C.Structure):  # rg_fingerprint_pair
+    _fields_ = [("i", C.c_uint32), ("j", C.c_uint32), ("errors", C.c_uint32), ("bits", C.c_uint32), ("lag", C.c_int32), ("flags", C.c_uint32)]
+
+
+FINGERPRINT_SYMBOLS = [
+    ("rg_fingerprint_edges", _int, [_u32, _P(_u32)]),
+    ("rg_same_recording", _int, [_vp, _P(C.c_char_p), _sz, _P(FingerprintOpts), _P(FingerprintRecord), _P(FingerprintPair), _sz, _P(_sz),
+                                 _P(_u32), _sz]),
+    ("rg_fingerprint_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _vp, _sz, _P(FingerprintRecord), _P(_u32), _P(C.c_float)]),
+    ("rg_fingerprint_match_codes", _int, [_vp, _int, _sz, _P(_u32), _P(_u32), _P(_u32), _P(FingerprintOpts), _P(FingerprintPairRecord)]),
+    ("rg_fingerprint_groups", _sz, [_sz, _P(FingerprintPairRecord), _P(_u32), _P(_u32)]),
+    ("rg_fingerprint_kernel_shape", _int, [_P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_fingerprint_rate", _int, [_vp, _sz, _u64, _P(FingerprintOpts), _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl),
+                                   _P(_sz)]),
+]
+
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions
 NODE_OPEN = C.CFUNCTYPE(_vp, _int, _vp)
 NODE_CLOSE = C.CFUNCTYPE(None, _vp, _vp)
@@ -520,7 +572,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + ANCESTRY_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

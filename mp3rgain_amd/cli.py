@@ -19,7 +19,7 @@ from dataclasses import dataclass, field
 from pathlib import Path
 from typing import List, Optional, Tuple
 
-from . import mp3gain, mp4meta
+from . import _capi, mp3gain, mp4meta
 from . import replaygain as rgmod
 
 VERSION = "0.1.0"
@@ -79,6 +79,9 @@ class Options:  # src/main.rs:65-96
     ancestry: bool = False   # this façade only (--ancestry): is this PCM a decoded MP3?  The granule grid, per file and view
     ancestry_segments: Optional[int] = None  # with --ancestry (--ancestry-segments S): segments per file, 0 = the whole file
     ancestry_granules: Optional[int] = None  # with --ancestry (--ancestry-granules G): granules per segment
+    duplicates: bool = False  # this façade only (--duplicates): which of these files are the same recording?  Fingerprints and every pair
+    dup_radius: Optional[float] = None  # with --duplicates (--dup-radius SECONDS): the largest offset looked for, in seconds at 44.1 kHz
+    dup_ber: Optional[int] = None  # with --duplicates (--dup-ber PERMILLE): the share of differing bits up to which a pair matches
     files: List[Path] = field(default_factory=list)
 
 
@@ -177,6 +180,12 @@ def parse_args(args: List[str], out, err) -> Options:
             o.ancestry_segments = _parse_int(need("--ancestry-segments", "--ancestry-segments requires an argument"), "invalid segment count", 32, signed=False)
         elif arg == "--ancestry-granules":
             o.ancestry_granules = _parse_int(need("--ancestry-granules", "--ancestry-granules requires an argument"), "invalid granule count", 32, signed=False)
+        elif arg == "--duplicates":  # not in the reference: a command of its own, like --stats
+            o.duplicates = True
+        elif arg == "--dup-radius":
+            o.dup_radius = _parse_positive(need("--dup-radius", "--dup-radius requires an argument"), "invalid radius")
+        elif arg == "--dup-ber":
+            o.dup_ber = _parse_int(need("--dup-ber", "--dup-ber requires an argument"), "invalid per mille value", 32, signed=False)
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -311,7 +320,27 @@ def parse_args(args: List[str], out, err) -> Options:
                                         ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
         if others:
             raise CliError(f"--ancestry is a command of its own and cannot be combined with {', '.join(others)}")
+    if o.dup_radius is not None and not o.duplicates:
+        raise CliError("--dup-radius requires --duplicates")
+    if o.dup_ber is not None and not o.duplicates:
+        raise CliError("--dup-ber requires --duplicates")
+    if o.dup_ber is not None and not 1 <= o.dup_ber <= 1000:
+        raise CliError(f"--dup-ber takes 1 to 1000 per mille: {o.dup_ber}")
+    if o.dup_radius is not None and not 1 <= dup_radius_codes(o.dup_radius) <= _capi.FP_MAX_RADIUS:
+        raise CliError(f"--dup-radius takes {512 / 44100:.3f} to {_capi.FP_MAX_RADIUS * 512 / 44100:.1f} seconds: {o.dup_radius}")
+    if o.duplicates:
+        others = [name for name, on in (("--verify", o.verify), ("--rip", o.rip), ("--stats", o.stats), ("--spectrum", o.spectrum), ("--dr", o.dr),
+                                        ("--ancestry", o.ancestry), ("--r128", o.r128), ("-x", o.max_amplitude_only), ("-r", o.track_gain),
+                                        ("-a", o.album_gain), ("-u", o.undo), ("-g", o.gain_steps is not None), ("-l", o.channel_gain is not None),
+                                        ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
+        if others:
+            raise CliError(f"--duplicates is a command of its own and cannot be combined with {', '.join(others)}")
     return o
+
+
+def dup_radius_codes(seconds: float) -> int:
+    """--dup-radius in codes of 512 samples, taken at 44.1 kHz."""
+    return int(round(seconds * 44100.0 / 512.0))
 
 
 # ---- JSON shapes (src/main.rs:101-165): field order of the structs, None fields skipped -----------------------
@@ -550,6 +579,8 @@ class Cli:
             return self.cmd_dr()
         if o.ancestry:
             return self.cmd_ancestry()
+        if o.duplicates:
+            return self.cmd_duplicates()
         if o.max_amplitude_only:
             return self.cmd_max_amplitude()
         if o.stored_tag_mode == "delete":
@@ -1001,6 +1032,74 @@ class Cli:
                                f"  z {v.z:.1f}  x{v.iso:.2f}" + ("  *" if v.flagged else "") + (f"  non-finite {v.nonfinite}" if v.nonfinite else ""))
         if o.output_format == "json":
             _print_json(self.out, files=results, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+        return 1 if failed else 0
+
+    # ---- --duplicates (not in the reference): which of these files are the same recording?  On the GPU ---------------------
+    def cmd_duplicates(self) -> int:
+        """Every file decoded by the route the analysis uses and fingerprinted on the first GPU, then every pair matched at every
+        lag within the radius (rg_same_recording).  Text: a paragraph per group of more than one file, every member with its
+        lag in seconds and the share of differing bits against the group's first file (`via` another member when the two did not
+        match directly), and a closing `N files, G groups of duplicates`.  The fingerprint and the threshold are conventions
+        of this project, measured on its own synthetic material only.  A report: exit status 1 only when a file fails or has
+        dropped frames.  TSV, no header: a row per file `file, group (the index of its first member), verdicts, codes,
+        matches, frames, sample rate, dropped frames` (a failing file: `file, error text`) and a row per matching pair `"pair",
+        file i, file j, lag of j in seconds, differing bits, bits, per mille`."""
+        o = self.o
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        radius = None if o.dup_radius is None else dup_radius_codes(o.dup_radius)
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            recs, pairs, groups = an.same_recording(o.files, radius=radius, max_ber_permille=o.dup_ber)
+        if self.talk:
+            self.p(f"mp3rgain duplicate search among {len(o.files)} file(s): sub-band fingerprints, every pair at every offset"
+                   " (a convention of this project, compatible with no other fingerprint)")
+            self.p()
+        failed = sum(1 for r in recs if r.error is not None or not r.complete)
+        by = {(p.i, p.j): p for p in pairs}
+
+        def against(first, k):  # -> (lag of file k against `first` in seconds, share of differing bits) or None
+            p = by.get((first, k))
+            return None if p is None else (p.lag_of_j * 512.0 / recs[k].sample_rate, p.ber)
+
+        if o.output_format == "json":
+            files = []
+            for i, (file, r) in enumerate(zip(o.files, recs)):
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                else:
+                    d.update(verdicts=r.verdicts, group=r.group, matches=r.matches, codes=r.codes, frames=r.frames, sample_rate=r.sample_rate,
+                             channels=r.channels, dropped_frames=r.dropped_frames, nonfinite_frames=r.nonfinite_frames, complete=r.complete)
+                files.append(d)
+            _print_json(self.out, files=files,
+                        pairs=[{"i": p.i, "j": p.j, "lag_codes": p.lag_of_j, "lag_seconds": p.lag_of_j * 512.0 / recs[p.j].sample_rate,
+                                "errors": p.errors, "bits": p.bits, "ber": p.ber} for p in pairs],
+                        groups=[[str(o.files[k]) for k in g] for g in groups],
+                        summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+            return 1 if failed else 0
+        if o.output_format == "tsv":
+            for file, r in zip(o.files, recs):
+                if r.error is not None:
+                    self.p(f"{_name(file)}\t{r.error}")
+                else:
+                    self.p(f"{_name(file)}\t{r.group}\t{','.join(r.verdicts)}\t{r.codes}\t{r.matches}\t{r.frames}\t{r.sample_rate}\t{r.dropped_frames}")
+            for p in pairs:
+                self.p(f"pair\t{_name(o.files[p.i])}\t{_name(o.files[p.j])}\t{p.lag_of_j * 512.0 / recs[p.j].sample_rate:.3f}\t{p.errors}\t{p.bits}\t"
+                       f"{1000.0 * p.ber:.1f}")
+            return 1 if failed else 0
+        for file, r in zip(o.files, recs):
+            if r.error is not None:
+                self.e(f"{_name(file)} - {r.error}")
+            elif r.verdicts != ["ok"] and not o.quiet:
+                notes = r.verdicts + ([f"{r.dropped_frames} frames dropped"] if r.dropped_frames else [])
+                self.p(f"{_name(file)}  [{', '.join(notes)}]")
+        for n, g in enumerate(groups, 1):
+            self.p(f"group {n}: {len(g)} files")
+            self.p(f"    {_name(o.files[g[0]])}")
+            for k in g[1:]:
+                a = against(g[0], k)
+                self.p(f"    {_name(o.files[k])}   " + ("via another member" if a is None else f"{a[0]:+.3f} s   {100.0 * a[1]:.1f} % of bits differ"))
+            self.p()
+        self.p(f"{len(o.files)} files, {len(groups)} groups of duplicates")
         return 1 if failed else 0
 
     # ---- find_max_amplitude, src/lib.rs:1174-1199 ------------------------------------------------------------
@@ -1670,6 +1769,17 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "            active, active_total, flagged, nonfinite].  Exit status 1 only for a file that fails or has dropped frames",
         "--ancestry-segments <S>  With --ancestry: segments per file, spread evenly (default 16; 0 = the whole file)",
         "--ancestry-granules <G>  With --ancestry: granules of 576 samples per segment (default 32)",
+        "--duplicates  Which of these files are the same recording?  On the GPU (WAV, FLAC, MP3): a sub-band-difference fingerprint",
+        "            per file (a 32-bit code per 512 samples, 33 bands from 300 to 2000 Hz), then every pair of files at every offset",
+        "            within the radius, by the share of differing bits.  Finds the same audio after lossy coding, a gain change, some",
+        "            samples of delay or silence in front; not across sample rates, not from 96 kHz up, not time-stretched or",
+        "            pitch-shifted copies, not excerpts offset by more than the radius.  A paragraph per group of more than one file",
+        "            (offset and differing bits against its first file) and `N files, G groups of duplicates`.  A convention of this",
+        "            project, compatible with no other fingerprint; the threshold was measured on synthetic material only.  JSON:",
+        "            files[group, matches, codes, verdicts, ...], pairs[i, j, lag_codes, lag_seconds, errors, bits, ber], groups.",
+        "            Exit status 1 only for a file that fails or has dropped frames",
+        "--dup-radius <seconds>  With --duplicates: the largest offset looked for (default 5.94 = 512 codes at 44.1 kHz; at most 23.7)",
+        "--dup-ber <permille>  With --duplicates: the share of differing bits up to which a pair matches (default 316)",
         "-v          Show version",
         "-h          Show this help",
     ):

@@ -325,6 +325,8 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_spectrum.release();
     c->d_dr.release();
     c->d_ancestry.release();
+    c->d_fprint.release();
+    c->d_fp_codes.release();
     c->h_mp3_crc.release();
     if (c->file_pool && c->file_pool_free) c->file_pool_free(c->file_pool);
     c->file_pool = nullptr;

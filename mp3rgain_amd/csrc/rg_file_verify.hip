@@ -1,8 +1,8 @@
 // rg_file_verify.hip -- the file-level calls that check files instead of measuring loudness: rg_flac_verify
 // (include/mp3rgain_amd_flac.h), rg_mp3_verify (include/mp3rgain_amd_mp3verify.h), rg_rip_checksums
 // (include/mp3rgain_amd_rip.h), and the four PCM scans, which share one group driver (pcm_scan_group): rg_pcm_stats
-// (include/mp3rgain_amd_stats.h), rg_dynamic_range (include/mp3rgain_amd_dr.h), rg_ancestry (include/mp3rgain_amd_ancestry.h) and
-// rg_spectrum (include/mp3rgain_amd_spectrum.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
+// (include/mp3rgain_amd_stats.h), rg_dynamic_range (include/mp3rgain_amd_dr.h), rg_ancestry (include/mp3rgain_amd_ancestry.h),
+// rg_spectrum (include/mp3rgain_amd_spectrum.h) and rg_same_recording (include/mp3rgain_amd_fingerprint.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
 // command: what this library does not decode itself is not a stream it could vouch for.  A file's status lives in its record,
 // and the record of a file that failed holds nothing else.
 #include <algorithm>
@@ -11,6 +11,7 @@
 #include "rg_dr.h"
 #include "rg_files.h"
 #include "rg_flac_md5.h"
+#include "rg_fprint.h"
 #include "rg_mp3verify.h"
 #include "rg_rip.h"
 #include "rg_spectrum.h"
@@ -541,3 +542,108 @@ extern "C" int rg_spectrum(rg_ctx *c, const char *const *paths, size_t n, const 
         n * RG_SPEC_MAX_CHANNELS * RG_SPEC_BANDS * sizeof(double));
 }
 
+
+// ---- rg_same_recording: the fingerprint kernels of rg_fprint.hip per group, the match kernel of rg_fprint_match.hip once ----
+// The codes of every group stay in c->d_fp_codes, one group's behind the other's; `used` counts them.
+namespace {
+struct FpCall {
+    size_t used = 0;  // codes in c->d_fp_codes
+};
+}  // namespace
+
+// room for `need` codes with the first `used` kept
+static int fp_codes_grow(rg_ctx *c, size_t used, size_t need, hipStream_t s) {
+    if (need <= c->d_fp_codes.cap) return RG_OK;
+    DevBuf<uint32_t> bigger;
+    RG_HIP(c, bigger.reserve(std::max(need, 2 * c->d_fp_codes.cap)));
+    hipError_t e = hipSuccess;
+    if (used) e = hipMemcpyAsync(bigger.p, c->d_fp_codes.p, used * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        bigger.release();
+        RG_HIP(c, e);
+    }
+    c->d_fp_codes.release();
+    c->d_fp_codes = bigger;
+    return RG_OK;
+}
+
+static int fingerprint_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, FpCall *call, rg_fingerprint_result *out) {
+    FileGroup g(c, paths, first, n);
+    out += first;
+    std::vector<PcmRec> recs;  // plane: the track's place in `tracks`
+    std::vector<RgFpTrack> tracks(n + 1);
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        const int rc = rg_fp_track(i, g.descs[k], g.arena_bytes, &tracks[recs.size()], err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        recs.push_back(PcmRec{k, recs.size()});
+        return RG_OK;
+    };
+    const auto finish = [&]() -> int {
+        if (recs.empty()) return RG_OK;
+        uint64_t fmt_tile[4], codes = 0;
+        (void)rg_fp_plan(tracks.data(), recs.size(), fmt_tile, call->used, 0);
+        for (size_t t = 0; t < recs.size(); ++t) codes += tracks[t].frames ? tracks[t].frames - 1u : 0u;
+        int rc = fp_codes_grow(c, call->used, call->used + (size_t)codes + 4, c->file_stream());
+        if (rc != RG_OK) return rc;
+        std::vector<uint32_t> nonfinite(recs.size());
+        rc = rg_fprint_device(c, c->d_arena.p, tracks.data(), recs.size(), c->d_fp_codes.p, nullptr, nonfinite.data(), c->file_stream());
+        if (rc != RG_OK) return rc;
+        call->used += (size_t)codes;
+        for (const PcmRec &r : recs)
+            rg_fp_fill(g.descs[r.k], tracks[r.plane], dropped_frames(g, r.k), nonfinite[r.plane], (uint32_t)(first + g.slot[r.k]), &out[g.slot[r.k]]);
+        return RG_OK;
+    };
+    return pcm_scan_group(g, "fingerprint", RG_FP_MAX_CHANNELS, out, add, finish);
+}
+
+extern "C" int rg_same_recording(rg_ctx *c, const char *const *paths, size_t n, const rg_fingerprint_opts *opts, rg_fingerprint_result *out,
+                                 rg_fingerprint_pair *pairs, size_t max_pairs, size_t *n_pairs, uint32_t *codes_out, size_t codes_cap) {
+    if (!c || !n_pairs || (max_pairs && !pairs) || (codes_cap && !codes_out)) return RG_ERR_INVALID_ARG;
+    *n_pairs = 0;
+    if (n > 65535) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_same_recording: %zu files, at most 65535 in one call", n);
+    FpCall call;
+    rg_fingerprint_opts o;
+    int rc = pcm_scan_call(c, paths, n, opts, out, rg_fp_options,
+                           [&](size_t first, size_t cnt, const rg_fingerprint_opts &) { return fingerprint_group(c, paths, first, cnt, &call, out); });
+    if (rc != RG_OK || n == 0) return rc;
+    char err[256] = "";
+    (void)rg_fp_options(opts, &o, err, sizeof err);  // (the call above has checked them)
+    return no_throw(c, [&]() -> int {
+        hipStream_t s = c->file_stream();
+        std::vector<uint32_t> counts(n), rates(n), groups(n), matches(n);
+        std::vector<uint64_t> at(n);
+        for (size_t i = 0; i < n; ++i) {  // a failing file has no codes and takes part in no pair
+            const bool ok = out[i].status == RG_OK;
+            counts[i] = ok ? out[i].codes : 0u;
+            rates[i] = ok ? out[i].sample_rate : 0u;
+            at[i] = ok ? out[i].codes_at : 0u;
+        }
+        std::vector<rg_fingerprint_pair_record> records(n * (n - 1) / 2 + 1);
+        std::vector<RgFpPair> compared;
+        rg_fp_pairs(n, counts.data(), rates.data(), at.data(), o, &compared, records.data());
+        const int mrc = rg_fprint_match_device(c, c->d_fp_codes.p, compared, o, records.data(), s);
+        if (mrc != RG_OK) return mrc;
+        *n_pairs = rg_fingerprint_groups(n, records.data(), groups.data(), matches.data());
+        size_t rec = 0, found = 0;
+        for (size_t i = 0; i < n; ++i)
+            for (size_t j = i + 1; j < n; ++j, ++rec) {
+                const rg_fingerprint_pair_record &r = records[rec];
+                if (!(r.flags & RG_FP_PAIR_MATCH)) continue;
+                if (found < max_pairs) pairs[found] = rg_fingerprint_pair{(uint32_t)i, (uint32_t)j, r.errors, r.bits, r.lag, r.flags};
+                ++found;
+            }
+        const size_t fit = std::min(call.used, codes_cap);
+        if (fit) {
+            RG_HIP(c, hipMemcpyAsync(codes_out, c->d_fp_codes.p, fit * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            RG_HIP(c, hipStreamSynchronize(s));
+        }
+        for (size_t i = 0; i < n; ++i) {
+            if (out[i].status != RG_OK) continue;
+            out[i].group = groups[i];
+            out[i].matches = matches[i];
+            if (!codes_out || out[i].codes_at + out[i].codes > codes_cap) out[i].codes_at = UINT64_MAX;
+        }
+        return RG_OK;
+    });
+}

@@ -439,6 +439,159 @@ def album_dr(records) -> Optional[int]:
     return int(round(sum(vals) / len(vals))) if vals else None
 
 
+def _fingerprint_opts(block, probes, radius, max_ber_permille):
+    """rg_fingerprint_opts, or NULL (the header's defaults) when all are None; a None field is its default."""
+    if block is None and probes is None and radius is None and max_ber_permille is None:
+        return None
+    return C.byref(_capi.FingerprintOpts(int(block or 0), int(probes or 0), int(radius or 0), int(max_ber_permille or 0)))
+
+
+def fingerprint_edges(sample_rate: int):
+    """rg_fingerprint_edges -> (the 34 band edges as a list, whether the rate is supported)."""
+    e = (C.c_uint32 * (_capi.FP_BANDS + 1))()
+    rc = _capi.load().rg_fingerprint_edges(int(sample_rate), e)
+    if rc not in (0, _capi.RG_ERR_UNSUPPORTED_RATE):
+        raise ReplayGainError(rc, f"rg_fingerprint_edges: rate {sample_rate}")
+    return list(e), rc == 0
+
+
+def fingerprint_codes(frames: int) -> int:
+    """K of a track of `frames` PCM frames at a supported rate."""
+    return max(0, (int(frames) - _capi.FP_FRAME) // _capi.FP_HOP) if frames >= _capi.FP_FRAME else 0
+
+
+def fingerprint_arena(ctx, route: int, descs, arena, bands=True):
+    """rg_fingerprint_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None ->
+    ([FingerprintRecord], codes, bands): codes a uint32 array of every track's codes in track order (record.codes_at,
+    record.codes), bands a float32 array [sum of F][33] (record.frames_at, record.fp_frames; None when `bands` is false)."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    out = (_capi.FingerprintRecord * max(1, n))()
+    most = sum(fingerprint_codes(int(t.frames)) + 1 for t in descs)  # the frames of every track at a supported rate
+    codes = np.zeros(max(1, most), dtype=np.uint32)
+    e = np.zeros((max(1, most), _capi.FP_BANDS), dtype=np.float32) if bands else None
+    rc = L.rg_fingerprint_arena(ctx, int(route), n, d, arena.ctypes.data if arena.size else None, arena.size, out,
+                                codes.ctypes.data_as(C.POINTER(C.c_uint32)), e.ctypes.data_as(C.POINTER(C.c_float)) if bands else None)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    recs = list(out[:n])
+    return recs, codes[:sum(int(r.codes) for r in recs)], (e[:sum(int(r.fp_frames) for r in recs)] if bands else None)
+
+
+def fingerprint_match_codes(ctx, route: int, codes, rates, block=None, probes=None, radius=None, max_ber_permille=None):
+    """rg_fingerprint_match_codes on constructed codes: `codes` a list of uint32 arrays, one per track, `rates` their sample
+    rates; route 0 is the host (ctx = None), route 1 the kernel -> a structured array of the n (n - 1) / 2 pair records in
+    (i, j) order, fields errors, bits, lag, flags."""
+    L = _capi.load()
+    n = len(codes)
+    counts = np.array([len(c) for c in codes], dtype=np.uint32)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint32) for c in codes]) if n else np.zeros(0, dtype=np.uint32))
+    r = np.array(list(rates), dtype=np.uint32)
+    dt = np.dtype([("errors", "<u4"), ("bits", "<u4"), ("lag", "<i4"), ("flags", "<u4")])
+    out = np.zeros(max(1, n * (n - 1) // 2), dtype=dt)
+    u32p = C.POINTER(C.c_uint32)
+    rc = L.rg_fingerprint_match_codes(ctx, int(route), n, counts.ctypes.data_as(u32p), r.ctypes.data_as(u32p),
+                                      flat.ctypes.data_as(u32p) if flat.size else None, _fingerprint_opts(block, probes, radius, max_ber_permille),
+                                      out.ctypes.data_as(C.POINTER(_capi.FingerprintPairRecord)))
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return out[:n * (n - 1) // 2]
+
+
+def fingerprint_groups(n: int, pair_records):
+    """rg_fingerprint_groups on the pair records of fingerprint_match_codes -> (groups, matches, number of matching pairs)."""
+    L = _capi.load()
+    rec = np.ascontiguousarray(pair_records)
+    g, m = np.zeros(max(1, n), dtype=np.uint32), np.zeros(max(1, n), dtype=np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    found = L.rg_fingerprint_groups(n, rec.ctypes.data_as(C.POINTER(_capi.FingerprintPairRecord)) if rec.size else None, g.ctypes.data_as(u32p),
+                                    m.ctypes.data_as(u32p))
+    return g[:n], m[:n], int(found)
+
+
+def fingerprint_kernel_shape():
+    """rg_fingerprint_kernel_shape -> (tile_codes, lanes, lds_bytes, match_lanes, lags_per_lane)."""
+    v = [C.c_uint32() for _ in range(5)]
+    rc = _capi.load().rg_fingerprint_kernel_shape(*[C.byref(x) for x in v])
+    if rc != 0:
+        raise ReplayGainError(rc, "rg_fingerprint_kernel_shape")
+    return tuple(x.value for x in v)
+
+
+@dataclass
+class Fingerprint:
+    """One file of Analyzer.same_recording (rg_fingerprint_result).  The fingerprint and the threshold are conventions of
+    include/mp3rgain_amd_fingerprint.h, measured on this project's own synthetic material only."""
+    frames: int
+    sample_rate: int
+    channels: int
+    format: int
+    dropped_frames: int
+    flags: int
+    fp_frames: int
+    codes: int
+    nonfinite_frames: int
+    group: int               # the smallest index of the files this one is the same recording as (its own when alone)
+    matches: int
+    error: Optional["ReplayGainError"] = None  # why there is no fingerprint; every other field is then zero
+
+    @property
+    def complete(self) -> bool:
+        return bool(self.flags & _capi.FP_COMPLETE)
+
+    @property
+    def short(self) -> bool:
+        return bool(self.flags & _capi.FP_SHORT)
+
+    @property
+    def unsupported_rate(self) -> bool:
+        return bool(self.flags & _capi.FP_RATE)
+
+    @property
+    def nonfinite(self) -> bool:
+        return bool(self.flags & _capi.FP_NONFINITE)
+
+    @property
+    def verdicts(self) -> list:
+        """The flags as words, in a fixed order; ["ok"] when there is nothing to report."""
+        names = (("rate", self.unsupported_rate), ("short", self.short and not self.unsupported_rate), ("nonfinite", self.nonfinite),
+                 ("incomplete", self.error is None and not self.complete))
+        return [n for n, on in names if on] or ["ok"]
+
+
+@dataclass
+class SamePair:
+    """One matching pair of Analyzer.same_recording (rg_fingerprint_pair): files i < j; `lag` codes of 512 samples of the
+    longer file against the shorter (`probe_j`: the shorter is j)."""
+    i: int
+    j: int
+    errors: int
+    bits: int
+    lag: int
+    flags: int
+
+    @property
+    def ber(self) -> float:
+        return self.errors / self.bits if self.bits else 0.0
+
+    @property
+    def probe_j(self) -> bool:
+        return bool(self.flags & _capi.FP_PAIR_PROBE_J)
+
+    @property
+    def lag_of_j(self) -> int:
+        """How many codes later than in file i the common audio lies in file j."""
+        return -self.lag if self.probe_j else self.lag
+
+
+def fingerprint_from_record(r, error=None) -> Fingerprint:
+    """A Fingerprint from an rg_fingerprint_result."""
+    return Fingerprint(int(r.frames), int(r.sample_rate), int(r.channels), int(r.format), int(r.dropped_frames), int(r.flags), int(r.fp_frames),
+                       int(r.codes), int(r.nonfinite_frames), int(r.group), int(r.matches), error)
+
+
 def _ancestry_opts(segments, granules, z_min, iso_min, active_floor):
     """rg_ancestry_opts, or NULL (the header's defaults) when all are None.  segments = 0 is the whole plane as one segment."""
     if segments is None and granules is None and z_min is None and iso_min is None and active_floor is None:
@@ -1517,6 +1670,52 @@ class Analyzer:
     @staticmethod
     def dr_kernel_shape(fmt: int):
         return dr_kernel_shape(fmt)
+
+    def _same_recording_call(self, files, block, probes, radius, max_ber_permille, codes_cap):
+        paths, out = self._file_args(files, _capi.FingerprintRecord)
+        n = len(files)
+        max_pairs = n * (n - 1) // 2
+        pairs = (_capi.FingerprintPair * max(1, max_pairs))()
+        n_pairs = C.c_size_t(0)
+        codes = np.zeros(max(1, int(codes_cap)), dtype=np.uint32) if codes_cap else None
+        self._check(self._lib.rg_same_recording(self._ctx, paths, n, _fingerprint_opts(block, probes, radius, max_ber_permille), out, pairs, max_pairs,
+                                                C.byref(n_pairs), codes.ctypes.data_as(C.POINTER(C.c_uint32)) if codes_cap else None,
+                                                int(codes_cap) if codes_cap else 0))
+        return out, pairs, int(n_pairs.value), codes
+
+    def same_recording(self, files, block=None, probes=None, radius=None, max_ber_permille=None):
+        """rg_same_recording: `files` (WAV, FLAC or MPEG Layer III) decoded by the route the analysis uses, fingerprinted where
+        the PCM lies, and every pair matched at every lag within `radius` codes, all on this GPU ->
+        ([Fingerprint], [SamePair], groups): the matching pairs in (i, j) order, and `groups` the lists of indices of the
+        files that are the same recording (more than one file each), in order of their first file.  A file that takes no part
+        carries its ReplayGainError in `.error`."""
+        out, pairs, n_pairs, _ = self._same_recording_call(files, block, probes, radius, max_ber_permille, 0)
+        recs = [fingerprint_from_record(r, err) for r, err in self._file_records(out, len(files))]
+        found = [SamePair(int(p.i), int(p.j), int(p.errors), int(p.bits), int(p.lag), int(p.flags)) for p in pairs[:n_pairs]]
+        by = {}
+        for i, r in enumerate(recs):
+            if r.error is None:
+                by.setdefault(r.group, []).append(i)
+        return recs, found, [g for _, g in sorted(by.items()) if len(g) > 1]
+
+    def same_recording_raw(self, files, block=None, probes=None, radius=None, max_ber_permille=None, codes_cap=0):
+        """same_recording's arrays as the C call left them -> (record bytes, pair bytes, codes or None): tests compare routes byte
+        for byte."""
+        out, pairs, n_pairs, codes = self._same_recording_call(files, block, probes, radius, max_ber_permille, codes_cap)
+        return (bytes(out)[:len(files) * C.sizeof(_capi.FingerprintRecord)], bytes(pairs)[:n_pairs * C.sizeof(_capi.FingerprintPair)], codes)
+
+    def fingerprint_arena(self, route: int, descs, arena, bands=True):
+        """rg_fingerprint_arena, the seam of the fingerprint kernels -> ([FingerprintRecord], codes, bands); route 0 = the
+        serial host twin, route 1 = the arena copied to this GPU and the kernels, route 2 = the kernels' arithmetic on the host."""
+        return fingerprint_arena(self._ctx, route, descs, arena, bands)
+
+    def fingerprint_match_codes(self, route: int, codes, rates, block=None, probes=None, radius=None, max_ber_permille=None):
+        """rg_fingerprint_match_codes, the seam of the match kernel, on constructed codes -> the pair records."""
+        return fingerprint_match_codes(self._ctx, route, codes, rates, block, probes, radius, max_ber_permille)
+
+    @staticmethod
+    def fingerprint_kernel_shape():
+        return fingerprint_kernel_shape()
 
     def _ancestry_call(self, files, segments, granules, z_min, iso_min, active_floor):
         paths, out = self._file_args(files, _capi.AncestryRecord)
