@@ -549,6 +549,76 @@ pub mod replaygain {
     }
 }
 
+/// The tempo scan of `include/mp3rgain_amd_tempo.h`: how fast is each of these WAV, FLAC or MP3 files?  An onset curve per file (one
+/// integer per 512 samples from 32 bands between 60 and 8000 Hz), its windowed autocorrelation and a constant-tempo beat grid, all
+/// on the GPU and all integer after the onset curve.  The estimator is a convention of that header, tried on synthetic material
+/// only and held to no other BPM tool; the reading lies in `[min_bpm, 2 min_bpm)` by convention, drifting tempo is only flagged
+/// (`stable_permille`), and the first beat is coarse.  A module of its own, as [`fingerprint`] is.
+/// `tests/test_rust_tempo_layout.py` compares these declarations with the header.
+pub mod tempo {
+    use super::ffi::RgCtx;
+    use std::os::raw::{c_char, c_int};
+
+    pub const TEMPO_SHORT: u32 = 1;
+    pub const TEMPO_RATE: u32 = 2;
+    pub const TEMPO_NONFINITE: u32 = 4;
+    pub const TEMPO_COMPLETE: u32 = 8;
+    pub const TEMPO_RANGE: u32 = 16;
+    pub const TEMPO_NONE: u32 = 32;
+    pub const TEMPO_MAX_CHANNELS: usize = 8;
+    pub const TEMPO_FRAME: u32 = 4096;
+    pub const TEMPO_HOP: u32 = 512;
+    pub const TEMPO_BANDS: u32 = 32;
+    /// `RG_TEMPO_WINDOW`, `RG_TEMPO_WINDOW_HOP`, `RG_TEMPO_MIN_BPM`: what a zero in the options means
+    pub const TEMPO_WINDOW: u32 = 1024;
+    pub const TEMPO_WINDOW_HOP: u32 = 256;
+    pub const TEMPO_MIN_BPM: u32 = 80;
+    pub const TEMPO_MIN_WINDOW: u32 = 32;
+    pub const TEMPO_MAX_WINDOW: u32 = 1024;
+    pub const TEMPO_MAX_HARMONICS: u32 = 8;
+    pub const TEMPO_ONSET_MAX: u32 = 1023;
+    /// samples added to the best phase of the beat grid: the median `tools/tempo_refcheck.py` measured
+    pub const TEMPO_BEAT_BIAS: u32 = 4120;
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_tempo_opts`: a zero field means its default; a null pointer means all defaults
+    pub struct RgTempoOpts {
+        pub window: u32,
+        pub hop: u32,
+        pub min_bpm: u32,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_tempo_result`: `period16 == 0` means no tempo; `bpm_milli` is the reading in thousandths of a BPM
+    pub struct RgTempoResult {
+        pub status: i32,
+        pub flags: u32,
+        pub frames: u64,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub format: u32,
+        pub dropped_frames: u32,
+        pub onsets: u32,
+        pub windows: u32,
+        pub period16: u32,
+        pub harmonics: u32,
+        pub bpm_milli: u32,
+        pub confidence_permille: u32,
+        pub stable_permille: u32,
+        pub first_beat: u32,
+        pub nonfinite_frames: u32,
+        pub band_frames: u32,
+        pub onsets_at: u64,
+    }
+
+    extern "C" {
+        pub fn rg_tempo(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, opts: *const RgTempoOpts, out: *mut RgTempoResult, onsets_out: *mut u16,
+                        onsets_cap: usize) -> c_int;
+    }
+}
+
 /// The duplicate finder of `include/mp3rgain_amd_fingerprint.h`: which of these WAV, FLAC or MP3 files are the same recording?  A
 /// sub-band-difference fingerprint per file (a 32-bit code per 512 samples) and a match of every pair of files at every lag within
 /// a radius, both on the GPU.  The fingerprint is a convention of that header, compatible with no other fingerprint, and its

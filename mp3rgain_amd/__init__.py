@@ -35,6 +35,7 @@ from .replaygain import (  # noqa: F401
     RipOffsetSignatures,
     SamePair,
     Spectrum,
+    Tempo,
     album_dr,
     ancestry_arena,
     ancestry_from_record,
@@ -61,6 +62,11 @@ from .replaygain import (  # noqa: F401
     spectrum_arena,
     spectrum_kernel_shape,
     spectrum_verdict,
+    tempo_arena,
+    tempo_bands,
+    tempo_from_onsets,
+    tempo_from_record,
+    tempo_kernel_shape,
 )
 
 __version__ = "0.1.0"

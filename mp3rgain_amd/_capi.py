@@ -532,6 +532,51 @@ FINGERPRINT_SYMBOLS = [
                                    _P(_sz)]),
 ]
 
+# include/mp3rgain_amd_tempo.h (tempo and beat grid: the onset curve and its windowed autocorrelation)
+TEMPO_SHORT, TEMPO_RATE, TEMPO_NONFINITE, TEMPO_COMPLETE, TEMPO_RANGE, TEMPO_NONE = 1, 2, 4, 8, 16, 32
+TEMPO_MAX_CHANNELS, TEMPO_FRAME, TEMPO_HOP, TEMPO_BANDS = 8, 4096, 512, 32
+TEMPO_WINDOW, TEMPO_WINDOW_HOP, TEMPO_MIN_BPM = 1024, 256, 80
+TEMPO_MIN_WINDOW, TEMPO_MAX_WINDOW, TEMPO_MAX_HARMONICS, TEMPO_ONSET_MAX = 32, 1024, 8, 1023
+TEMPO_BEAT_BIAS = 4120
+
+
+class TempoOpts(C.Structure):  # rg_tempo_opts
+    _fields_ = [("window", C.c_uint32), ("hop", C.c_uint32), ("min_bpm", C.c_uint32)]
+
+
+class TempoRecord(C.Structure):  # rg_tempo_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("onsets", C.c_uint32),
+        ("windows", C.c_uint32),
+        ("period16", C.c_uint32),
+        ("harmonics", C.c_uint32),
+        ("bpm_milli", C.c_uint32),
+        ("confidence_permille", C.c_uint32),
+        ("stable_permille", C.c_uint32),
+        ("first_beat", C.c_uint32),
+        ("nonfinite_frames", C.c_uint32),
+        ("band_frames", C.c_uint32),
+        ("onsets_at", C.c_uint64),
+    ]
+
+
+TEMPO_SYMBOLS = [
+    ("rg_tempo_bands", _int, [_u32, _P(_u32)]),
+    ("rg_tempo", _int, [_vp, _P(C.c_char_p), _sz, _P(TempoOpts), _P(TempoRecord), _P(C.c_uint16), _sz]),
+    ("rg_tempo_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _vp, _sz, _P(TempoOpts), _P(TempoRecord), _P(C.c_uint16), _P(C.c_float)]),
+    ("rg_tempo_from_onsets", _int, [_vp, _int, _sz, _P(_u32), _P(_u32), _P(C.c_uint16), _P(TempoOpts), _P(TempoRecord), _P(C.c_int64)]),
+    ("rg_tempo_kernel_shape", _int, [_P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_tempo_rate", _int, [_vp, _sz, _u64, _P(TempoOpts), _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl),
+                             _P(_sz)]),
+]
+
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions
 NODE_OPEN = C.CFUNCTYPE(_vp, _int, _vp)
 NODE_CLOSE = C.CFUNCTYPE(None, _vp, _vp)
@@ -572,7 +617,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

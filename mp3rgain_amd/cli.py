@@ -82,6 +82,8 @@ class Options:  # src/main.rs:65-96
     duplicates: bool = False  # this façade only (--duplicates): which of these files are the same recording?  Fingerprints and every pair
     dup_radius: Optional[float] = None  # with --duplicates (--dup-radius SECONDS): the largest offset looked for, in seconds at 44.1 kHz
     dup_ber: Optional[int] = None  # with --duplicates (--dup-ber PERMILLE): the share of differing bits up to which a pair matches
+    tempo: bool = False  # this façade only (--tempo): how fast is each file?  BPM and a constant-tempo beat grid
+    tempo_min: Optional[int] = None  # with --tempo (--tempo-min BPM): the reading lies in [BPM, 2 BPM)
     files: List[Path] = field(default_factory=list)
 
 
@@ -186,6 +188,10 @@ def parse_args(args: List[str], out, err) -> Options:
             o.dup_radius = _parse_positive(need("--dup-radius", "--dup-radius requires an argument"), "invalid radius")
         elif arg == "--dup-ber":
             o.dup_ber = _parse_int(need("--dup-ber", "--dup-ber requires an argument"), "invalid per mille value", 32, signed=False)
+        elif arg == "--tempo":  # not in the reference: a command of its own, like --duplicates
+            o.tempo = True
+        elif arg == "--tempo-min":
+            o.tempo_min = _parse_int(need("--tempo-min", "--tempo-min requires an argument"), "invalid BPM", 32, signed=False)
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -335,7 +341,25 @@ def parse_args(args: List[str], out, err) -> Options:
                                         ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
         if others:
             raise CliError(f"--duplicates is a command of its own and cannot be combined with {', '.join(others)}")
+    if o.tempo_min is not None and not o.tempo:
+        raise CliError("--tempo-min requires --tempo")
+    if o.tempo_min is not None and not 30 <= o.tempo_min <= 300:
+        raise CliError(f"--tempo-min takes 30 to 300 BPM: {o.tempo_min}")
+    if o.tempo:
+        others = [name for name, on in (("--verify", o.verify), ("--rip", o.rip), ("--stats", o.stats), ("--spectrum", o.spectrum), ("--dr", o.dr),
+                                        ("--ancestry", o.ancestry), ("--duplicates", o.duplicates), ("--r128", o.r128), ("-x", o.max_amplitude_only),
+                                        ("-r", o.track_gain), ("-a", o.album_gain), ("-u", o.undo), ("-g", o.gain_steps is not None),
+                                        ("-l", o.channel_gain is not None), ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
+        if others:
+            raise CliError(f"--tempo is a command of its own and cannot be combined with {', '.join(others)}")
     return o
+
+
+def tempo_line(r) -> str:
+    """A file's reading as the text output has it (without the name)."""
+    if not r.found:
+        return "no tempo found"
+    return f"{r.bpm:.2f} BPM  (confidence {r.confidence:.2f}, steady {r.steady:.2f}, first beat {r.first_beat_seconds:.3f} s)"
 
 
 def dup_radius_codes(seconds: float) -> int:
@@ -581,6 +605,8 @@ class Cli:
             return self.cmd_ancestry()
         if o.duplicates:
             return self.cmd_duplicates()
+        if o.tempo:
+            return self.cmd_tempo()
         if o.max_amplitude_only:
             return self.cmd_max_amplitude()
         if o.stored_tag_mode == "delete":
@@ -1100,6 +1126,53 @@ class Cli:
                 self.p(f"    {_name(o.files[k])}   " + ("via another member" if a is None else f"{a[0]:+.3f} s   {100.0 * a[1]:.1f} % of bits differ"))
             self.p()
         self.p(f"{len(o.files)} files, {len(groups)} groups of duplicates")
+        return 1 if failed else 0
+
+    # ---- --tempo (not in the reference): how fast is each file?  On the GPU -----------------------------------------------------
+    def cmd_tempo(self) -> int:
+        """Every file decoded by the route the analysis uses; its onset curve, the windowed autocorrelation and the beat grid on
+        the first GPU (rg_tempo).  Text: a line per file, `128.00 BPM  (confidence 0.89, steady 1.00, first beat 0.157 s)  name`
+        or `no tempo found  name`, with the verdicts in brackets when there are any.  The estimator is a convention of this
+        project, tried on synthetic material only; the reading lies in [--tempo-min, twice that).  A report: exit status 1 only
+        when a file fails or has dropped frames.  TSV, no header: a row per file `file, bpm, confidence, steady, first beat in
+        seconds, verdicts, period16, onsets, windows, frames, sample rate, dropped frames` (a failing file: `file, error text`)."""
+        o = self.o
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            recs = an.tempo(o.files, min_bpm=o.tempo_min)
+        failed = sum(1 for r in recs if r.error is not None or not r.complete)
+        if o.output_format == "json":
+            files = []
+            for file, r in zip(o.files, recs):
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                else:
+                    d.update(bpm=r.bpm, confidence=r.confidence, steady=r.steady, first_beat_seconds=r.first_beat_seconds, first_beat=r.first_beat if r.found else None,
+                             period16=r.period16, harmonics=r.harmonics, verdicts=r.verdicts, onsets=r.onsets, windows=r.windows, frames=r.frames,
+                             sample_rate=r.sample_rate, channels=r.channels, dropped_frames=r.dropped_frames, nonfinite_frames=r.nonfinite_frames,
+                             complete=r.complete)
+                files.append(d)
+            _print_json(self.out, files=files, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+            return 1 if failed else 0
+        if o.output_format == "tsv":
+            for file, r in zip(o.files, recs):
+                if r.error is not None:
+                    self.p(f"{_name(file)}\t{r.error}")
+                    continue
+                reading = f"{r.bpm:.3f}\t{r.confidence:.3f}\t{r.steady:.3f}\t{r.first_beat_seconds:.3f}" if r.found else "\t\t\t"
+                self.p(f"{_name(file)}\t{reading}\t{','.join(r.verdicts)}\t{r.period16}\t{r.onsets}\t{r.windows}\t{r.frames}\t{r.sample_rate}\t{r.dropped_frames}")
+            return 1 if failed else 0
+        if self.talk:
+            self.p(f"mp3rgain tempo of {len(o.files)} file(s): onset curve and windowed autocorrelation"
+                   " (a convention of this project, tried on synthetic material only)")
+            self.p()
+        for file, r in zip(o.files, recs):
+            if r.error is not None:
+                self.e(f"{_name(file)} - {r.error}")
+                continue
+            notes = [v for v in r.verdicts if v not in ("ok", "none")] + ([f"{r.dropped_frames} frames dropped"] if r.dropped_frames else [])
+            self.p(f"{tempo_line(r)}  {_name(file)}" + (f"  [{', '.join(notes)}]" if notes else ""))
         return 1 if failed else 0
 
     # ---- find_max_amplitude, src/lib.rs:1174-1199 ------------------------------------------------------------
@@ -1780,6 +1853,14 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "            Exit status 1 only for a file that fails or has dropped frames",
         "--dup-radius <seconds>  With --duplicates: the largest offset looked for (default 5.94 = 512 codes at 44.1 kHz; at most 23.7)",
         "--dup-ber <permille>  With --duplicates: the share of differing bits up to which a pair matches (default 316)",
+        "--tempo     How fast is each file?  On the GPU (WAV, FLAC, MP3): an onset curve (one value per 512 samples from 32 bands between",
+        "            60 and 8000 Hz), its autocorrelation over windows of 1024 onsets, and a constant-tempo beat grid.  A line per file:",
+        "            `128.00 BPM  (confidence 0.89, steady 1.00, first beat 0.157 s)  name`, or `no tempo found`.  The reading lies in",
+        "            [--tempo-min, twice that): the octave is a convention.  `steady` is the share of windows that agree with the",
+        "            file's tempo; the first beat is coarse (a 93 ms window).  A convention of this project, tried on synthetic",
+        "            material only and held to no other BPM tool.  JSON: files[bpm, confidence, steady, first_beat_seconds, period16,",
+        "            verdicts, ...].  Exit status 1 only for a file that fails or has dropped frames",
+        "--tempo-min <BPM>  With --tempo: the lowest tempo reported (default 80; 30 to 300)",
         "-v          Show version",
         "-h          Show this help",
     ):

@@ -327,6 +327,8 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_ancestry.release();
     c->d_fprint.release();
     c->d_fp_codes.release();
+    c->d_tempo.release();
+    c->d_tp_onsets.release();
     c->h_mp3_crc.release();
     if (c->file_pool && c->file_pool_free) c->file_pool_free(c->file_pool);
     c->file_pool = nullptr;

@@ -2,7 +2,8 @@
 // (include/mp3rgain_amd_flac.h), rg_mp3_verify (include/mp3rgain_amd_mp3verify.h), rg_rip_checksums
 // (include/mp3rgain_amd_rip.h), and the four PCM scans, which share one group driver (pcm_scan_group): rg_pcm_stats
 // (include/mp3rgain_amd_stats.h), rg_dynamic_range (include/mp3rgain_amd_dr.h), rg_ancestry (include/mp3rgain_amd_ancestry.h),
-// rg_spectrum (include/mp3rgain_amd_spectrum.h) and rg_same_recording (include/mp3rgain_amd_fingerprint.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
+// rg_spectrum (include/mp3rgain_amd_spectrum.h), rg_same_recording (include/mp3rgain_amd_fingerprint.h) and rg_tempo
+// (include/mp3rgain_amd_tempo.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
 // command: what this library does not decode itself is not a stream it could vouch for.  A file's status lives in its record,
 // and the record of a file that failed holds nothing else.
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include "rg_mp3verify.h"
 #include "rg_rip.h"
 #include "rg_spectrum.h"
+#include "rg_tempo.h"
 #include "rg_stats.h"
 
 using namespace rgf;
@@ -646,4 +648,74 @@ extern "C" int rg_same_recording(rg_ctx *c, const char *const *paths, size_t n, 
         }
         return RG_OK;
     });
+}
+
+// ---- rg_tempo: the onset kernels of rg_tempo.hip per group, and the window and finish kernels behind them ------------------
+// A group's onset curves lie in c->d_tp_onsets while its stage 2 runs; the caller's copy of them is filled group by group.
+namespace {
+struct TempoCall {
+    uint16_t *onsets_out;
+    size_t cap, used = 0;  // onsets the caller's array holds, and those already in it
+};
+}  // namespace
+
+static int tempo_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_tempo_opts &o, TempoCall *call, rg_tempo_result *out) {
+    FileGroup g(c, paths, first, n);
+    out += first;
+    std::vector<PcmRec> recs;  // plane: the track's place in `tracks`
+    std::vector<RgFpTrack> tracks(n + 1);
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        const int rc = rg_tp_track(i, g.descs[k], g.arena_bytes, &tracks[recs.size()], err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        recs.push_back(PcmRec{k, recs.size()});
+        return RG_OK;
+    };
+    const auto finish = [&]() -> int {
+        if (recs.empty()) return RG_OK;
+        hipStream_t s = c->file_stream();
+        uint64_t fmt_tile[4], onsets = 0;
+        (void)rg_fp_plan(tracks.data(), recs.size(), fmt_tile, 0, 0);
+        for (size_t t = 0; t < recs.size(); ++t) onsets += tracks[t].frames ? tracks[t].frames - 1u : 0u;
+        RG_HIP(c, c->d_tp_onsets.reserve((size_t)onsets + 8));
+        std::vector<uint32_t> nonfinite(recs.size());
+        int rc = rg_tempo_onsets_device(c, c->d_arena.p, tracks.data(), recs.size(), c->d_tp_onsets.p, nullptr, nonfinite.data(), s);
+        if (rc != RG_OK) return rc;
+        std::vector<RgTpTrack> s2(recs.size());
+        std::vector<RgTpFinish> fin(recs.size());
+        for (const PcmRec &r : recs) {
+            rg_tp_stage2_track(g.descs[r.k].sample_rate, tracks[r.plane].frames ? tracks[r.plane].frames - 1u : 0u, o, &s2[r.plane]);
+            s2[r.plane].onsets_at = tracks[r.plane].codes_at;
+        }
+        rc = rg_tempo_stage2_device(c, c->d_tp_onsets.p, s2.data(), recs.size(), o, fin.data(), nullptr, s);
+        if (rc != RG_OK) return rc;
+        // the caller's copy: whole tracks, as many as fit
+        size_t fit = 0;
+        for (const PcmRec &r : recs) {
+            const RgFpTrack &t = tracks[r.plane];
+            const uint64_t k = t.frames ? t.frames - 1u : 0u;
+            uint64_t at = UINT64_MAX;
+            if (call->onsets_out && fit == t.codes_at && call->used + t.codes_at + k <= call->cap) {
+                at = call->used + t.codes_at;
+                fit = (size_t)(t.codes_at + k);
+            }
+            rg_tp_fill(&g.descs[r.k], g.descs[r.k].sample_rate, t.frames, s2[r.plane], fin[r.plane], dropped_frames(g, r.k), nonfinite[r.plane], at,
+                       &out[g.slot[r.k]]);
+            out[g.slot[r.k]].band_frames = 0;  // the file call gives no band energies
+        }
+        if (fit) {
+            RG_HIP(c, hipMemcpyAsync(call->onsets_out + call->used, c->d_tp_onsets.p, fit * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+            RG_HIP(c, hipStreamSynchronize(s));
+            call->used += fit;
+        }
+        return RG_OK;
+    };
+    return pcm_scan_group(g, "tempo", RG_TEMPO_MAX_CHANNELS, out, add, finish);
+}
+
+extern "C" int rg_tempo(rg_ctx *c, const char *const *paths, size_t n, const rg_tempo_opts *opts, rg_tempo_result *out, uint16_t *onsets_out,
+                        size_t onsets_cap) {
+    if (!c || (onsets_cap && !onsets_out)) return RG_ERR_INVALID_ARG;
+    TempoCall call{onsets_out, onsets_out ? onsets_cap : 0};
+    return pcm_scan_call(c, paths, n, opts, out, rg_tp_options,
+                         [&](size_t first, size_t cnt, const rg_tempo_opts &o) { return tempo_group(c, paths, first, cnt, o, &call, out); });
 }

@@ -3,9 +3,12 @@
 // kernels' f32 arithmetic on the host, the groups) and rg_file_verify.hip (rg_same_recording) share it.  The transform is the
 // spectral scan's (rg_spectrum.h: tables, passes, rg_spec_dft16); what is written once here for both sides is how a band of
 // the two frames of a pair is summed and how a code comes from two rows of band energies.  Both translation units are compiled
-// without contraction, so the two give the same bits.
+// without contraction, so the two give the same bits.  The tempo scan (rg_tempo.h) is a second user of the track record, the
+// plan, the tile walk (rg_fprint_tile.h on the device, rg_fp_tile_bands_host here) and the double transform of route 0.
 #pragma once
 
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "../../include/mp3rgain_amd_fingerprint.h"
@@ -101,6 +104,114 @@ RG_SPEC_HD uint32_t rg_fp_probe_start(uint32_t p, uint32_t ka, uint32_t block, u
     return (uint32_t)((uint64_t)(2u * p + 1u) * (ka - block) / (2u * probes));
 }
 
+// ---- what the host twins of the fingerprint and of the tempo scan (rg_tempo.h) walk alike -------------------------------------
+// sample k of the track's signal: the channel, or the mean of the first two, in f32
+inline float rg_fp_signal_at(const unsigned char *arena, const RgFpTrack &t, uint64_t k) {
+    const auto value = [&](uint64_t off) {
+        const uint32_t raw = rg_pcm_raw_at(arena + off, t.format, k);
+        switch (t.format) {
+            case RG_FMT_F32_PLANAR: return rg_spec_value<RG_FMT_F32_PLANAR>(raw);
+            case RG_FMT_S16_PLANAR: return rg_spec_value<RG_FMT_S16_PLANAR>(raw);
+            default: return rg_spec_value<RG_FMT_S32_PLANAR>(raw);
+        }
+    };
+    const float a = value(t.off0);
+    return t.channels >= 2 ? (a + value(t.off1)) * 0.5f : a;
+}
+
+// re, im <- their L-point DFT: decimation in time, radix 2, in double (route 0)
+inline void rg_fp_fft_double(double *re, double *im) {
+    const uint32_t L = RG_FP_FRAME;
+    static const std::vector<double> *roots = [] {
+        std::vector<double> *r = new std::vector<double>(RG_FP_FRAME);  // cos, -sin of 2 pi k / L, k < L / 2
+        for (uint32_t k = 0; k < RG_FP_FRAME / 2; ++k) {
+            (*r)[2 * k] = std::cos(2.0 * 3.14159265358979323846 * k / RG_FP_FRAME);
+            (*r)[2 * k + 1] = -std::sin(2.0 * 3.14159265358979323846 * k / RG_FP_FRAME);
+        }
+        return r;
+    }();
+    for (uint32_t i = 1, j = 0; i < L; ++i) {  // bit reversal
+        uint32_t bit = L >> 1;
+        for (; j & bit; bit >>= 1) j ^= bit;
+        j ^= bit;
+        if (i < j) {
+            std::swap(re[i], re[j]);
+            std::swap(im[i], im[j]);
+        }
+    }
+    for (uint32_t len = 2; len <= L; len <<= 1) {
+        const uint32_t step = L / len;
+        for (uint32_t i = 0; i < L; i += len)
+            for (uint32_t k = 0; k < len / 2; ++k) {
+                const double wr = (*roots)[2 * k * step], wi = (*roots)[2 * k * step + 1];
+                const uint32_t a = i + k, b = i + k + len / 2;
+                const double xr = re[b] * wr - im[b] * wi, xi = re[b] * wi + im[b] * wr;
+                re[b] = re[a] - xr;
+                im[b] = im[a] - xi;
+                re[a] += xr;
+                im[a] += xi;
+            }
+    }
+}
+
+// route 2, one workgroup of a tile kernel (rg_fprint_tile.h): the band energies of the tile's *nf frames, BANDS floats each, to
+// E[RG_FP_TILE_FRAMES * BANDS], with t.e[0 .. BANDS] the edges; -> the non-finite frames among those the tile owns.  The unit
+// that instantiates it is compiled without contraction.
+template <uint32_t BANDS>
+inline uint32_t rg_fp_tile_bands_host(const unsigned char *arena, const RgFpTrack &t, uint32_t tile, float *E, uint32_t *nf_out) {
+    const RgSpecTables &tb = rg_spec_tables();
+    const uint32_t f0 = tile * RG_FP_TILE_CODES, left = t.frames - f0, nf = left < RG_FP_TILE_FRAMES ? left : RG_FP_TILE_FRAMES;
+    const uint32_t count = (nf - 1u) * RG_FP_HOP + RG_FP_FRAME;
+    std::vector<float> pcm(count);
+    for (uint32_t k = 0; k < count; ++k) pcm[k] = rg_fp_signal_at(arena, t, (uint64_t)f0 * RG_FP_HOP + k);
+    std::vector<RgSpecC> x(RG_SPEC_FRAME), z(RG_SPEC_FRAME);
+    uint32_t nonfinite = 0;
+    for (uint32_t pr = 0; pr < nf; pr += 2) {
+        const bool has_b = pr + 1 < nf;
+        const float *fa = &pcm[pr * RG_FP_HOP], *fb = has_b ? fa + RG_FP_HOP : fa;
+        bool bad_a = false, bad_b = false;
+        if (t.format == RG_FMT_F32_PLANAR)
+            for (uint32_t n = 0; n < RG_FP_FRAME; ++n) {
+                bad_a |= rg_fp_nonfinite(fa[n]);
+                if (has_b) bad_b |= rg_fp_nonfinite(fb[n]);
+            }
+        const bool use_a = !bad_a, use_b = has_b && !bad_b;
+        RgSpecC v[16];
+        for (uint32_t l = 0; l < RG_FP_LANES; ++l) {  // pass 1: lane l = 16 n1 + n0
+            for (uint32_t n2 = 0; n2 < 16; ++n2) {
+                const uint32_t n = 256 * n2 + l;
+                const float w = tb.window[n];
+                v[n2].x = use_a ? fa[n] * w : 0.0f;
+                v[n2].y = use_b ? fb[n] * w : 0.0f;
+            }
+            rg_spec_pass1(v, l, tb.tw1);
+            for (uint32_t k0 = 0; k0 < 16; ++k0) x[k0 * 256 + l] = v[k0];
+        }
+        for (uint32_t l = 0; l < RG_FP_LANES; ++l) {  // pass 2: lane l = 16 k0 + n0, in place
+            const uint32_t k0 = l >> 4, n0 = l & 15u;
+            for (uint32_t n1 = 0; n1 < 16; ++n1) v[n1] = x[k0 * 256 + n1 * 16 + n0];
+            rg_spec_pass2(v, n0, tb.tw2);
+            for (uint32_t k1 = 0; k1 < 16; ++k1) x[k0 * 256 + k1 * 16 + n0] = v[k1];
+        }
+        for (uint32_t l = 0; l < RG_FP_LANES; ++l) {  // pass 3: lane l = 16 k1 + k0
+            const uint32_t k1 = l >> 4, k0 = l & 15u;
+            for (uint32_t n0 = 0; n0 < 16; ++n0) v[n0] = x[k0 * 256 + k1 * 16 + n0];
+            rg_spec_dft16(v);
+            for (uint32_t k2 = 0; k2 < 16; ++k2) z[l + 256 * k2] = v[k2];
+        }
+        const auto zat = [&](uint32_t k) { return z[k]; };
+        for (uint32_t m = 0; m < BANDS; ++m) {
+            E[pr * BANDS + m] = use_a ? rg_fp_band(zat, t.e[m], t.e[m + 1], 0) : 0.0f;
+            if (has_b) E[(pr + 1) * BANDS + m] = use_b ? rg_fp_band(zat, t.e[m], t.e[m + 1], 1) : 0.0f;
+        }
+        // a tile owns every frame but its first, which is the last of the tile before; tile 0 owns that too
+        if (bad_a && (pr || !tile)) ++nonfinite;
+        if (has_b && bad_b) ++nonfinite;
+    }
+    *nf_out = nf;
+    return nonfinite;
+}
+
 // ---- host side (rg_fprint_host.cpp) ------------------------------------------------------------------------------------------
 // the options, checked: NULL or a zero field = the default
 int rg_fp_options(const rg_fingerprint_opts *opts, rg_fingerprint_opts *out, char *err, size_t err_len);
@@ -108,7 +219,26 @@ int rg_fp_options(const rg_fingerprint_opts *opts, rg_fingerprint_opts *out, cha
 int rg_fp_track(size_t i, const rg_track_desc &t, size_t arena_bytes, RgFpTrack *out, char *err, size_t err_len);
 // first_tile of tracks[0 .. n), the tiles of one format contiguous: fmt_tile[f] .. fmt_tile[f + 1]; codes_at and frames_at
 // packed in track order from codes_base / frames_base; -> tiles
-uint64_t rg_fp_plan(RgFpTrack *tracks, size_t n, uint64_t fmt_tile[4], uint64_t codes_base, uint64_t frames_base);
+// (inline: the tempo scan plans its tiles with it too)
+inline uint64_t rg_fp_plan(RgFpTrack *tracks, size_t n, uint64_t fmt_tile[4], uint64_t codes_base, uint64_t frames_base) {
+    uint64_t tiles = 0;
+    for (uint32_t f = 0; f < 3; ++f) {
+        fmt_tile[f] = tiles;
+        for (size_t i = 0; i < n; ++i) {
+            if (tracks[i].format != f) continue;
+            tracks[i].first_tile = tiles;
+            tiles += tracks[i].n_tiles;
+        }
+    }
+    fmt_tile[3] = tiles;
+    for (size_t i = 0; i < n; ++i) {
+        tracks[i].codes_at = codes_base;
+        tracks[i].frames_at = frames_base;
+        codes_base += tracks[i].frames ? tracks[i].frames - 1u : 0u;
+        frames_base += tracks[i].frames;
+    }
+    return tiles;
+}
 // route 0 and route 2 of one track: codes[0 .. K), bands[0 .. 33 F) (either may be NULL), -> non-finite frames
 uint32_t rg_fp_serial_host(const unsigned char *arena, const RgFpTrack &t, uint32_t *codes, float *bands);
 uint32_t rg_fp_folded_host(const unsigned char *arena, const RgFpTrack &t, uint32_t *codes, float *bands);

@@ -12,8 +12,6 @@
 
 #include "rg_fprint.h"
 
-static const double kPi = 3.14159265358979323846;
-
 extern "C" int rg_fingerprint_edges(uint32_t sample_rate, uint32_t *edges) {
     if (!edges || !sample_rate) return RG_ERR_INVALID_ARG;
     bool ok = true;
@@ -54,76 +52,7 @@ int rg_fp_track(size_t i, const rg_track_desc &t, size_t arena_bytes, RgFpTrack 
     return RG_OK;
 }
 
-uint64_t rg_fp_plan(RgFpTrack *tracks, size_t n, uint64_t fmt_tile[4], uint64_t codes_base, uint64_t frames_base) {
-    uint64_t tiles = 0;
-    for (uint32_t f = 0; f < 3; ++f) {
-        fmt_tile[f] = tiles;
-        for (size_t i = 0; i < n; ++i) {
-            if (tracks[i].format != f) continue;
-            tracks[i].first_tile = tiles;
-            tiles += tracks[i].n_tiles;
-        }
-    }
-    fmt_tile[3] = tiles;
-    for (size_t i = 0; i < n; ++i) {
-        tracks[i].codes_at = codes_base;
-        tracks[i].frames_at = frames_base;
-        codes_base += tracks[i].frames ? tracks[i].frames - 1u : 0u;
-        frames_base += tracks[i].frames;
-    }
-    return tiles;
-}
-
-// sample k of the track's signal: the channel, or the mean of the first two, in f32
-static inline float signal_at(const unsigned char *arena, const RgFpTrack &t, uint64_t k) {
-    const auto value = [&](uint64_t off) {
-        const uint32_t raw = rg_pcm_raw_at(arena + off, t.format, k);
-        switch (t.format) {
-            case RG_FMT_F32_PLANAR: return rg_spec_value<RG_FMT_F32_PLANAR>(raw);
-            case RG_FMT_S16_PLANAR: return rg_spec_value<RG_FMT_S16_PLANAR>(raw);
-            default: return rg_spec_value<RG_FMT_S32_PLANAR>(raw);
-        }
-    };
-    const float a = value(t.off0);
-    return t.channels >= 2 ? (a + value(t.off1)) * 0.5f : a;
-}
-
-// ---- route 0: the definitions ------------------------------------------------------------------------------------------------
-// re, im <- their L-point DFT: decimation in time, radix 2, in double
-static void fft_double(double *re, double *im) {
-    const uint32_t L = RG_FP_FRAME;
-    static const std::vector<double> *roots = [] {
-        std::vector<double> *r = new std::vector<double>(RG_FP_FRAME);  // cos, -sin of 2 pi k / L, k < L / 2
-        for (uint32_t k = 0; k < RG_FP_FRAME / 2; ++k) {
-            (*r)[2 * k] = std::cos(2.0 * kPi * k / RG_FP_FRAME);
-            (*r)[2 * k + 1] = -std::sin(2.0 * kPi * k / RG_FP_FRAME);
-        }
-        return r;
-    }();
-    for (uint32_t i = 1, j = 0; i < L; ++i) {  // bit reversal
-        uint32_t bit = L >> 1;
-        for (; j & bit; bit >>= 1) j ^= bit;
-        j ^= bit;
-        if (i < j) {
-            std::swap(re[i], re[j]);
-            std::swap(im[i], im[j]);
-        }
-    }
-    for (uint32_t len = 2; len <= L; len <<= 1) {
-        const uint32_t step = L / len;
-        for (uint32_t i = 0; i < L; i += len)
-            for (uint32_t k = 0; k < len / 2; ++k) {
-                const double wr = (*roots)[2 * k * step], wi = (*roots)[2 * k * step + 1];
-                const uint32_t a = i + k, b = i + k + len / 2;
-                const double xr = re[b] * wr - im[b] * wi, xi = re[b] * wi + im[b] * wr;
-                re[b] = re[a] - xr;
-                im[b] = im[a] - xi;
-                re[a] += xr;
-                im[a] += xi;
-            }
-    }
-}
-
+// ---- route 0: the definitions (the signal and the double transform are rg_fprint.h's, shared with the tempo scan) ---------------
 uint32_t rg_fp_serial_host(const unsigned char *arena, const RgFpTrack &t, uint32_t *codes, float *bands) {
     const RgSpecTables &tb = rg_spec_tables();
     std::vector<double> re(RG_FP_FRAME), im(RG_FP_FRAME);
@@ -132,7 +61,7 @@ uint32_t rg_fp_serial_host(const unsigned char *arena, const RgFpTrack &t, uint3
     for (uint32_t n = 0; n < t.frames; ++n) {
         bool bad = false;
         for (uint32_t k = 0; k < RG_FP_FRAME; ++k) {
-            const float x = signal_at(arena, t, (uint64_t)n * RG_FP_HOP + k);
+            const float x = rg_fp_signal_at(arena, t, (uint64_t)n * RG_FP_HOP + k);
             bad |= rg_fp_nonfinite(x);
             re[k] = (double)x * (double)tb.window[k];
             im[k] = 0.0;
@@ -141,7 +70,7 @@ uint32_t rg_fp_serial_host(const unsigned char *arena, const RgFpTrack &t, uint3
             ++nonfinite;
             for (uint32_t m = 0; m < RG_FP_BANDS; ++m) cur[m] = 0.0;
         } else {
-            fft_double(re.data(), im.data());
+            rg_fp_fft_double(re.data(), im.data());
             for (uint32_t m = 0; m < RG_FP_BANDS; ++m) {
                 double s = 0.0;
                 for (uint32_t b = t.e[m]; b < t.e[m + 1]; ++b) s += re[b] * re[b] + im[b] * im[b];
@@ -164,56 +93,9 @@ uint32_t rg_fp_serial_host(const unsigned char *arena, const RgFpTrack &t, uint3
 // ---- route 2: the kernels' arithmetic ---------------------------------------------------------------------------------------
 // one workgroup of the tile kernel: tile `tile` of the track; -> the non-finite frames among those the tile owns
 static uint32_t tile_host(const unsigned char *arena, const RgFpTrack &t, uint32_t tile, uint32_t *codes, float *bands) {
-    const RgSpecTables &tb = rg_spec_tables();
-    const uint32_t f0 = tile * RG_FP_TILE_CODES, left = t.frames - f0, nf = left < RG_FP_TILE_FRAMES ? left : RG_FP_TILE_FRAMES;
-    const uint32_t count = (nf - 1u) * RG_FP_HOP + RG_FP_FRAME;
-    std::vector<float> pcm(count);
-    for (uint32_t k = 0; k < count; ++k) pcm[k] = signal_at(arena, t, (uint64_t)f0 * RG_FP_HOP + k);
-    std::vector<RgSpecC> x(RG_SPEC_FRAME), z(RG_SPEC_FRAME);
     float E[RG_FP_TILE_FRAMES * RG_FP_BANDS];
-    uint32_t nonfinite = 0;
-    for (uint32_t pr = 0; pr < nf; pr += 2) {
-        const bool has_b = pr + 1 < nf;
-        const float *fa = &pcm[pr * RG_FP_HOP], *fb = has_b ? fa + RG_FP_HOP : fa;
-        bool bad_a = false, bad_b = false;
-        if (t.format == RG_FMT_F32_PLANAR)
-            for (uint32_t n = 0; n < RG_FP_FRAME; ++n) {
-                bad_a |= rg_fp_nonfinite(fa[n]);
-                if (has_b) bad_b |= rg_fp_nonfinite(fb[n]);
-            }
-        const bool use_a = !bad_a, use_b = has_b && !bad_b;
-        RgSpecC v[16];
-        for (uint32_t l = 0; l < RG_FP_LANES; ++l) {  // pass 1: lane l = 16 n1 + n0
-            for (uint32_t n2 = 0; n2 < 16; ++n2) {
-                const uint32_t n = 256 * n2 + l;
-                const float w = tb.window[n];
-                v[n2].x = use_a ? fa[n] * w : 0.0f;
-                v[n2].y = use_b ? fb[n] * w : 0.0f;
-            }
-            rg_spec_pass1(v, l, tb.tw1);
-            for (uint32_t k0 = 0; k0 < 16; ++k0) x[k0 * 256 + l] = v[k0];
-        }
-        for (uint32_t l = 0; l < RG_FP_LANES; ++l) {  // pass 2: lane l = 16 k0 + n0, in place
-            const uint32_t k0 = l >> 4, n0 = l & 15u;
-            for (uint32_t n1 = 0; n1 < 16; ++n1) v[n1] = x[k0 * 256 + n1 * 16 + n0];
-            rg_spec_pass2(v, n0, tb.tw2);
-            for (uint32_t k1 = 0; k1 < 16; ++k1) x[k0 * 256 + k1 * 16 + n0] = v[k1];
-        }
-        for (uint32_t l = 0; l < RG_FP_LANES; ++l) {  // pass 3: lane l = 16 k1 + k0
-            const uint32_t k1 = l >> 4, k0 = l & 15u;
-            for (uint32_t n0 = 0; n0 < 16; ++n0) v[n0] = x[k0 * 256 + k1 * 16 + n0];
-            rg_spec_dft16(v);
-            for (uint32_t k2 = 0; k2 < 16; ++k2) z[l + 256 * k2] = v[k2];
-        }
-        const auto zat = [&](uint32_t k) { return z[k]; };
-        for (uint32_t m = 0; m < RG_FP_BANDS; ++m) {
-            E[pr * RG_FP_BANDS + m] = use_a ? rg_fp_band(zat, t.e[m], t.e[m + 1], 0) : 0.0f;
-            if (has_b) E[(pr + 1) * RG_FP_BANDS + m] = use_b ? rg_fp_band(zat, t.e[m], t.e[m + 1], 1) : 0.0f;
-        }
-        // a tile owns every frame but its first, which is the last of the tile before; tile 0 owns that too
-        if (bad_a && (pr || !tile)) ++nonfinite;
-        if (has_b && bad_b) ++nonfinite;
-    }
+    uint32_t nf = 0;
+    const uint32_t f0 = tile * RG_FP_TILE_CODES, nonfinite = rg_fp_tile_bands_host<RG_FP_BANDS>(arena, t, tile, E, &nf);
     for (uint32_t i = 0; i + 1 < nf; ++i)
         if (codes) codes[f0 + i] = rg_fp_code(&E[i * RG_FP_BANDS], &E[(i + 1) * RG_FP_BANDS]);
     if (bands)

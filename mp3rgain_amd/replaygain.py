@@ -592,6 +592,132 @@ def fingerprint_from_record(r, error=None) -> Fingerprint:
                        int(r.codes), int(r.nonfinite_frames), int(r.group), int(r.matches), error)
 
 
+def _tempo_opts(window, hop, min_bpm):
+    """rg_tempo_opts, or NULL (the header's defaults) when all are None; a None field is its default."""
+    if window is None and hop is None and min_bpm is None:
+        return None
+    return C.byref(_capi.TempoOpts(int(window or 0), int(hop or 0), int(min_bpm or 0)))
+
+
+def tempo_bands(sample_rate: int):
+    """rg_tempo_bands -> (the 33 band edges as a list, whether the rate is supported)."""
+    e = (C.c_uint32 * (_capi.TEMPO_BANDS + 1))()
+    rc = _capi.load().rg_tempo_bands(int(sample_rate), e)
+    if rc not in (0, _capi.RG_ERR_UNSUPPORTED_RATE):
+        raise ReplayGainError(rc, f"rg_tempo_bands: rate {sample_rate}")
+    return list(e), rc == 0
+
+
+def tempo_arena(ctx, route: int, descs, arena, window=None, hop=None, min_bpm=None, bands=True):
+    """rg_tempo_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> ([TempoRecord], onsets, bands):
+    onsets a uint16 array of every track's curve in track order (record.onsets_at, record.onsets), bands a float32 array
+    [sum of F][32] in track order (record.band_frames rows each; None when `bands` is false)."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    out = (_capi.TempoRecord * max(1, n))()
+    most = sum(fingerprint_codes(int(t.frames)) + 1 for t in descs)  # the frames of every track at a supported rate
+    onsets = np.zeros(max(1, most), dtype=np.uint16)
+    e = np.zeros((max(1, most), _capi.TEMPO_BANDS), dtype=np.float32) if bands else None
+    rc = L.rg_tempo_arena(ctx, int(route), n, d, arena.ctypes.data if arena.size else None, arena.size, _tempo_opts(window, hop, min_bpm), out,
+                          onsets.ctypes.data_as(C.POINTER(C.c_uint16)), e.ctypes.data_as(C.POINTER(C.c_float)) if bands else None)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    recs = list(out[:n])
+    return recs, onsets[:sum(int(r.onsets) for r in recs)], (e[:sum(int(r.band_frames) for r in recs)] if bands else None)
+
+
+def tempo_from_onsets(ctx, route: int, onsets, rates, window=None, hop=None, min_bpm=None):
+    """rg_tempo_from_onsets on constructed curves: `onsets` a list of uint16 arrays, one per track, `rates` their sample rates;
+    route 0 is the host (ctx = None), route 1 the kernels -> ([TempoRecord], acf): acf an int64 array [n][W], C of every track."""
+    L = _capi.load()
+    n = len(onsets)
+    counts = np.array([len(o) for o in onsets], dtype=np.uint32)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(o, dtype=np.uint16) for o in onsets]) if n else np.zeros(0, dtype=np.uint16))
+    r = np.array(list(rates), dtype=np.uint32)
+    W = int(window or _capi.TEMPO_WINDOW)
+    out = (_capi.TempoRecord * max(1, n))()
+    acf = np.zeros((max(1, n), max(1, min(W, _capi.TEMPO_MAX_WINDOW))), dtype=np.int64)
+    u32p = C.POINTER(C.c_uint32)
+    rc = L.rg_tempo_from_onsets(ctx, int(route), n, counts.ctypes.data_as(u32p), r.ctypes.data_as(u32p),
+                                flat.ctypes.data_as(C.POINTER(C.c_uint16)) if flat.size else None, _tempo_opts(window, hop, min_bpm), out,
+                                acf.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return list(out[:n]), acf[:n]
+
+
+def tempo_kernel_shape():
+    """rg_tempo_kernel_shape -> (tile_onsets, lanes, lds_bytes, acf_lanes, lags_per_lane)."""
+    v = [C.c_uint32() for _ in range(5)]
+    rc = _capi.load().rg_tempo_kernel_shape(*[C.byref(x) for x in v])
+    if rc != 0:
+        raise ReplayGainError(rc, "rg_tempo_kernel_shape")
+    return tuple(x.value for x in v)
+
+
+@dataclass
+class Tempo:
+    """One file of Analyzer.tempo (rg_tempo_result).  The estimator is a convention of include/mp3rgain_amd_tempo.h, tried on
+    this project's own synthetic material only; the reading lies in [min_bpm, 2 min_bpm) by convention."""
+    frames: int
+    sample_rate: int
+    channels: int
+    format: int
+    dropped_frames: int
+    flags: int
+    onsets: int
+    windows: int
+    period16: int
+    harmonics: int
+    bpm_milli: int
+    confidence_permille: int
+    stable_permille: int
+    first_beat: int
+    nonfinite_frames: int
+    error: Optional["ReplayGainError"] = None  # why there is no reading; every other field is then zero
+
+    @property
+    def found(self) -> bool:
+        return self.error is None and self.period16 != 0
+
+    @property
+    def bpm(self) -> Optional[float]:
+        return self.bpm_milli / 1000.0 if self.found else None
+
+    @property
+    def confidence(self) -> float:
+        return self.confidence_permille / 1000.0
+
+    @property
+    def steady(self) -> float:
+        return self.stable_permille / 1000.0
+
+    @property
+    def first_beat_seconds(self) -> Optional[float]:
+        return self.first_beat / self.sample_rate if self.found and self.sample_rate else None
+
+    @property
+    def complete(self) -> bool:
+        return bool(self.flags & _capi.TEMPO_COMPLETE)
+
+    @property
+    def verdicts(self) -> list:
+        """The flags as words, in a fixed order; ["ok"] when there is nothing to report."""
+        f = self.flags
+        names = (("rate", f & _capi.TEMPO_RATE), ("short", f & _capi.TEMPO_SHORT and not f & _capi.TEMPO_RATE), ("range", f & _capi.TEMPO_RANGE),
+                 ("none", f & _capi.TEMPO_NONE), ("nonfinite", f & _capi.TEMPO_NONFINITE), ("incomplete", self.error is None and not self.complete))
+        return [n for n, on in names if on] or ["ok"]
+
+
+def tempo_from_record(r, error=None) -> Tempo:
+    """A Tempo from an rg_tempo_result."""
+    return Tempo(int(r.frames), int(r.sample_rate), int(r.channels), int(r.format), int(r.dropped_frames), int(r.flags), int(r.onsets), int(r.windows),
+                 int(r.period16), int(r.harmonics), int(r.bpm_milli), int(r.confidence_permille), int(r.stable_permille), int(r.first_beat),
+                 int(r.nonfinite_frames), error)
+
+
 def _ancestry_opts(segments, granules, z_min, iso_min, active_floor):
     """rg_ancestry_opts, or NULL (the header's defaults) when all are None.  segments = 0 is the whole plane as one segment."""
     if segments is None and granules is None and z_min is None and iso_min is None and active_floor is None:
@@ -1716,6 +1842,39 @@ class Analyzer:
     @staticmethod
     def fingerprint_kernel_shape():
         return fingerprint_kernel_shape()
+
+    def _tempo_call(self, files, window, hop, min_bpm, onsets_cap):
+        paths, out = self._file_args(files, _capi.TempoRecord)
+        onsets = np.zeros(max(1, int(onsets_cap)), dtype=np.uint16) if onsets_cap else None
+        self._check(self._lib.rg_tempo(self._ctx, paths, len(files), _tempo_opts(window, hop, min_bpm), out,
+                                       onsets.ctypes.data_as(C.POINTER(C.c_uint16)) if onsets_cap else None, int(onsets_cap) if onsets_cap else 0))
+        return out, onsets
+
+    def tempo(self, files, window=None, hop=None, min_bpm=None):
+        """rg_tempo: `files` (WAV, FLAC or MPEG Layer III) decoded by the route the analysis uses; the onset curve, its windowed
+        autocorrelation and the beat grid where the PCM lies, all on this GPU -> [Tempo].  A file that fails carries its
+        ReplayGainError in `.error`."""
+        out, _ = self._tempo_call(files, window, hop, min_bpm, 0)
+        return [tempo_from_record(r, err) for r, err in self._file_records(out, len(files))]
+
+    def tempo_raw(self, files, window=None, hop=None, min_bpm=None, onsets_cap=0):
+        """tempo's arrays as the C call left them -> (record bytes, [TempoRecord], onsets or None): tests compare routes byte for
+        byte."""
+        out, onsets = self._tempo_call(files, window, hop, min_bpm, onsets_cap)
+        return bytes(out)[:len(files) * C.sizeof(_capi.TempoRecord)], list(out[:len(files)]), onsets
+
+    def tempo_arena(self, route: int, descs, arena, window=None, hop=None, min_bpm=None, bands=True):
+        """rg_tempo_arena, the seam of the tempo kernels -> ([TempoRecord], onsets, bands); route 0 = the serial host twin,
+        route 1 = the arena copied to this GPU and the kernels, route 2 = the kernels' arithmetic on the host."""
+        return tempo_arena(self._ctx, route, descs, arena, window, hop, min_bpm, bands)
+
+    def tempo_from_onsets(self, route: int, onsets, rates, window=None, hop=None, min_bpm=None):
+        """rg_tempo_from_onsets, the seam of the window and finish kernels, on constructed curves -> ([TempoRecord], acf)."""
+        return tempo_from_onsets(self._ctx, route, onsets, rates, window, hop, min_bpm)
+
+    @staticmethod
+    def tempo_kernel_shape():
+        return tempo_kernel_shape()
 
     def _ancestry_call(self, files, segments, granules, z_min, iso_min, active_floor):
         paths, out = self._file_args(files, _capi.AncestryRecord)
