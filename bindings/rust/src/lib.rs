@@ -549,6 +549,75 @@ pub mod replaygain {
     }
 }
 
+/// The key scan of `include/mp3rgain_amd_key.h`: in which musical key is each of these WAV, FLAC or MP3 files?  The signal
+/// decimated to 5 .. 10 kHz, a chroma row per 512 decimated samples from 60 semitone bands (C2 .. B6, A4 = 440 Hz), the rows summed
+/// and matched against the Krumhansl-Kessler profiles of the 12 major and 12 minor keys, all on the GPU and all integer after the
+/// rows.  The estimator is a convention of that header, tried on synthetic material only and held to no other key finder; key
+/// changes are only flagged (`stable_permille`).  A module of its own, as [`tempo`] is.
+/// `tests/test_rust_key_layout.py` compares these declarations with the header.
+pub mod key {
+    use super::ffi::RgCtx;
+    use std::os::raw::{c_char, c_int};
+
+    pub const KEY_SHORT: u32 = 1;
+    pub const KEY_RATE: u32 = 2;
+    pub const KEY_NONFINITE: u32 = 4;
+    pub const KEY_COMPLETE: u32 = 8;
+    pub const KEY_NONE: u32 = 16;
+    pub const KEY_MAX_CHANNELS: usize = 8;
+    pub const KEY_FRAME: u32 = 4096;
+    pub const KEY_HOP: u32 = 512;
+    pub const KEY_BANDS: u32 = 60;
+    pub const KEY_CHROMA: u32 = 12;
+    pub const KEY_RANGE: u32 = 160;
+    pub const KEY_TARGET_RATE: u32 = 5000;
+    pub const KEY_MAX_DECIM: u32 = 80;
+    pub const KEY_TAPS_PER_DECIM: u32 = 16;
+    /// `RG_KEY_SEGMENT`: what a zero in the options means
+    pub const KEY_SEGMENT: u32 = 128;
+    pub const KEY_MIN_SEGMENT: u32 = 8;
+    pub const KEY_MAX_SEGMENT: u32 = 4096;
+    pub const KEY_ROW_MAX: u32 = 800;
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_key_opts`: a zero means the default; a null pointer likewise
+    pub struct RgKeyOpts {
+        pub segment: u32,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_key_result`: `key` = 12 mode + tonic, meaningful without `KEY_SHORT`, `KEY_RATE` and `KEY_NONE` in `flags`
+    pub struct RgKeyResult {
+        pub status: i32,
+        pub flags: u32,
+        pub frames: u64,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub format: u32,
+        pub dropped_frames: u32,
+        pub decim: u32,
+        pub decimated: u32,
+        pub rows: u32,
+        pub silent_rows: u32,
+        pub nonfinite_frames: u32,
+        pub key: u32,
+        pub tonic: u32,
+        pub mode: u32,
+        pub correlation_permille: u32,
+        pub margin_permille: u32,
+        pub segments: u32,
+        pub stable_permille: u32,
+        pub chroma_at: u64,
+    }
+
+    extern "C" {
+        pub fn rg_key(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, opts: *const RgKeyOpts, out: *mut RgKeyResult, chroma_out: *mut u16,
+                      chroma_cap: usize) -> c_int;
+    }
+}
+
 /// The tempo scan of `include/mp3rgain_amd_tempo.h`: how fast is each of these WAV, FLAC or MP3 files?  An onset curve per file (one
 /// integer per 512 samples from 32 bands between 60 and 8000 Hz), its windowed autocorrelation and a constant-tempo beat grid, all
 /// on the GPU and all integer after the onset curve.  The estimator is a convention of that header, tried on synthetic material

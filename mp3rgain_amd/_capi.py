@@ -577,6 +577,52 @@ TEMPO_SYMBOLS = [
                              _P(_sz)]),
 ]
 
+# include/mp3rgain_amd_key.h (musical key: the decimated chromagram and the key-profile match)
+KEY_SHORT, KEY_RATE, KEY_NONFINITE, KEY_COMPLETE, KEY_NONE = 1, 2, 4, 8, 16
+KEY_MAX_CHANNELS, KEY_FRAME, KEY_HOP, KEY_BANDS, KEY_CHROMA, KEY_RANGE = 8, 4096, 512, 60, 12, 160
+KEY_TARGET_RATE, KEY_MAX_DECIM, KEY_TAPS_PER_DECIM = 5000, 80, 16
+KEY_SEGMENT, KEY_MIN_SEGMENT, KEY_MAX_SEGMENT, KEY_ROW_MAX = 128, 8, 4096, 800
+
+
+class KeyOpts(C.Structure):  # rg_key_opts
+    _fields_ = [("segment", C.c_uint32)]
+
+
+class KeyRecord(C.Structure):  # rg_key_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("decim", C.c_uint32),
+        ("decimated", C.c_uint32),
+        ("rows", C.c_uint32),
+        ("silent_rows", C.c_uint32),
+        ("nonfinite_frames", C.c_uint32),
+        ("key", C.c_uint32),
+        ("tonic", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("correlation_permille", C.c_uint32),
+        ("margin_permille", C.c_uint32),
+        ("segments", C.c_uint32),
+        ("stable_permille", C.c_uint32),
+        ("chroma_at", C.c_uint64),
+    ]
+
+
+KEY_SYMBOLS = [
+    ("rg_key_bands", _int, [_u32, _P(_u32), _P(_u32)]),
+    ("rg_key_filter", _int, [_u32, _P(C.c_float)]),
+    ("rg_key", _int, [_vp, _P(C.c_char_p), _sz, _P(KeyOpts), _P(KeyRecord), _P(C.c_uint16), _sz]),
+    ("rg_key_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _vp, _sz, _P(KeyOpts), _P(KeyRecord), _P(C.c_float), _P(C.c_float), _P(C.c_uint16)]),
+    ("rg_key_from_chroma", _int, [_vp, _int, _sz, _P(_u32), _P(C.c_uint16), _P(KeyOpts), _P(KeyRecord)]),
+    ("rg_key_kernel_shape", _int, [_P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_key_rate", _int, [_vp, _sz, _u64, _P(KeyOpts), _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz)]),
+]
+
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions
 NODE_OPEN = C.CFUNCTYPE(_vp, _int, _vp)
 NODE_CLOSE = C.CFUNCTYPE(None, _vp, _vp)
@@ -617,7 +663,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

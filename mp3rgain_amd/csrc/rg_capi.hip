@@ -329,6 +329,9 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_fp_codes.release();
     c->d_tempo.release();
     c->d_tp_onsets.release();
+    c->d_key.release();
+    c->d_key_decim.release();
+    c->d_key_rows.release();
     c->h_mp3_crc.release();
     if (c->file_pool && c->file_pool_free) c->file_pool_free(c->file_pool);
     c->file_pool = nullptr;

@@ -201,6 +201,9 @@ struct rg_ctx {
     DevBuf<uint32_t> d_fp_codes;             // the fingerprint codes of one rg_same_recording call, kept from group to group
     DevBuf<unsigned char> d_tempo;           // rg_tempo.hip: stage 1 as d_fprint, then [track records | window -> track | P16_w | C | finish records] of one launch
     DevBuf<uint16_t> d_tp_onsets;            // the onset curves of one group of an rg_tempo call (the seam: and the band energies behind them)
+    DevBuf<unsigned char> d_key;             // rg_key.hip: the tile walk's job as d_fprint, then [key track records | run starts | run -> track | taps | rows records | finish records] of one launch
+    DevBuf<float> d_key_decim;               // the decimated mono f32 signals of one group of an rg_key call, each track's run 16-byte aligned (the seam: and the band energies behind them)
+    DevBuf<uint16_t> d_key_rows;             // the chroma rows of that group, twelve per frame
     unsigned loader_threads = 0;             // tuning key 7: host threads of the file loaders; 0 = every core this process may use
     // Routing knobs of the file layer.  The environment is read ONCE, at rg_create (rg_capi.hip: read_env_defaults; getenv is
     // not safe against a host application's setenv, and a value that does not parse is ignored with a message in

@@ -2,8 +2,8 @@
 // (include/mp3rgain_amd_flac.h), rg_mp3_verify (include/mp3rgain_amd_mp3verify.h), rg_rip_checksums
 // (include/mp3rgain_amd_rip.h), and the four PCM scans, which share one group driver (pcm_scan_group): rg_pcm_stats
 // (include/mp3rgain_amd_stats.h), rg_dynamic_range (include/mp3rgain_amd_dr.h), rg_ancestry (include/mp3rgain_amd_ancestry.h),
-// rg_spectrum (include/mp3rgain_amd_spectrum.h), rg_same_recording (include/mp3rgain_amd_fingerprint.h) and rg_tempo
-// (include/mp3rgain_amd_tempo.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
+// rg_spectrum (include/mp3rgain_amd_spectrum.h), rg_same_recording (include/mp3rgain_amd_fingerprint.h), rg_tempo
+// (include/mp3rgain_amd_tempo.h) and rg_key (include/mp3rgain_amd_key.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
 // command: what this library does not decode itself is not a stream it could vouch for.  A file's status lives in its record,
 // and the record of a file that failed holds nothing else.
 #include <algorithm>
@@ -17,6 +17,7 @@
 #include "rg_rip.h"
 #include "rg_spectrum.h"
 #include "rg_tempo.h"
+#include "rg_key.h"
 #include "rg_stats.h"
 
 using namespace rgf;
@@ -718,4 +719,60 @@ extern "C" int rg_tempo(rg_ctx *c, const char *const *paths, size_t n, const rg_
     TempoCall call{onsets_out, onsets_out ? onsets_cap : 0};
     return pcm_scan_call(c, paths, n, opts, out, rg_tp_options,
                          [&](size_t first, size_t cnt, const rg_tempo_opts &o) { return tempo_group(c, paths, first, cnt, o, &call, out); });
+}
+
+// ---- rg_key: the decimation, tiles and finish kernels of rg_key.hip per group ----------------------------------------------
+// A group's decimated signals and chroma rows lie in c->d_key_decim and c->d_key_rows; the caller's copy of the rows is filled
+// group by group.
+namespace {
+struct KeyCall {
+    uint16_t *chroma_out;
+    size_t cap, used = 0;  // rows the caller's array holds, and those already in it
+};
+}  // namespace
+
+static int key_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_key_opts &o, KeyCall *call, rg_key_result *out) {
+    FileGroup g(c, paths, first, n);
+    out += first;
+    std::vector<PcmRec> recs;  // plane: the track's place in `tracks`
+    std::vector<RgKeyTrack> tracks(n + 1);
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        const int rc = rg_key_track(i, g.descs[k], g.arena_bytes, &tracks[recs.size()], err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        recs.push_back(PcmRec{k, recs.size()});
+        return RG_OK;
+    };
+    const auto finish = [&]() -> int {
+        if (recs.empty()) return RG_OK;
+        hipStream_t s = c->file_stream();
+        std::vector<uint32_t> nonfinite(recs.size());
+        std::vector<RgKeyFinish> fin(recs.size());
+        const int rc = rg_key_device(c, c->d_arena.p, tracks.data(), recs.size(), o, false, fin.data(), nonfinite.data(), s);
+        if (rc != RG_OK) return rc;
+        // the caller's copy: whole tracks, as many as fit
+        size_t fit = 0;
+        for (const PcmRec &r : recs) {
+            const RgKeyTrack &t = tracks[r.plane];
+            uint64_t at = UINT64_MAX;
+            if (call->chroma_out && fit == t.rows_at && call->used + t.rows_at + t.rows <= call->cap) {
+                at = call->used + t.rows_at;
+                fit = (size_t)(t.rows_at + t.rows);
+            }
+            rg_key_fill(&g.descs[r.k], &t, t.rows, fin[r.plane], dropped_frames(g, r.k), nonfinite[r.plane], at, &out[g.slot[r.k]]);
+        }
+        if (fit) {
+            RG_HIP(c, hipMemcpyAsync(call->chroma_out + call->used * RG_KEY_CHROMA, c->d_key_rows.p, fit * RG_KEY_CHROMA * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+            RG_HIP(c, hipStreamSynchronize(s));
+            call->used += fit;
+        }
+        return RG_OK;
+    };
+    return pcm_scan_group(g, "key", RG_KEY_MAX_CHANNELS, out, add, finish);
+}
+
+extern "C" int rg_key(rg_ctx *c, const char *const *paths, size_t n, const rg_key_opts *opts, rg_key_result *out, uint16_t *chroma_out, size_t chroma_cap) {
+    if (!c || (chroma_cap && !chroma_out)) return RG_ERR_INVALID_ARG;
+    KeyCall call{chroma_out, chroma_out ? chroma_cap : 0};
+    return pcm_scan_call(c, paths, n, opts, out, rg_key_options,
+                         [&](size_t first, size_t cnt, const rg_key_opts &o) { return key_group(c, paths, first, cnt, o, &call, out); });
 }

@@ -76,6 +76,15 @@ RG_SPEC_HD bool rg_fp_nonfinite(float x) {
     return (u & 0x7F800000u) == 0x7F800000u;
 }
 
+// q(E) of the tempo and key scans (rg_tempo.h, rg_key.h): the bit pattern of max(E, 2^-16), shifted right by 18 (a NaN takes
+// the floor); one step is 1/32 of an octave of power
+RG_SPEC_HD uint32_t rg_tp_q(float e) {
+    const float x = e > 1.52587890625e-5f ? e : 1.52587890625e-5f;
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    return u >> 18;
+}
+
 // the best lag so far of a pair; bits == 0: none
 struct RgFpBest {
     uint32_t errors, bits;
@@ -155,11 +164,13 @@ inline void rg_fp_fft_double(double *re, double *im) {
 }
 
 // route 2, one workgroup of a tile kernel (rg_fprint_tile.h): the band energies of the tile's *nf frames, BANDS floats each, to
-// E[RG_FP_TILE_FRAMES * BANDS], with t.e[0 .. BANDS] the edges; -> the non-finite frames among those the tile owns.  The unit
+// E[RG_FP_TILE_FRAMES * BANDS], with t.e[0 .. BANDS] (or `edges`, when given) the edges; -> the non-finite frames among those the tile owns.  The unit
 // that instantiates it is compiled without contraction.
 template <uint32_t BANDS>
-inline uint32_t rg_fp_tile_bands_host(const unsigned char *arena, const RgFpTrack &t, uint32_t tile, float *E, uint32_t *nf_out) {
+inline uint32_t rg_fp_tile_bands_host(const unsigned char *arena, const RgFpTrack &t, uint32_t tile, float *E, uint32_t *nf_out,
+                                      const uint32_t *edges = nullptr) {
     const RgSpecTables &tb = rg_spec_tables();
+    const uint32_t *e = edges ? edges : t.e;  // the key scan's 61 edges do not fit the record
     const uint32_t f0 = tile * RG_FP_TILE_CODES, left = t.frames - f0, nf = left < RG_FP_TILE_FRAMES ? left : RG_FP_TILE_FRAMES;
     const uint32_t count = (nf - 1u) * RG_FP_HOP + RG_FP_FRAME;
     std::vector<float> pcm(count);
@@ -201,8 +212,8 @@ inline uint32_t rg_fp_tile_bands_host(const unsigned char *arena, const RgFpTrac
         }
         const auto zat = [&](uint32_t k) { return z[k]; };
         for (uint32_t m = 0; m < BANDS; ++m) {
-            E[pr * BANDS + m] = use_a ? rg_fp_band(zat, t.e[m], t.e[m + 1], 0) : 0.0f;
-            if (has_b) E[(pr + 1) * BANDS + m] = use_b ? rg_fp_band(zat, t.e[m], t.e[m + 1], 1) : 0.0f;
+            E[pr * BANDS + m] = use_a ? rg_fp_band(zat, e[m], e[m + 1], 0) : 0.0f;
+            if (has_b) E[(pr + 1) * BANDS + m] = use_b ? rg_fp_band(zat, e[m], e[m + 1], 1) : 0.0f;
         }
         // a tile owns every frame but its first, which is the last of the tile before; tile 0 owns that too
         if (bad_a && (pr || !tile)) ++nonfinite;

@@ -36,10 +36,11 @@ __device__ __forceinline__ float *rg_fp_tile_rows(unsigned char *s_raw) {
 
 // Tile t of track p by a workgroup of RG_FP_LANES lanes, every lane calling it: on return (after a barrier) the rows
 // E[i * BANDS + m], i < nf, lie at rg_fp_tile_rows; -> nf, the tile's frames (frame f0 = t * 7 is row 0).  *nonfinite: the
-// non-finite frames among those the tile owns (the same value in every lane).
+// non-finite frames among those the tile owns (the same value in every lane).  `edges`: BANDS + 1 edges to take instead of p.e.
 template <int FMT, uint32_t BANDS>
 __device__ __forceinline__ uint32_t rg_fp_tile_bands(const unsigned char *__restrict__ arena, const RgSpecTables *__restrict__ tables, const RgFpTrack &p,
-                                                     uint32_t t, unsigned char *s_raw, uint32_t *nonfinite_out) {
+                                                     uint32_t t, unsigned char *s_raw, uint32_t *nonfinite_out,
+                                                     const uint32_t *__restrict__ edges = nullptr) {
     RgSpecC *s_x = reinterpret_cast<RgSpecC *>(s_raw);
     float *s_pcm = reinterpret_cast<float *>(s_raw + RG_FP_XCH * 8u);
     float *s_E = s_pcm + RG_FP_STAGE;
@@ -56,7 +57,7 @@ __device__ __forceinline__ uint32_t rg_fp_tile_bands(const unsigned char *__rest
             const float a = fp_load<FMT>(p0, base + k);
             s_pcm[k] = two ? (a + fp_load<FMT>(p1, base + k)) * 0.5f : a;
         }
-        if (tid <= BANDS) s_e[tid] = p.e[tid];
+        if (tid <= BANDS) s_e[tid] = edges ? edges[tid] : p.e[tid];  // (the key scan's 61 edges do not fit the record)
     }
     float win[16];
 #pragma unroll

@@ -30,13 +30,7 @@ struct RgTpFinish {
     uint32_t period16, confidence_permille, stable_permille, first_beat;
 };
 
-// q(E): the bit pattern of max(E, 2^-16), shifted right by 18 (a NaN takes the floor)
-RG_SPEC_HD uint32_t rg_tp_q(float e) {
-    const float x = e > 1.52587890625e-5f ? e : 1.52587890625e-5f;
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u >> 18;
-}
+// (q(E), rg_tp_q, lies in rg_fprint.h: the key scan compresses its band energies with it too)
 // the onset of frame n from E[n - 1] (`prev`) and E[n] (`cur`), 32 floats each
 RG_SPEC_HD uint16_t rg_tp_onset(const float *prev, const float *cur) {
     uint32_t s = 0;

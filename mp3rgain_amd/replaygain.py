@@ -718,6 +718,173 @@ def tempo_from_record(r, error=None) -> Tempo:
                  int(r.nonfinite_frames), error)
 
 
+def _key_opts(segment):
+    """rg_key_opts, or NULL (the header's default) when `segment` is None."""
+    return None if segment is None else C.byref(_capi.KeyOpts(int(segment)))
+
+
+def key_bands(sample_rate: int):
+    """rg_key_bands -> (D, the 61 band edges as a list (None at an unsupported rate), whether the rate is supported)."""
+    e = (C.c_uint32 * (_capi.KEY_BANDS + 1))()
+    d = C.c_uint32()
+    rc = _capi.load().rg_key_bands(int(sample_rate), C.byref(d), e)
+    if rc not in (0, _capi.RG_ERR_UNSUPPORTED_RATE):
+        raise ReplayGainError(rc, f"rg_key_bands: rate {sample_rate}")
+    return d.value, (list(e) if rc == 0 else None), rc == 0
+
+
+def key_filter(decim: int):
+    """rg_key_filter -> the 16 D + 1 taps of factor D as a float32 array."""
+    taps = np.zeros(_capi.KEY_TAPS_PER_DECIM * int(decim) + 1, dtype=np.float32)
+    rc = _capi.load().rg_key_filter(int(decim), taps.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise ReplayGainError(rc, f"rg_key_filter: factor {decim}")
+    return taps
+
+
+def key_arena(ctx, route: int, descs, arena, segment=None, bands=True):
+    """rg_key_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> ([KeyRecord], y, bands, chroma): y a
+    float32 array of every track's decimated signal in track order (record.decimated each), bands a float32 array [sum of F][60]
+    (None when `bands` is false), chroma a uint16 array [sum of F][12] (record.chroma_at, record.rows)."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    out = (_capi.KeyRecord * max(1, n))()
+    most_y = sum(int(t.frames) for t in descs)
+    most_rows = sum(int(t.frames) // _capi.KEY_HOP + 1 for t in descs)
+    y = np.zeros(max(1, most_y), dtype=np.float32)
+    e = np.zeros((max(1, most_rows), _capi.KEY_BANDS), dtype=np.float32) if bands else None
+    chroma = np.zeros((max(1, most_rows), _capi.KEY_CHROMA), dtype=np.uint16)
+    rc = L.rg_key_arena(ctx, int(route), n, d, arena.ctypes.data if arena.size else None, arena.size, _key_opts(segment), out,
+                        y.ctypes.data_as(C.POINTER(C.c_float)), e.ctypes.data_as(C.POINTER(C.c_float)) if bands else None,
+                        chroma.ctypes.data_as(C.POINTER(C.c_uint16)))
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    recs = list(out[:n])
+    rows = sum(int(r.rows) for r in recs)
+    return recs, y[:sum(int(r.decimated) for r in recs)], (e[:rows] if bands else None), chroma[:rows]
+
+
+def key_from_chroma(ctx, route: int, chroma, segment=None):
+    """rg_key_from_chroma on constructed rows: `chroma` a list of uint16 arrays [F][12], one per track; route 0 is the host
+    (ctx = None), route 1 the finish kernel -> [KeyRecord]."""
+    L = _capi.load()
+    n = len(chroma)
+    rows = [np.asarray(c, dtype=np.uint16).reshape(-1, _capi.KEY_CHROMA) for c in chroma]
+    counts = np.array([len(c) for c in rows], dtype=np.uint32)
+    flat = np.ascontiguousarray(np.concatenate(rows) if n else np.zeros((0, _capi.KEY_CHROMA), dtype=np.uint16))
+    out = (_capi.KeyRecord * max(1, n))()
+    rc = L.rg_key_from_chroma(ctx, int(route), n, counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                              flat.ctypes.data_as(C.POINTER(C.c_uint16)) if flat.size else None, _key_opts(segment), out)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return list(out[:n])
+
+
+def key_kernel_shape():
+    """rg_key_kernel_shape -> (decim_outputs, decim_lanes, tile_rows, tile_lanes, tile_lds_bytes)."""
+    v = [C.c_uint32() for _ in range(5)]
+    rc = _capi.load().rg_key_kernel_shape(*[C.byref(x) for x in v])
+    if rc != 0:
+        raise ReplayGainError(rc, "rg_key_kernel_shape")
+    return tuple(x.value for x in v)
+
+
+KEY_TONICS = ("C", "C#", "D", "Eb", "E", "F", "F#", "G", "Ab", "A", "Bb", "B")
+
+
+def key_name(key: int) -> str:
+    """`A minor` for key 12 mode + tonic."""
+    return f"{KEY_TONICS[key % 12]} {'minor' if key // 12 else 'major'}"
+
+
+def key_camelot(key: int) -> str:
+    """The Camelot wheel: C major is 8B, A minor 8A; a minor key has the number of its relative major."""
+    tonic, minor = key % 12, key // 12
+    if minor:
+        tonic = (tonic + 3) % 12
+    return f"{((7 * tonic) % 12 + 7) % 12 + 1}{'A' if minor else 'B'}"
+
+
+def key_open_key(key: int) -> str:
+    """Open Key notation: Camelot number n -> ((n + 4) mod 12) + 1, `d` for major and `m` for minor; 8B is 1d."""
+    cam = key_camelot(key)
+    return f"{(int(cam[:-1]) + 4) % 12 + 1}{'m' if key // 12 else 'd'}"
+
+
+@dataclass
+class Key:
+    """One file of Analyzer.key (rg_key_result).  The estimator is a convention of include/mp3rgain_amd_key.h, tried on this
+    project's own synthetic material only."""
+    frames: int
+    sample_rate: int
+    channels: int
+    format: int
+    dropped_frames: int
+    flags: int
+    decim: int
+    decimated: int
+    rows: int
+    silent_rows: int
+    nonfinite_frames: int
+    key: int
+    tonic: int
+    mode: int
+    correlation_permille: int
+    margin_permille: int
+    segments: int
+    stable_permille: int
+    error: Optional["ReplayGainError"] = None  # why there is no reading; every other field is then zero
+
+    @property
+    def found(self) -> bool:
+        return self.error is None and not self.flags & (_capi.KEY_SHORT | _capi.KEY_RATE | _capi.KEY_NONE)
+
+    @property
+    def name(self) -> Optional[str]:
+        return key_name(self.key) if self.found else None
+
+    @property
+    def camelot(self) -> Optional[str]:
+        return key_camelot(self.key) if self.found else None
+
+    @property
+    def open_key(self) -> Optional[str]:
+        return key_open_key(self.key) if self.found else None
+
+    @property
+    def correlation(self) -> float:
+        return self.correlation_permille / 1000.0
+
+    @property
+    def margin(self) -> float:
+        return self.margin_permille / 1000.0
+
+    @property
+    def steady(self) -> float:
+        return self.stable_permille / 1000.0
+
+    @property
+    def complete(self) -> bool:
+        return bool(self.flags & _capi.KEY_COMPLETE)
+
+    @property
+    def verdicts(self) -> list:
+        """The flags as words, in a fixed order; ["ok"] when there is nothing to report."""
+        f = self.flags
+        names = (("rate", f & _capi.KEY_RATE), ("short", f & _capi.KEY_SHORT and not f & _capi.KEY_RATE), ("none", f & _capi.KEY_NONE),
+                 ("nonfinite", f & _capi.KEY_NONFINITE), ("incomplete", self.error is None and not self.complete))
+        return [n for n, on in names if on] or ["ok"]
+
+
+def key_from_record(r, error=None) -> Key:
+    """A Key from an rg_key_result."""
+    return Key(int(r.frames), int(r.sample_rate), int(r.channels), int(r.format), int(r.dropped_frames), int(r.flags), int(r.decim), int(r.decimated),
+               int(r.rows), int(r.silent_rows), int(r.nonfinite_frames), int(r.key), int(r.tonic), int(r.mode), int(r.correlation_permille),
+               int(r.margin_permille), int(r.segments), int(r.stable_permille), error)
+
+
 def _ancestry_opts(segments, granules, z_min, iso_min, active_floor):
     """rg_ancestry_opts, or NULL (the header's defaults) when all are None.  segments = 0 is the whole plane as one segment."""
     if segments is None and granules is None and z_min is None and iso_min is None and active_floor is None:
@@ -1875,6 +2042,39 @@ class Analyzer:
     @staticmethod
     def tempo_kernel_shape():
         return tempo_kernel_shape()
+
+    def _key_call(self, files, segment, chroma_cap):
+        paths, out = self._file_args(files, _capi.KeyRecord)
+        chroma = np.zeros((max(1, int(chroma_cap)), _capi.KEY_CHROMA), dtype=np.uint16) if chroma_cap else None
+        self._check(self._lib.rg_key(self._ctx, paths, len(files), _key_opts(segment), out,
+                                     chroma.ctypes.data_as(C.POINTER(C.c_uint16)) if chroma_cap else None, int(chroma_cap) if chroma_cap else 0))
+        return out, chroma
+
+    def key(self, files, segment=None):
+        """rg_key: `files` (WAV, FLAC or MPEG Layer III) decoded by the route the analysis uses; the decimation, the chroma rows
+        and the key-profile match where the PCM lies, all on this GPU -> [Key].  A file that fails carries its ReplayGainError
+        in `.error`."""
+        out, _ = self._key_call(files, segment, 0)
+        return [key_from_record(r, err) for r, err in self._file_records(out, len(files))]
+
+    def key_raw(self, files, segment=None, chroma_cap=0):
+        """key's arrays as the C call left them -> (record bytes, [KeyRecord], chroma rows or None): tests compare routes byte
+        for byte."""
+        out, chroma = self._key_call(files, segment, chroma_cap)
+        return bytes(out)[:len(files) * C.sizeof(_capi.KeyRecord)], list(out[:len(files)]), chroma
+
+    def key_arena(self, route: int, descs, arena, segment=None, bands=True):
+        """rg_key_arena, the seam of the key kernels -> ([KeyRecord], y, bands, chroma); route 0 = the serial host twin, route 1 =
+        the arena copied to this GPU and the kernels, route 2 = the kernels' arithmetic on the host."""
+        return key_arena(self._ctx, route, descs, arena, segment, bands)
+
+    def key_from_chroma(self, route: int, chroma, segment=None):
+        """rg_key_from_chroma, the seam of the finish kernel, on constructed rows -> [KeyRecord]."""
+        return key_from_chroma(self._ctx, route, chroma, segment)
+
+    @staticmethod
+    def key_kernel_shape():
+        return key_kernel_shape()
 
     def _ancestry_call(self, files, segments, granules, z_min, iso_min, active_floor):
         paths, out = self._file_args(files, _capi.AncestryRecord)
