@@ -549,6 +549,62 @@ pub mod replaygain {
     }
 }
 
+/// Duplicates across sample rates (`include/mp3rgain_amd_resample.h`): is this 96 kHz download that CD track?  Every file is brought
+/// to 11025 Hz by a rational polyphase resampler on the GPU, fingerprinted there by stage 1 of [`fingerprint`] and matched by its
+/// stage 2, whatever the file's own rate.  The options and the pairs are [`fingerprint`]'s; a zero option means this call's default.
+/// The threshold is measured on synthetic material only.  `tests/test_rust_resample_layout.py` compares these declarations with the
+/// header.
+pub mod resample {
+    use super::ffi::RgCtx;
+    use super::fingerprint::{RgFingerprintOpts, RgFingerprintPair};
+    use std::os::raw::{c_char, c_int};
+
+    pub const RS_SHORT: u32 = 1;
+    pub const RS_RATE: u32 = 2;
+    pub const RS_RATE_OUT: u32 = 11025;
+    pub const RS_MAX_PHASES: u32 = 441;
+    pub const RS_MAX_RATIO: u32 = 32;
+    pub const RS_MIN_RATE: u32 = 8000;
+    pub const RS_HALF_PER_W: u32 = 8;
+    pub const RS_MAX_CHANNELS: usize = 8;
+    /// `RG_XR_*`: what a zero in the options means here
+    pub const XR_BLOCK: u32 = 64;
+    pub const XR_PROBES: u32 = 8;
+    pub const XR_RADIUS: u32 = 128;
+    pub const XR_MAX_BER_PERMILLE: u32 = 303;
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_xrate_result`: `rg_fingerprint_result`'s fields for the file's signal at 11025 Hz, then L, M and the resampled count
+    pub struct RgXrateResult {
+        pub status: i32,
+        pub flags: u32,
+        pub frames: u64,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub format: u32,
+        pub dropped_frames: u32,
+        pub fp_frames: u32,
+        pub codes: u32,
+        pub nonfinite_frames: u32,
+        pub group: u32,
+        pub matches: u32,
+        pub reserved: u32,
+        pub codes_at: u64,
+        pub frames_at: u64,
+        pub up: u32,
+        pub down: u32,
+        pub resampled: u32,
+        pub reserved2: u32,
+        pub y_at: u64,
+    }
+
+    extern "C" {
+        pub fn rg_same_recording_xrate(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, opts: *const RgFingerprintOpts, out: *mut RgXrateResult,
+                                       pairs: *mut RgFingerprintPair, max_pairs: usize, n_pairs: *mut usize, codes_out: *mut u32, codes_cap: usize) -> c_int;
+    }
+}
+
 /// The key scan of `include/mp3rgain_amd_key.h`: in which musical key is each of these WAV, FLAC or MP3 files?  The signal
 /// decimated to 5 .. 10 kHz, a chroma row per 512 decimated samples from 60 semitone bands (C2 .. B6, A4 = 440 Hz), the rows summed
 /// and matched against the Krumhansl-Kessler profiles of the 12 major and 12 minor keys, all on the GPU and all integer after the

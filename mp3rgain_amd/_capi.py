@@ -623,6 +623,51 @@ KEY_SYMBOLS = [
     ("rg_key_rate", _int, [_vp, _sz, _u64, _P(KeyOpts), _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz)]),
 ]
 
+# include/mp3rgain_amd_resample.h (duplicates across sample rates: the rational resampler and the cross-rate fingerprint)
+RS_SHORT, RS_RATE = 1, 2
+RS_RATE_OUT, RS_MAX_PHASES, RS_MAX_RATIO, RS_MIN_RATE, RS_HALF_PER_W, RS_MAX_CHANNELS = 11025, 441, 32, 8000, 8, 8
+XR_BLOCK, XR_PROBES, XR_RADIUS, XR_MAX_BER_PERMILLE = 64, 8, 128, 303
+
+
+class ResampleRecord(C.Structure):  # rg_resample_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("up", C.c_uint32),
+        ("down", C.c_uint32),
+        ("taps", C.c_uint32),
+        ("resampled", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("y_at", C.c_uint64),
+    ]
+
+
+class XrateRecord(C.Structure):  # rg_xrate_result
+    _fields_ = FingerprintRecord._fields_ + [
+        ("up", C.c_uint32),
+        ("down", C.c_uint32),
+        ("resampled", C.c_uint32),
+        ("reserved2", C.c_uint32),
+        ("y_at", C.c_uint64),
+    ]
+
+
+RESAMPLE_SYMBOLS = [
+    ("rg_resample_plan", _int, [_u32, _P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_resample_filter", _int, [_u32, _u32, _P(C.c_float)]),
+    ("rg_resample_window", _int, [_u32, _u64, _P(_u64), _P(_u32)]),
+    ("rg_resample_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _vp, _sz, _P(ResampleRecord), _P(C.c_float)]),
+    ("rg_xrate_fingerprint_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _vp, _sz, _P(XrateRecord), _P(_u32), _P(C.c_float), _P(C.c_float)]),
+    ("rg_same_recording_xrate", _int, [_vp, _P(C.c_char_p), _sz, _P(FingerprintOpts), _P(XrateRecord), _P(FingerprintPair), _sz, _P(_sz),
+                                       _P(_u32), _sz]),
+    ("rg_resample_kernel_shape", _int, [_P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_resample_rate", _int, [_vp, _sz, _u64, _u32, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz)]),
+]
+
 # rg_node_backend (include/mp3rgain_amd_node.h): a table of per-device functions
 NODE_OPEN = C.CFUNCTYPE(_vp, _int, _vp)
 NODE_CLOSE = C.CFUNCTYPE(None, _vp, _vp)
@@ -663,7 +708,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS + RESAMPLE_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

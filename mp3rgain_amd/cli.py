@@ -81,6 +81,7 @@ class Options:  # src/main.rs:65-96
     ancestry_granules: Optional[int] = None  # with --ancestry (--ancestry-granules G): granules per segment
     duplicates: bool = False  # this façade only (--duplicates): which of these files are the same recording?  Fingerprints and every pair
     dup_radius: Optional[float] = None  # with --duplicates (--dup-radius SECONDS): the largest offset looked for, in seconds at 44.1 kHz
+    dup_any_rate: bool = False  # with --duplicates (--dup-any-rate): every file brought to 11025 Hz first, so copies at different sample rates match
     dup_ber: Optional[int] = None  # with --duplicates (--dup-ber PERMILLE): the share of differing bits up to which a pair matches
     tempo: bool = False  # this façade only (--tempo): how fast is each file?  BPM and a constant-tempo beat grid
     tempo_min: Optional[int] = None  # with --tempo (--tempo-min BPM): the reading lies in [BPM, 2 BPM)
@@ -186,6 +187,8 @@ def parse_args(args: List[str], out, err) -> Options:
             o.ancestry_granules = _parse_int(need("--ancestry-granules", "--ancestry-granules requires an argument"), "invalid granule count", 32, signed=False)
         elif arg == "--duplicates":  # not in the reference: a command of its own, like --stats
             o.duplicates = True
+        elif arg == "--dup-any-rate":
+            o.dup_any_rate = True
         elif arg == "--dup-radius":
             o.dup_radius = _parse_positive(need("--dup-radius", "--dup-radius requires an argument"), "invalid radius")
         elif arg == "--dup-ber":
@@ -336,9 +339,14 @@ def parse_args(args: List[str], out, err) -> Options:
         raise CliError("--dup-radius requires --duplicates")
     if o.dup_ber is not None and not o.duplicates:
         raise CliError("--dup-ber requires --duplicates")
+    if o.dup_any_rate and not o.duplicates:
+        raise CliError("--dup-any-rate requires --duplicates")
     if o.dup_ber is not None and not 1 <= o.dup_ber <= 1000:
         raise CliError(f"--dup-ber takes 1 to 1000 per mille: {o.dup_ber}")
-    if o.dup_radius is not None and not 1 <= dup_radius_codes(o.dup_radius) <= _capi.FP_MAX_RADIUS:
+    if o.dup_radius is not None and o.dup_any_rate and not 1 <= dup_radius_codes(o.dup_radius, _capi.RS_RATE_OUT) <= _capi.FP_MAX_RADIUS:
+        raise CliError(f"--dup-radius takes {512 / _capi.RS_RATE_OUT:.3f} to {_capi.FP_MAX_RADIUS * 512 / _capi.RS_RATE_OUT:.1f} seconds with --dup-any-rate: "
+                       f"{o.dup_radius}")
+    if o.dup_radius is not None and not o.dup_any_rate and not 1 <= dup_radius_codes(o.dup_radius) <= _capi.FP_MAX_RADIUS:
         raise CliError(f"--dup-radius takes {512 / 44100:.3f} to {_capi.FP_MAX_RADIUS * 512 / 44100:.1f} seconds: {o.dup_radius}")
     if o.duplicates:
         others = [name for name, on in (("--verify", o.verify), ("--rip", o.rip), ("--stats", o.stats), ("--spectrum", o.spectrum), ("--dr", o.dr),
@@ -387,9 +395,9 @@ def tempo_line(r) -> str:
     return f"{r.bpm:.2f} BPM  (confidence {r.confidence:.2f}, steady {r.steady:.2f}, first beat {r.first_beat_seconds:.3f} s)"
 
 
-def dup_radius_codes(seconds: float) -> int:
-    """--dup-radius in codes of 512 samples, taken at 44.1 kHz."""
-    return int(round(seconds * 44100.0 / 512.0))
+def dup_radius_codes(seconds: float, rate: float = 44100.0) -> int:
+    """--dup-radius in codes of 512 samples, taken at 44.1 kHz (with --dup-any-rate: at the common rate, 11025 Hz)."""
+    return int(round(seconds * rate / 512.0))
 
 
 # ---- JSON shapes (src/main.rs:101-165): field order of the structs, None fields skipped -----------------------
@@ -1099,9 +1107,17 @@ class Cli:
         file i, file j, lag of j in seconds, differing bits, bits, per mille`."""
         o = self.o
         devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
-        radius = None if o.dup_radius is None else dup_radius_codes(o.dup_radius)
+        any_rate = o.dup_any_rate  # every file at 11025 Hz first (rg_same_recording_xrate): a code is 46.4 ms for every file
+        radius = None if o.dup_radius is None else dup_radius_codes(o.dup_radius, _capi.RS_RATE_OUT if any_rate else 44100.0)
         with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
-            recs, pairs, groups = an.same_recording(o.files, radius=radius, max_ber_permille=o.dup_ber)
+            if any_rate:
+                recs, pairs, groups = an.same_recording_any_rate(o.files, radius=radius, max_ber_permille=o.dup_ber)
+            else:
+                recs, pairs, groups = an.same_recording(o.files, radius=radius, max_ber_permille=o.dup_ber)
+
+        def code_rate(k):  # the rate a code of file k counts 512 samples of
+            return _capi.RS_RATE_OUT if any_rate else recs[k].sample_rate
+
         if self.talk:
             self.p(f"mp3rgain duplicate search among {len(o.files)} file(s): sub-band fingerprints, every pair at every offset"
                    " (a convention of this project, compatible with no other fingerprint)")
@@ -1111,7 +1127,7 @@ class Cli:
 
         def against(first, k):  # -> (lag of file k against `first` in seconds, share of differing bits) or None
             p = by.get((first, k))
-            return None if p is None else (p.lag_of_j * 512.0 / recs[k].sample_rate, p.ber)
+            return None if p is None else (p.lag_of_j * 512.0 / code_rate(k), p.ber)
 
         if o.output_format == "json":
             files = []
@@ -1124,7 +1140,7 @@ class Cli:
                              channels=r.channels, dropped_frames=r.dropped_frames, nonfinite_frames=r.nonfinite_frames, complete=r.complete)
                 files.append(d)
             _print_json(self.out, files=files,
-                        pairs=[{"i": p.i, "j": p.j, "lag_codes": p.lag_of_j, "lag_seconds": p.lag_of_j * 512.0 / recs[p.j].sample_rate,
+                        pairs=[{"i": p.i, "j": p.j, "lag_codes": p.lag_of_j, "lag_seconds": p.lag_of_j * 512.0 / code_rate(p.j),
                                 "errors": p.errors, "bits": p.bits, "ber": p.ber} for p in pairs],
                         groups=[[str(o.files[k]) for k in g] for g in groups],
                         summary=_summary(len(o.files), len(o.files) - failed, failed, False))
@@ -1136,7 +1152,7 @@ class Cli:
                 else:
                     self.p(f"{_name(file)}\t{r.group}\t{','.join(r.verdicts)}\t{r.codes}\t{r.matches}\t{r.frames}\t{r.sample_rate}\t{r.dropped_frames}")
             for p in pairs:
-                self.p(f"pair\t{_name(o.files[p.i])}\t{_name(o.files[p.j])}\t{p.lag_of_j * 512.0 / recs[p.j].sample_rate:.3f}\t{p.errors}\t{p.bits}\t"
+                self.p(f"pair\t{_name(o.files[p.i])}\t{_name(o.files[p.j])}\t{p.lag_of_j * 512.0 / code_rate(p.j):.3f}\t{p.errors}\t{p.bits}\t"
                        f"{1000.0 * p.ber:.1f}")
             return 1 if failed else 0
         for file, r in zip(o.files, recs):
@@ -1147,10 +1163,10 @@ class Cli:
                 self.p(f"{_name(file)}  [{', '.join(notes)}]")
         for n, g in enumerate(groups, 1):
             self.p(f"group {n}: {len(g)} files")
-            self.p(f"    {_name(o.files[g[0]])}")
+            self.p(f"    {_name(o.files[g[0]])}" + (f"   {recs[g[0]].sample_rate} Hz" if any_rate else ""))
             for k in g[1:]:
                 a = against(g[0], k)
-                self.p(f"    {_name(o.files[k])}   " + ("via another member" if a is None else f"{a[0]:+.3f} s   {100.0 * a[1]:.1f} % of bits differ"))
+                self.p(f"    {_name(o.files[k])}   " + (f"{recs[k].sample_rate} Hz   " if any_rate else "") + ("via another member" if a is None else f"{a[0]:+.3f} s   {100.0 * a[1]:.1f} % of bits differ"))
             self.p()
         self.p(f"{len(o.files)} files, {len(groups)} groups of duplicates")
         return 1 if failed else 0
@@ -1928,6 +1944,9 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "            files[group, matches, codes, verdicts, ...], pairs[i, j, lag_codes, lag_seconds, errors, bits, ber], groups.",
         "            Exit status 1 only for a file that fails or has dropped frames",
         "--dup-radius <seconds>  With --duplicates: the largest offset looked for (default 5.94 = 512 codes at 44.1 kHz; at most 23.7)",
+        "--dup-any-rate  With --duplicates: every file is brought to 11025 Hz on the GPU first, so the 44.1 kHz rip and the 48 / 96 / 192 kHz",
+        "            download of the same master match; each member is shown with its own sample rate.  --dup-radius then defaults to",
+        f"            5.94 s = 128 codes of 46.4 ms, --dup-ber to {_capi.XR_MAX_BER_PERMILLE}",
         "--dup-ber <permille>  With --duplicates: the share of differing bits up to which a pair matches (default 316)",
         "--tempo     How fast is each file?  On the GPU (WAV, FLAC, MP3): an onset curve (one value per 512 samples from 32 bands between",
         "            60 and 8000 Hz), its autocorrelation over windows of 1024 onsets, and a constant-tempo beat grid.  A line per file:",

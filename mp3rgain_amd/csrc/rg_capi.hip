@@ -332,6 +332,8 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_key.release();
     c->d_key_decim.release();
     c->d_key_rows.release();
+    c->d_rs.release();
+    c->d_rs_y.release();
     c->h_mp3_crc.release();
     if (c->file_pool && c->file_pool_free) c->file_pool_free(c->file_pool);
     c->file_pool = nullptr;

@@ -204,6 +204,8 @@ struct rg_ctx {
     DevBuf<unsigned char> d_key;             // rg_key.hip: the tile walk's job as d_fprint, then [key track records | run starts | run -> track | taps | rows records | finish records] of one launch
     DevBuf<float> d_key_decim;               // the decimated mono f32 signals of one group of an rg_key call, each track's run 16-byte aligned (the seam: and the band energies behind them)
     DevBuf<uint16_t> d_key_rows;             // the chroma rows of that group, twelve per frame
+    DevBuf<unsigned char> d_rs;              // rg_resample.hip: [track records | run starts | run -> track | workgroup starts | tap tables] of one launch
+    DevBuf<float> d_rs_y;                    // the resampled mono f32 signals (11025 Hz) of one group of an rg_same_recording_xrate call, each track's run 16-byte aligned
     unsigned loader_threads = 0;             // tuning key 7: host threads of the file loaders; 0 = every core this process may use
     // Routing knobs of the file layer.  The environment is read ONCE, at rg_create (rg_capi.hip: read_env_defaults; getenv is
     // not safe against a host application's setenv, and a value that does not parse is ignored with a message in

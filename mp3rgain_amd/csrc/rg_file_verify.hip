@@ -18,6 +18,7 @@
 #include "rg_spectrum.h"
 #include "rg_tempo.h"
 #include "rg_key.h"
+#include "rg_resample.h"
 #include "rg_stats.h"
 
 using namespace rgf;
@@ -600,6 +601,36 @@ static int fingerprint_group(rg_ctx *c, const char *const *paths, size_t first, 
     return pcm_scan_group(g, "fingerprint", RG_FP_MAX_CHANNELS, out, add, finish);
 }
 
+// what follows the last group of rg_same_recording and of rg_same_recording_xrate: the pair list, the match kernel over the
+// `used` codes in c->d_fp_codes, the groups, the caller's pairs and its copy of the codes
+static int fp_match_call(rg_ctx *c, size_t n, const std::vector<uint32_t> &counts, const std::vector<uint32_t> &rates, const std::vector<uint64_t> &at,
+                         const rg_fingerprint_opts &o, size_t used, rg_fingerprint_pair *pairs, size_t max_pairs, size_t *n_pairs, uint32_t *codes_out,
+                         size_t codes_cap, std::vector<uint32_t> *groups, std::vector<uint32_t> *matches) {
+    hipStream_t s = c->file_stream();
+    groups->assign(n, 0);
+    matches->assign(n, 0);
+    std::vector<rg_fingerprint_pair_record> records(n * (n - 1) / 2 + 1);
+    std::vector<RgFpPair> compared;
+    rg_fp_pairs(n, counts.data(), rates.data(), at.data(), o, &compared, records.data());
+    const int mrc = rg_fprint_match_device(c, c->d_fp_codes.p, compared, o, records.data(), s);
+    if (mrc != RG_OK) return mrc;
+    *n_pairs = rg_fingerprint_groups(n, records.data(), groups->data(), matches->data());
+    size_t rec = 0, found = 0;
+    for (size_t i = 0; i < n; ++i)
+        for (size_t j = i + 1; j < n; ++j, ++rec) {
+            const rg_fingerprint_pair_record &r = records[rec];
+            if (!(r.flags & RG_FP_PAIR_MATCH)) continue;
+            if (found < max_pairs) pairs[found] = rg_fingerprint_pair{(uint32_t)i, (uint32_t)j, r.errors, r.bits, r.lag, r.flags};
+            ++found;
+        }
+    const size_t fit = std::min(used, codes_cap);
+    if (fit) {
+        RG_HIP(c, hipMemcpyAsync(codes_out, c->d_fp_codes.p, fit * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        RG_HIP(c, hipStreamSynchronize(s));
+    }
+    return RG_OK;
+}
+
 extern "C" int rg_same_recording(rg_ctx *c, const char *const *paths, size_t n, const rg_fingerprint_opts *opts, rg_fingerprint_result *out,
                                  rg_fingerprint_pair *pairs, size_t max_pairs, size_t *n_pairs, uint32_t *codes_out, size_t codes_cap) {
     if (!c || !n_pairs || (max_pairs && !pairs) || (codes_cap && !codes_out)) return RG_ERR_INVALID_ARG;
@@ -613,8 +644,7 @@ extern "C" int rg_same_recording(rg_ctx *c, const char *const *paths, size_t n, 
     char err[256] = "";
     (void)rg_fp_options(opts, &o, err, sizeof err);  // (the call above has checked them)
     return no_throw(c, [&]() -> int {
-        hipStream_t s = c->file_stream();
-        std::vector<uint32_t> counts(n), rates(n), groups(n), matches(n);
+        std::vector<uint32_t> counts(n), rates(n);
         std::vector<uint64_t> at(n);
         for (size_t i = 0; i < n; ++i) {  // a failing file has no codes and takes part in no pair
             const bool ok = out[i].status == RG_OK;
@@ -622,25 +652,79 @@ extern "C" int rg_same_recording(rg_ctx *c, const char *const *paths, size_t n, 
             rates[i] = ok ? out[i].sample_rate : 0u;
             at[i] = ok ? out[i].codes_at : 0u;
         }
-        std::vector<rg_fingerprint_pair_record> records(n * (n - 1) / 2 + 1);
-        std::vector<RgFpPair> compared;
-        rg_fp_pairs(n, counts.data(), rates.data(), at.data(), o, &compared, records.data());
-        const int mrc = rg_fprint_match_device(c, c->d_fp_codes.p, compared, o, records.data(), s);
+        std::vector<uint32_t> groups, matches;
+        const int mrc = fp_match_call(c, n, counts, rates, at, o, call.used, pairs, max_pairs, n_pairs, codes_out, codes_cap, &groups, &matches);
         if (mrc != RG_OK) return mrc;
-        *n_pairs = rg_fingerprint_groups(n, records.data(), groups.data(), matches.data());
-        size_t rec = 0, found = 0;
-        for (size_t i = 0; i < n; ++i)
-            for (size_t j = i + 1; j < n; ++j, ++rec) {
-                const rg_fingerprint_pair_record &r = records[rec];
-                if (!(r.flags & RG_FP_PAIR_MATCH)) continue;
-                if (found < max_pairs) pairs[found] = rg_fingerprint_pair{(uint32_t)i, (uint32_t)j, r.errors, r.bits, r.lag, r.flags};
-                ++found;
-            }
-        const size_t fit = std::min(call.used, codes_cap);
-        if (fit) {
-            RG_HIP(c, hipMemcpyAsync(codes_out, c->d_fp_codes.p, fit * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            RG_HIP(c, hipStreamSynchronize(s));
+        for (size_t i = 0; i < n; ++i) {
+            if (out[i].status != RG_OK) continue;
+            out[i].group = groups[i];
+            out[i].matches = matches[i];
+            if (!codes_out || out[i].codes_at + out[i].codes > codes_cap) out[i].codes_at = UINT64_MAX;
         }
+        return RG_OK;
+    });
+}
+
+// ---- rg_same_recording_xrate: per group the resampler (rg_resample.hip) and the fingerprint kernels on its output, the match once
+// (include/mp3rgain_amd_resample.h).  The codes are kept as rg_same_recording keeps them; a group's resampled signals lie in
+// c->d_rs_y while its tiles run.
+static int xrate_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, FpCall *call, rg_xrate_result *out) {
+    FileGroup g(c, paths, first, n);
+    out += first;
+    std::vector<PcmRec> recs;  // plane: the track's place in `tracks`
+    std::vector<RgRsTrack> tracks(n + 1);
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        const int rc = rg_rs_track(i, g.descs[k], g.arena_bytes, &tracks[recs.size()], err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        recs.push_back(PcmRec{k, recs.size()});
+        return RG_OK;
+    };
+    const auto finish = [&]() -> int {
+        if (recs.empty()) return RG_OK;
+        std::vector<RgFpTrack> fp(recs.size() + 1);
+        uint64_t codes = 0;
+        for (size_t t = 0; t < recs.size(); ++t) {
+            rg_xr_fp_track(tracks[t], 0, &fp[t]);
+            codes += fp[t].frames ? fp[t].frames - 1u : 0u;
+        }
+        int rc = fp_codes_grow(c, call->used, call->used + (size_t)codes + 4, c->file_stream());
+        if (rc != RG_OK) return rc;
+        std::vector<uint32_t> nonfinite(recs.size());
+        rc = rg_xrate_device(c, c->d_arena.p, tracks.data(), fp.data(), recs.size(), call->used, c->d_fp_codes.p, nullptr, nonfinite.data(), c->file_stream());
+        if (rc != RG_OK) return rc;
+        call->used += (size_t)codes;
+        for (const PcmRec &r : recs)
+            rg_xr_fill(g.descs[r.k], tracks[r.plane], fp[r.plane], dropped_frames(g, r.k), nonfinite[r.plane], (uint32_t)(first + g.slot[r.k]), 0,
+                       &out[g.slot[r.k]]);
+        return RG_OK;
+    };
+    return pcm_scan_group(g, "fingerprint", RG_RS_MAX_CHANNELS, out, add, finish);
+}
+
+extern "C" int rg_same_recording_xrate(rg_ctx *c, const char *const *paths, size_t n, const rg_fingerprint_opts *opts, rg_xrate_result *out,
+                                       rg_fingerprint_pair *pairs, size_t max_pairs, size_t *n_pairs, uint32_t *codes_out, size_t codes_cap) {
+    if (!c || !n_pairs || (max_pairs && !pairs) || (codes_cap && !codes_out)) return RG_ERR_INVALID_ARG;
+    *n_pairs = 0;
+    if (n > 65535) return rg_set_err(c, RG_ERR_INVALID_ARG, "rg_same_recording_xrate: %zu files, at most 65535 in one call", n);
+    FpCall call;
+    rg_fingerprint_opts o;
+    int rc = pcm_scan_call(c, paths, n, opts, out, rg_xr_options,
+                           [&](size_t first, size_t cnt, const rg_fingerprint_opts &) { return xrate_group(c, paths, first, cnt, &call, out); });
+    if (rc != RG_OK || n == 0) return rc;
+    char err[256] = "";
+    (void)rg_xr_options(opts, &o, err, sizeof err);  // (the call above has checked them)
+    return no_throw(c, [&]() -> int {
+        std::vector<uint32_t> counts(n), rates(n);
+        std::vector<uint64_t> at(n);
+        for (size_t i = 0; i < n; ++i) {  // a failing file has no codes and takes part in no pair; every other is at 11025 Hz now
+            const bool ok = out[i].status == RG_OK;
+            counts[i] = ok ? out[i].codes : 0u;
+            rates[i] = ok && !(out[i].flags & RG_FP_RATE) ? RG_RS_RATE_OUT : 0u;
+            at[i] = ok ? out[i].codes_at : 0u;
+        }
+        std::vector<uint32_t> groups, matches;
+        const int mrc = fp_match_call(c, n, counts, rates, at, o, call.used, pairs, max_pairs, n_pairs, codes_out, codes_cap, &groups, &matches);
+        if (mrc != RG_OK) return mrc;
         for (size_t i = 0; i < n; ++i) {
             if (out[i].status != RG_OK) continue;
             out[i].group = groups[i];

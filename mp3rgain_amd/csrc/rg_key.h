@@ -195,4 +195,12 @@ struct rg_ctx;
 // nonfinite[i] <- track i; `s` has been synchronised on return
 int rg_key_device(rg_ctx *c, const unsigned char *d_arena, RgKeyTrack *tracks, size_t n, const rg_key_opts &o, bool want_bands, RgKeyFinish *finish,
                   uint32_t *nonfinite, hipStream_t s);
+// Stage 1a alone, for the rational resampler's L = 1 tracks (rg_resample.hip): `tracks` hold off0, off1, n, m, decim, format,
+// channels, n_wg and recip; they are planned here (first_wg, taps_at), with y_at[i] where track i's y goes.  prepare: the job,
+// uploaded to c->d_key, `s` synchronised (*job stays NULL when no track has an output); launch: the decimation kernel enqueued
+// on `s`, y to d_y; free: the job.
+struct RgKeyDecimJob;
+int rg_key_decimate_prepare(rg_ctx *c, RgKeyTrack *tracks, const uint64_t *y_at, size_t n, hipStream_t s, RgKeyDecimJob **job);
+int rg_key_decimate_launch(rg_ctx *c, const unsigned char *d_arena, const RgKeyDecimJob *job, float *d_y, hipStream_t s);
+void rg_key_decimate_free(RgKeyDecimJob *job);
 #endif

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <memory>
 #include <new>
 #include <thread>
 #include <vector>
@@ -328,6 +329,56 @@ int rg_key_device(rg_ctx *c, const unsigned char *d_arena, RgKeyTrack *tracks, s
     RG_HIP(c, hipStreamSynchronize(s));
     return RG_OK;
 }
+
+// ---- stage 1a alone: the L = 1 path of the rational resampler (rg_resample.hip) ------------------------------------------------
+struct RgKeyDecimJob : KeyJob {};
+
+int rg_key_decimate_prepare(rg_ctx *c, RgKeyTrack *tracks, const uint64_t *y_at, size_t n, hipStream_t s, RgKeyDecimJob **out) {
+    *out = nullptr;
+    std::unique_ptr<RgKeyDecimJob> owner(new RgKeyDecimJob);
+    RgKeyDecimJob &job = *owner;
+    std::vector<float> taps;
+    std::vector<uint64_t> first;
+    std::vector<uint32_t> run;
+    (void)rg_key_plan(tracks, n, job.fmt_wg, &taps, &job.rows);
+    job.max_decim = 1;
+    for (size_t i = 0; i < n; ++i) {
+        tracks[i].y_at = y_at[i];
+        job.max_decim = std::max(job.max_decim, tracks[i].decim);
+    }
+    for (uint32_t f = 0; f < 3; ++f)  // the runs in the order of their workgroups
+        for (size_t i = 0; i < n; ++i)
+            if (tracks[i].format == f && tracks[i].n_wg) {
+                first.push_back(tracks[i].first_wg);
+                run.push_back((uint32_t)i);
+            }
+    if (n > 0x7fffffffu || job.fmt_wg[3] > 0x7fffffffu)
+        return rg_set_err(c, RG_ERR_INVALID_ARG, "too much for one call: %zu tracks, %llu decimation workgroups", n, (unsigned long long)job.fmt_wg[3]);
+    if (run.empty()) return RG_OK;  // nothing to launch: *out stays NULL
+    job.n = n;
+    job.n_runs = run.size();
+    job.tracks_at = 0;
+    job.first_at = fp_a16(n * sizeof(RgKeyTrack));
+    job.run_at = fp_a16(job.first_at + first.size() * sizeof(uint64_t));
+    job.taps_at = fp_a16(job.run_at + run.size() * sizeof(uint32_t));
+    job.end = fp_a16(job.taps_at + taps.size() * sizeof(float));
+    job.head.assign(job.end, 0);
+    memcpy(job.head.data(), tracks, n * sizeof(RgKeyTrack));
+    memcpy(job.head.data() + job.first_at, first.data(), first.size() * sizeof(uint64_t));
+    memcpy(job.head.data() + job.run_at, run.data(), run.size() * sizeof(uint32_t));
+    if (!taps.empty()) memcpy(job.head.data() + job.taps_at, taps.data(), taps.size() * sizeof(float));
+    RG_HIP(c, c->d_key.reserve(job.end));
+    RG_HIP(c, hipMemcpyAsync(c->d_key.p, job.head.data(), job.head.size(), hipMemcpyHostToDevice, s));
+    RG_HIP(c, hipStreamSynchronize(s));
+    *out = owner.release();
+    return RG_OK;
+}
+
+int rg_key_decimate_launch(rg_ctx *c, const unsigned char *d_arena, const RgKeyDecimJob *job, float *d_y, hipStream_t s) {
+    return job ? key_launch_decim(c, d_arena, c->d_key.p, *job, d_y, s) : RG_OK;
+}
+
+void rg_key_decimate_free(RgKeyDecimJob *job) { delete job; }
 
 // ---- test seams (include/mp3rgain_amd_key.h) ---------------------------------------------------------------------------------
 extern "C" int rg_key_arena(void *ctx, int route, size_t n, const rg_track_desc *descs, const void *arena, size_t arena_bytes, const rg_key_opts *opts,

@@ -592,6 +592,89 @@ def fingerprint_from_record(r, error=None) -> Fingerprint:
                        int(r.codes), int(r.nonfinite_frames), int(r.group), int(r.matches), error)
 
 
+def resample_plan(sample_rate: int):
+    """rg_resample_plan -> (L, M, P, whether the rate is supported)."""
+    v = [C.c_uint32() for _ in range(3)]
+    rc = _capi.load().rg_resample_plan(int(sample_rate), *[C.byref(x) for x in v])
+    if rc not in (0, _capi.RG_ERR_UNSUPPORTED_RATE):
+        raise ReplayGainError(rc, f"rg_resample_plan: rate {sample_rate}")
+    return v[0].value, v[1].value, v[2].value, rc == 0
+
+
+def resample_filter(up: int, down: int):
+    """rg_resample_filter -> the tap table of (L, M) as a float32 array [L][P]."""
+    half = 8 * max(int(up), int(down))
+    taps = 1 if (up == 1 and down == 1) or up < 1 else 2 * half // int(up) + 1
+    h = np.zeros((max(1, int(up)), taps), dtype=np.float32)
+    rc = _capi.load().rg_resample_filter(int(up), int(down), h.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise ReplayGainError(rc, f"rg_resample_filter: ({up}, {down})")
+    return h
+
+
+def resample_window(sample_rate: int, j: int):
+    """rg_resample_window -> (b_j, p_j)."""
+    b, p = C.c_uint64(), C.c_uint32()
+    rc = _capi.load().rg_resample_window(int(sample_rate), int(j), C.byref(b), C.byref(p))
+    if rc != 0:
+        raise ReplayGainError(rc, f"rg_resample_window: rate {sample_rate}, output {j}")
+    return b.value, p.value
+
+
+def resample_count(sample_rate: int, frames: int) -> int:
+    """M_out of a track of `frames` PCM frames (0 at an unsupported rate), in Python integers."""
+    up, down, taps, ok = resample_plan(sample_rate)
+    return (int(frames) - taps) * up // down + 1 if ok and frames >= taps else 0
+
+
+def resample_arena(ctx, route: int, descs, arena):
+    """rg_resample_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> ([ResampleRecord], y): y a
+    float32 array of every track's resampled signal in track order (record.y_at, record.resampled)."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    out = (_capi.ResampleRecord * max(1, n))()
+    y = np.zeros(max(1, sum(resample_count(int(t.sample_rate), int(t.frames)) for t in descs if t.sample_rate)), dtype=np.float32)
+    rc = L.rg_resample_arena(ctx, int(route), n, d, arena.ctypes.data if arena.size else None, arena.size, out, y.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    recs = list(out[:n])
+    return recs, y[:sum(int(r.resampled) for r in recs)]
+
+
+def xrate_fingerprint_arena(ctx, route: int, descs, arena, bands=True):
+    """rg_xrate_fingerprint_arena without an Analyzer -> ([XrateRecord], codes, bands, y), as fingerprint_arena gives them for
+    the tracks' signals at 11025 Hz, and y as resample_arena's."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    out = (_capi.XrateRecord * max(1, n))()
+    counts = [resample_count(int(t.sample_rate), int(t.frames)) if t.sample_rate else 0 for t in descs]
+    y = np.zeros(max(1, sum(counts)), dtype=np.float32)
+    most = sum(fingerprint_codes(m) + 1 for m in counts)
+    codes = np.zeros(max(1, most), dtype=np.uint32)
+    e = np.zeros((max(1, most), _capi.FP_BANDS), dtype=np.float32) if bands else None
+    rc = L.rg_xrate_fingerprint_arena(ctx, int(route), n, d, arena.ctypes.data if arena.size else None, arena.size, out,
+                                      codes.ctypes.data_as(C.POINTER(C.c_uint32)), e.ctypes.data_as(C.POINTER(C.c_float)) if bands else None,
+                                      y.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    recs = list(out[:n])
+    return (recs, codes[:sum(int(r.codes) for r in recs)], (e[:sum(int(r.fp_frames) for r in recs)] if bands else None),
+            y[:sum(int(r.resampled) for r in recs)])
+
+
+def resample_kernel_shape():
+    """rg_resample_kernel_shape -> (outputs, lanes, max_span)."""
+    v = [C.c_uint32() for _ in range(3)]
+    rc = _capi.load().rg_resample_kernel_shape(*[C.byref(x) for x in v])
+    if rc != 0:
+        raise ReplayGainError(rc, "rg_resample_kernel_shape")
+    return tuple(x.value for x in v)
+
+
 def _tempo_opts(window, hop, min_bpm):
     """rg_tempo_opts, or NULL (the header's defaults) when all are None; a None field is its default."""
     if window is None and hop is None and min_bpm is None:
@@ -1996,6 +2079,47 @@ class Analyzer:
         for byte."""
         out, pairs, n_pairs, codes = self._same_recording_call(files, block, probes, radius, max_ber_permille, codes_cap)
         return (bytes(out)[:len(files) * C.sizeof(_capi.FingerprintRecord)], bytes(pairs)[:n_pairs * C.sizeof(_capi.FingerprintPair)], codes)
+
+    def _same_recording_any_rate_call(self, files, block, probes, radius, max_ber_permille, codes_cap):
+        paths, out = self._file_args(files, _capi.XrateRecord)
+        n = len(files)
+        max_pairs = n * (n - 1) // 2
+        pairs = (_capi.FingerprintPair * max(1, max_pairs))()
+        n_pairs = C.c_size_t(0)
+        codes = np.zeros(max(1, int(codes_cap)), dtype=np.uint32) if codes_cap else None
+        self._check(self._lib.rg_same_recording_xrate(self._ctx, paths, n, _fingerprint_opts(block, probes, radius, max_ber_permille), out, pairs,
+                                                      max_pairs, C.byref(n_pairs), codes.ctypes.data_as(C.POINTER(C.c_uint32)) if codes_cap else None,
+                                                      int(codes_cap) if codes_cap else 0))
+        return out, pairs, int(n_pairs.value), codes
+
+    def same_recording_any_rate(self, files, block=None, probes=None, radius=None, max_ber_permille=None):
+        """rg_same_recording_xrate: same_recording across sample rates.  Every file is brought to 11025 Hz on this GPU first (a
+        rational polyphase resampler), fingerprinted there and matched with every other, whatever its own rate ->
+        ([Fingerprint], [SamePair], groups) as same_recording gives them; `sample_rate` is the file's own, a code and a lag
+        count 512 / 11025 s for every file, and None means this call's defaults (block 64, probes 8, radius 128)."""
+        out, pairs, n_pairs, _ = self._same_recording_any_rate_call(files, block, probes, radius, max_ber_permille, 0)
+        recs = [fingerprint_from_record(r, err) for r, err in self._file_records(out, len(files))]
+        found = [SamePair(int(p.i), int(p.j), int(p.errors), int(p.bits), int(p.lag), int(p.flags)) for p in pairs[:n_pairs]]
+        by = {}
+        for i, r in enumerate(recs):
+            if r.error is None:
+                by.setdefault(r.group, []).append(i)
+        return recs, found, [g for _, g in sorted(by.items()) if len(g) > 1]
+
+    def same_recording_any_rate_raw(self, files, block=None, probes=None, radius=None, max_ber_permille=None, codes_cap=0):
+        """same_recording_any_rate's arrays as the C call left them -> (record bytes, [XrateRecord], pair bytes, codes or None)."""
+        out, pairs, n_pairs, codes = self._same_recording_any_rate_call(files, block, probes, radius, max_ber_permille, codes_cap)
+        return (bytes(out)[:len(files) * C.sizeof(_capi.XrateRecord)], list(out[:len(files)]), bytes(pairs)[:n_pairs * C.sizeof(_capi.FingerprintPair)],
+                codes)
+
+    def resample_arena(self, route: int, descs, arena):
+        """rg_resample_arena, the seam of the resampler -> ([ResampleRecord], y); route 0 = the definitions in double, route 1 =
+        the arena copied to this GPU and the kernels, route 2 = the kernels' arithmetic on the host."""
+        return resample_arena(self._ctx, route, descs, arena)
+
+    def xrate_fingerprint_arena(self, route: int, descs, arena, bands=True):
+        """rg_xrate_fingerprint_arena, the resampler and the fingerprint kernels on its output -> ([XrateRecord], codes, bands, y)."""
+        return xrate_fingerprint_arena(self._ctx, route, descs, arena, bands)
 
     def fingerprint_arena(self, route: int, descs, arena, bands=True):
         """rg_fingerprint_arena, the seam of the fingerprint kernels -> ([FingerprintRecord], codes, bands); route 0 = the
