@@ -549,6 +549,102 @@ pub mod replaygain {
     }
 }
 
+/// The stereo image scan of `include/mp3rgain_amd_stereo.h`: how do channels 0 and 1 of each of these WAV, FLAC or MP3 files relate?
+/// The exact moments of the two channels per block, how many frames are equal, opposite or zero, and the cross-correlation of the
+/// channels at every lag within a radius, all on the GPU and all integer in front of the finish: dual mono, an inverted copy, a
+/// lopsided or nearly mono image, a channel delayed by a few samples.  The definitions are a convention of that header, tried on
+/// synthetic material only and held to no other tool; `delay_permille` and `phase_permille` are measured on synthetic
+/// material (`tests/golden/stereo_measured.json`).  A module of its own, as [`dr`] is.  `tests/test_rust_stereo_layout.py` compares these declarations with the header.
+pub mod stereo {
+    use super::ffi::RgCtx;
+    use std::os::raw::{c_char, c_int};
+
+    pub const ST_COMPLETE: u32 = 1;
+    pub const ST_SILENT: u32 = 2;
+    pub const ST_NONFINITE: u32 = 4;
+    pub const ST_DUAL_MONO: u32 = 8;
+    pub const ST_INVERTED_COPY: u32 = 16;
+    pub const ST_OUT_OF_PHASE: u32 = 32;
+    pub const ST_NEAR_MONO: u32 = 64;
+    pub const ST_ONE_SIDED: u32 = 128;
+    pub const ST_DELAYED: u32 = 256;
+    pub const ST_MONO: u32 = 512;
+    pub const ST_MORE_CHANNELS: u32 = 1024;
+    pub const ST_MAX_CHANNELS: usize = 8;
+    pub const ST_MAX_RADIUS: u32 = 255;
+    pub const ST_MAX_BLOCK_FRAMES: u32 = 384000;
+    pub const ST_DEFAULT_RADIUS: u32 = 64;
+    pub const ST_DEFAULT_PHASE_PERMILLE: u32 = 587;
+    pub const ST_DEFAULT_DELAY_PERMILLE: u32 = 420;
+    pub const ST_DEFAULT_MONO_DB: u32 = 40;
+    pub const ST_DEFAULT_BALANCE_DB: u32 = 12;
+
+    #[derive(Clone, Copy, Debug)]
+    #[repr(C)]
+    /// `rg_stereo_opts`: `block_frames` 0 = the sample rate; every other field is taken as it stands; a null pointer means the defaults
+    pub struct RgStereoOpts {
+        pub block_frames: u32,
+        pub radius: u32,
+        pub phase_permille: u32,
+        pub delay_permille: u32,
+        pub mono_db: u32,
+        pub balance_db_limit: u32,
+    }
+
+    impl Default for RgStereoOpts {
+        fn default() -> Self {
+            RgStereoOpts {
+                block_frames: 0,
+                radius: ST_DEFAULT_RADIUS,
+                phase_permille: ST_DEFAULT_PHASE_PERMILLE,
+                delay_permille: ST_DEFAULT_DELAY_PERMILLE,
+                mono_db: ST_DEFAULT_MONO_DB,
+                balance_db_limit: ST_DEFAULT_BALANCE_DB,
+            }
+        }
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_stereo_result`: a positive `lag` means the right channel is late; `balance_db` and `side_db` may be infinite
+    pub struct RgStereoResult {
+        pub status: i32,
+        pub flags: u32,
+        pub frames: u64,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub format: u32,
+        pub dropped_frames: u32,
+        pub block_frames: u32,
+        pub radius: u32,
+        pub blocks: u32,
+        pub active_blocks: u32,
+        pub neg_blocks: u32,
+        pub mono_blocks: u32,
+        pub lag: i32,
+        pub anti_lag: i32,
+        pub equal_frames: u64,
+        pub opposite_frames: u64,
+        pub zero_frames: u64,
+        pub nonfinite: u64,
+        pub ell: i64,
+        pub err: i64,
+        pub elr: i64,
+        pub lag_sum: i64,
+        pub anti_sum: i64,
+        pub correlation: f64,
+        pub lag_correlation: f64,
+        pub anti_correlation: f64,
+        pub balance_db: f64,
+        pub side_db: f64,
+    }
+
+    extern "C" {
+        pub fn rg_stereo(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, opts: *const RgStereoOpts, out: *mut RgStereoResult,
+                         lag_sums: *mut i64) -> c_int;
+    }
+}
+
 /// Duplicates across sample rates (`include/mp3rgain_amd_resample.h`): is this 96 kHz download that CD track?  Every file is brought
 /// to 11025 Hz by a rational polyphase resampler on the GPU, fingerprinted there by stage 1 of [`fingerprint`] and matched by its
 /// stage 2, whatever the file's own rate.  The options and the pairs are [`fingerprint`]'s; a zero option means this call's default.

@@ -423,6 +423,59 @@ DR_SYMBOLS = [
     ("rg_dr_rate", _int, [_vp, _sz, _u64, _u32, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz), _P(_u64)]),
 ]
 
+# include/mp3rgain_amd_stereo.h (stereo image: moments of channels 0 and 1, raw comparisons, cross-correlation at every lag)
+(ST_COMPLETE, ST_SILENT, ST_NONFINITE, ST_DUAL_MONO, ST_INVERTED_COPY, ST_OUT_OF_PHASE, ST_NEAR_MONO, ST_ONE_SIDED, ST_DELAYED, ST_MONO,
+ ST_MORE_CHANNELS) = (1 << k for k in range(11))
+ST_MAX_CHANNELS, ST_MAX_RADIUS, ST_MAX_BLOCK_FRAMES = 8, 255, 384000
+ST_DEFAULT_RADIUS, ST_DEFAULT_PHASE_PERMILLE, ST_DEFAULT_DELAY_PERMILLE, ST_DEFAULT_MONO_DB, ST_DEFAULT_BALANCE_DB = 64, 587, 420, 40, 12
+
+
+class StereoOpts(C.Structure):  # rg_stereo_opts
+    _fields_ = [("block_frames", C.c_uint32), ("radius", C.c_uint32), ("phase_permille", C.c_uint32), ("delay_permille", C.c_uint32),
+                ("mono_db", C.c_uint32), ("balance_db_limit", C.c_uint32)]
+
+
+class StereoRecord(C.Structure):  # rg_stereo_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("block_frames", C.c_uint32),
+        ("radius", C.c_uint32),
+        ("blocks", C.c_uint32),
+        ("active_blocks", C.c_uint32),
+        ("neg_blocks", C.c_uint32),
+        ("mono_blocks", C.c_uint32),
+        ("lag", C.c_int32),
+        ("anti_lag", C.c_int32),
+        ("equal_frames", C.c_uint64),
+        ("opposite_frames", C.c_uint64),
+        ("zero_frames", C.c_uint64),
+        ("nonfinite", C.c_uint64),
+        ("ell", C.c_int64),
+        ("err", C.c_int64),
+        ("elr", C.c_int64),
+        ("lag_sum", C.c_int64),
+        ("anti_sum", C.c_int64),
+        ("correlation", C.c_double),
+        ("lag_correlation", C.c_double),
+        ("anti_correlation", C.c_double),
+        ("balance_db", C.c_double),
+        ("side_db", C.c_double),
+    ]
+
+
+STEREO_SYMBOLS = [
+    ("rg_stereo", _int, [_vp, _P(C.c_char_p), _sz, _P(StereoOpts), _P(StereoRecord), _P(C.c_int64)]),
+    ("rg_stereo_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _P(StereoOpts), _vp, _sz, _P(StereoRecord), _P(C.c_int64)]),
+    ("rg_stereo_kernel_shape", _int, [_u32, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_stereo_rate", _int, [_vp, _sz, _u64, _u32, _u32, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz), _P(_u64), _P(_u64)]),
+]
+
 # include/mp3rgain_amd_ancestry.h (lossy ancestry: an MP3 granule grid in PCM)
 ANC_COMPLETE, ANC_MP3_GRID, ANC_MIDSIDE, ANC_NONFINITE, ANC_SHORT, ANC_SILENT = 1, 2, 4, 8, 16, 32
 ANC_MAX_CHANNELS, ANC_MAX_VIEWS, ANC_ALIGNMENTS, ANC_VIEW_MID, ANC_VIEW_SIDE, ANC_NO_VIEW = 8, 10, 576, 8, 9, 0xFFFFFFFF
@@ -708,7 +761,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS + RESAMPLE_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + STEREO_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS + RESAMPLE_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

@@ -87,6 +87,8 @@ class Options:  # src/main.rs:65-96
     tempo_min: Optional[int] = None  # with --tempo (--tempo-min BPM): the reading lies in [BPM, 2 BPM)
     key: bool = False  # this façade only (--key): in which musical key is each file?  One of 12 major and 12 minor keys
     key_segment: Optional[int] = None  # with --key (--key-segment ROWS): the rows of a segment of the steadiness figure
+    stereo: bool = False  # this façade only (--stereo): how do the two channels of each file relate?  Dual mono, inverted, delayed, ...
+    stereo_radius: Optional[int] = None  # with --stereo (--stereo-radius N): the largest channel delay looked for, in samples
     files: List[Path] = field(default_factory=list)
 
 
@@ -201,6 +203,10 @@ def parse_args(args: List[str], out, err) -> Options:
             o.key = True
         elif arg == "--key-segment":
             o.key_segment = _parse_int(need("--key-segment", "--key-segment requires an argument"), "invalid number of rows", 32, signed=False)
+        elif arg == "--stereo":  # not in the reference: a command of its own, like --dr
+            o.stereo = True
+        elif arg == "--stereo-radius":
+            o.stereo_radius = _parse_int(need("--stereo-radius", "--stereo-radius requires an argument"), "invalid radius", 32, signed=False)
         elif arg == "--decoder":  # not in the reference: see the module docstring
             o.decoder = need("--decoder", "--decoder requires an argument")
         elif arg.startswith("-") and len(arg) > 1 and not arg.startswith("--"):
@@ -378,7 +384,48 @@ def parse_args(args: List[str], out, err) -> Options:
                                         ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
         if others:
             raise CliError(f"--key is a command of its own and cannot be combined with {', '.join(others)}")
+    if o.stereo_radius is not None and not o.stereo:
+        raise CliError("--stereo-radius requires --stereo")
+    if o.stereo_radius is not None and not 0 <= o.stereo_radius <= _capi.ST_MAX_RADIUS:
+        raise CliError(f"--stereo-radius takes 0 to {_capi.ST_MAX_RADIUS} samples: {o.stereo_radius}")
+    if o.stereo:
+        others = [name for name, on in (("--verify", o.verify), ("--rip", o.rip), ("--stats", o.stats), ("--spectrum", o.spectrum), ("--dr", o.dr),
+                                        ("--ancestry", o.ancestry), ("--duplicates", o.duplicates), ("--tempo", o.tempo), ("--key", o.key),
+                                        ("--r128", o.r128), ("-x", o.max_amplitude_only), ("-r", o.track_gain), ("-a", o.album_gain), ("-u", o.undo),
+                                        ("-g", o.gain_steps is not None), ("-l", o.channel_gain is not None),
+                                        ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
+        if others:
+            raise CliError(f"--stereo is a command of its own and cannot be combined with {', '.join(others)}")
     return o
+
+
+def _signed_db(x: float) -> str:
+    return f"{x:+.1f} dB" if math.isfinite(x) else ("+inf dB" if x > 0 else "-inf dB")
+
+
+def stereo_line(r) -> str:
+    """A file's reading as the text output has it (without the name): the first verdict that names what the file is, then the
+    figures."""
+    v = r.verdicts
+    if "mono file" in v:
+        return "mono file"
+    if "silent" in v:
+        return "silent"
+    if "dual mono" in v:
+        return "dual mono"
+    if "inverted copy" in v:
+        return "right channel is the inverted left"
+    figures = f"correlation {r.correlation:.2f}, side {_signed_db(r.side_db)}, balance {_signed_db(r.balance_db)}"
+    if "delayed" in v:
+        who = "right" if r.lag > 0 else "left"
+        return f"{who} channel late by {abs(r.lag)} sample{'s' if abs(r.lag) != 1 else ''} (correlation {r.lag_correlation:.3f} there, {r.correlation:.2f} in place)"
+    if "out of phase" in v:
+        return f"channels out of phase  ({figures})"
+    if "one-sided" in v:
+        return f"one-sided  ({figures})"
+    if "near mono" in v:
+        return f"near mono  ({figures})"
+    return f"stereo  ({figures})"
 
 
 def key_line(r) -> str:
@@ -642,6 +689,8 @@ class Cli:
             return self.cmd_tempo()
         if o.key:
             return self.cmd_key()
+        if o.stereo:
+            return self.cmd_stereo()
         if o.max_amplitude_only:
             return self.cmd_max_amplitude()
         if o.stored_tag_mode == "delete":
@@ -1265,6 +1314,65 @@ class Cli:
                 continue
             notes = [v for v in r.verdicts if v not in ("ok", "none")] + ([f"{r.dropped_frames} frames dropped"] if r.dropped_frames else [])
             self.p(f"{key_line(r)}  {_name(file)}" + (f"  [{', '.join(notes)}]" if notes else ""))
+        return 1 if failed else 0
+
+    # ---- --stereo (not in the reference): how do the two channels of each file relate?  On the GPU ----------------------------
+    def cmd_stereo(self) -> int:
+        """Every file decoded by the route the analysis uses; the moments of channels 0 and 1, the raw comparisons and the
+        cross-correlation at every lag within the radius on the first GPU (rg_stereo).  Text: a line per file, `stereo
+        (correlation 0.62, side -7.1 dB, balance +0.3 dB)  name`, `dual mono  name`, `right channel late by 3 samples (correlation
+        0.998 there, 0.41 in place)  name`, `channels out of phase  (...)  name`, `mono file  name`, with the other verdicts in
+        brackets.  The definitions are a convention of this project, tried on synthetic material only.  A report: exit status 1
+        only when a file fails or has dropped frames.  TSV, no header: a row per file `file, verdicts, correlation, side dB,
+        balance dB, lag, lag correlation, anti lag, anti correlation, frames, sample rate, channels, radius, dropped frames` (a
+        failing file: `file, error text`)."""
+        o = self.o
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            recs = an.stereo(o.files, radius=o.stereo_radius)
+        failed = sum(1 for r in recs if r.error is not None or not r.complete)
+        num = lambda x: x if math.isfinite(x) else None  # noqa: E731  (JSON has no infinity)
+        if o.output_format == "json":
+            files = []
+            for file, r in zip(o.files, recs):
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                else:
+                    d.update(verdicts=r.verdicts, reading=stereo_line(r), correlation=r.correlation, lag_correlation=r.lag_correlation,
+                             anti_correlation=r.anti_correlation, balance_db=num(r.balance_db), side_db=num(r.side_db),
+                             balance=("left" if r.balance_db > 0 else "right") if math.isinf(r.balance_db) else None,
+                             side=("all" if r.side_db > 0 else "none") if math.isinf(r.side_db) else None, lag=r.lag, anti_lag=r.anti_lag,
+                             lag_sum=r.lag_sum, anti_sum=r.anti_sum, ell=r.ell, err=r.err, elr=r.elr, equal_frames=r.equal_frames,
+                             opposite_frames=r.opposite_frames, zero_frames=r.zero_frames, nonfinite=r.nonfinite, blocks=r.blocks,
+                             active_blocks=r.active_blocks, neg_blocks=r.neg_blocks, mono_blocks=r.mono_blocks, block_frames=r.block_frames,
+                             radius=r.radius, frames=r.frames, sample_rate=r.sample_rate, channels=r.channels, format=r.format, flags=r.flags,
+                             dropped_frames=r.dropped_frames, complete=r.complete)
+                files.append(d)
+            _print_json(self.out, files=files, summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+            return 1 if failed else 0
+        if o.output_format == "tsv":
+            for file, r in zip(o.files, recs):
+                if r.error is not None:
+                    self.p(f"{_name(file)}\t{r.error}")
+                    continue
+                self.p(f"{_name(file)}\t{','.join(r.verdicts)}\t{r.correlation:.4f}\t{r.side_db:.2f}\t{r.balance_db:.2f}\t{r.lag}\t{r.lag_correlation:.4f}\t"
+                       f"{r.anti_lag}\t{r.anti_correlation:.4f}\t{r.frames}\t{r.sample_rate}\t{r.channels}\t{r.radius}\t{r.dropped_frames}")
+            return 1 if failed else 0
+        if self.talk:
+            self.p(f"mp3rgain stereo image of {len(o.files)} file(s): correlation, balance and channel delay within "
+                   f"{_capi.ST_DEFAULT_RADIUS if o.stereo_radius is None else o.stereo_radius} samples"
+                   " (a convention of this project, tried on synthetic material only)")
+            self.p()
+        named = ("stereo", "mono file", "silent", "dual mono", "inverted copy", "delayed", "out of phase", "one-sided", "near mono")
+        for file, r in zip(o.files, recs):
+            if r.error is not None:
+                self.e(f"{_name(file)} - {r.error}")
+                continue
+            line = stereo_line(r)
+            shown = next((w for w in named[1:] if w in r.verdicts), "stereo")
+            notes = [w for w in r.verdicts if w not in ("stereo", "incomplete", shown)] + ([f"{r.dropped_frames} frames dropped"] if r.dropped_frames else [])
+            self.p(f"{line}  {_name(file)}" + (f"  [{', '.join(notes)}]" if notes else ""))
         return 1 if failed else 0
 
     # ---- find_max_amplitude, src/lib.rs:1174-1199 ------------------------------------------------------------
@@ -1964,6 +2072,14 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "            other key finder.  JSON: files[key, camelot, open_key, correlation, margin, steady, verdicts, ...].  Exit status 1",
         "            only for a file that fails or has dropped frames",
         "--key-segment <rows>  With --key: the rows of a segment of `steady` (default 128, about 12 s; 8 to 4096)",
+        "--stereo    How do the two channels of each file relate?  On the GPU (WAV, FLAC, MP3): the exact moments of channels 0 and 1,",
+        "            how many frames are equal, opposite or zero, and the cross-correlation of the channels at every delay within the",
+        "            radius.  A line per file: `stereo  (correlation 0.62, side -7.1 dB, balance +0.3 dB)  name`, `dual mono`, `right",
+        "            channel is the inverted left`, `right channel late by 3 samples (correlation 0.998 there, 0.41 in place)`,",
+        "            `channels out of phase`, `one-sided`, `near mono`, `mono file`.  A convention of this project, tried on synthetic",
+        "            material only and held to no other tool.  JSON carries every field of the record.  Exit status 1 only for a file",
+        "            that fails or has dropped frames",
+        "--stereo-radius <N>  With --stereo: the largest delay looked for, in samples (default 64; 0 to 255)",
         "-v          Show version",
         "-h          Show this help",
     ):

@@ -196,6 +196,7 @@ struct rg_ctx {
     DevBuf<unsigned char> d_stats;           // rg_stats.hip: [plane records | tile -> plane | tile records | per-plane results] of one launch
     DevBuf<unsigned char> d_spectrum;        // rg_spectrum.hip: [tables | per run plane records, tile -> plane | tile records | skipped | per-plane results]
     DevBuf<unsigned char> d_dr;              // rg_dr.hip: [plane records | piece -> plane | piece records | block records | per-plane results] of one launch
+    DevBuf<unsigned char> d_stereo;          // rg_stereo.hip: [track records | piece -> track | tile -> track | piece records | lag sums | per-track results] of one launch
     DevBuf<unsigned char> d_ancestry;        // rg_ancestry.hip: [tables | view records | tile records | counts | nonfinite] of one launch
     DevBuf<unsigned char> d_fprint;          // rg_fprint.hip: [tables | track records | tile -> track | tile counts | track counts] of one launch; rg_fprint_match.hip: [pairs | records]
     DevBuf<uint32_t> d_fp_codes;             // the fingerprint codes of one rg_same_recording call, kept from group to group

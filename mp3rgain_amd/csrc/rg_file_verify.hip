@@ -3,7 +3,7 @@
 // (include/mp3rgain_amd_rip.h), and the four PCM scans, which share one group driver (pcm_scan_group): rg_pcm_stats
 // (include/mp3rgain_amd_stats.h), rg_dynamic_range (include/mp3rgain_amd_dr.h), rg_ancestry (include/mp3rgain_amd_ancestry.h),
 // rg_spectrum (include/mp3rgain_amd_spectrum.h), rg_same_recording (include/mp3rgain_amd_fingerprint.h), rg_tempo
-// (include/mp3rgain_amd_tempo.h) and rg_key (include/mp3rgain_amd_key.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
+// (include/mp3rgain_amd_tempo.h), rg_key (include/mp3rgain_amd_key.h) and rg_stereo (include/mp3rgain_amd_stereo.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
 // command: what this library does not decode itself is not a stream it could vouch for.  A file's status lives in its record,
 // and the record of a file that failed holds nothing else.
 #include <algorithm>
@@ -20,6 +20,7 @@
 #include "rg_key.h"
 #include "rg_resample.h"
 #include "rg_stats.h"
+#include "rg_stereo.h"
 
 using namespace rgf;
 
@@ -469,6 +470,44 @@ static int dr_group(rg_ctx *c, const char *const *paths, size_t first, size_t n,
 
 extern "C" int rg_dynamic_range(rg_ctx *c, const char *const *paths, size_t n, const rg_dr_opts *opts, rg_dr_result *out) {
     return pcm_scan_call(c, paths, n, opts, out, rg_dr_options, [&](size_t first, size_t cnt, const rg_dr_opts &o) { return dr_group(c, paths, first, cnt, o, out); });
+}
+
+// ---- rg_stereo: the kernels of rg_stereo.hip; the finish is host arithmetic on what comes back (rg_st_fill) ------------------
+// The caller's lag sums are rows by file, so a group fills the rows of its own files.
+static int stereo_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_stereo_opts &o, rg_stereo_result *out, int64_t *lag_sums) {
+    FileGroup g(c, paths, first, n);
+    out += first;
+    const uint32_t W = 2u * o.radius + 1u;
+    std::vector<PcmRec> recs;  // plane: the track's place in `tracks`
+    std::vector<RgStTrack> tracks(n + 1);
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        const int rc = rg_st_track(i, g.descs[k], o, true, g.arena_bytes, &tracks[recs.size()], err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        recs.push_back(PcmRec{k, recs.size()});
+        return RG_OK;
+    };
+    const auto finish = [&]() -> int {
+        if (recs.empty()) return RG_OK;
+        std::vector<RgStTotals> tot(recs.size());
+        std::vector<int64_t> sums(lag_sums ? recs.size() * W : 0);
+        const int rc = rg_st_device(c, c->d_arena.p, tracks.data(), recs.size(), o.radius, tot.data(), lag_sums ? sums.data() : nullptr, c->file_stream());
+        if (rc != RG_OK) return rc;
+        for (const PcmRec &r : recs) {
+            rg_st_fill(g.descs[r.k], o, tracks[r.plane].block, dropped_frames(g, r.k), tot[r.plane], &out[g.slot[r.k]]);
+            if (lag_sums) memcpy(lag_sums + (first + g.slot[r.k]) * W, &sums[r.plane * W], W * sizeof(int64_t));
+        }
+        return RG_OK;
+    };
+    return pcm_scan_group(g, "stereo scan", RG_ST_MAX_CHANNELS, out, add, finish);
+}
+
+extern "C" int rg_stereo(rg_ctx *c, const char *const *paths, size_t n, const rg_stereo_opts *opts, rg_stereo_result *out, int64_t *lag_sums) {
+    rg_stereo_opts probe;
+    char err[8];
+    const size_t rows = rg_st_options(opts, &probe, err, sizeof err) == RG_OK ? n * (2u * probe.radius + 1u) * sizeof(int64_t) : 0;  // (pcm_scan_call reports a bad option)
+    return pcm_scan_call(
+        c, paths, n, opts, out, rg_st_options, [&](size_t first, size_t cnt, const rg_stereo_opts &o) { return stereo_group(c, paths, first, cnt, o, out, lag_sums); },
+        lag_sums, rows);
 }
 
 // ---- rg_ancestry: the kernels of rg_ancestry.hip; the verdict is host arithmetic on the counts that come back (rg_anc_fill) --

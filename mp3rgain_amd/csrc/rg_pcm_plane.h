@@ -1,5 +1,5 @@
 // rg_pcm_plane.h -- internal, header-only: what the scans that read planar PCM where it lies in an arena (rg_stats.h,
-// rg_spectrum.h, rg_dr.h, rg_ancestry.h) share on the host: what a sample format is, how a stored sample is read, the checks of
+// rg_spectrum.h, rg_dr.h, rg_stereo.h, rg_ancestry.h) share on the host: what a sample format is, how a stored sample is read, the checks of
 // a track descriptor against the scan's limits and against the arena, and the argument checks of a test seam's host routes.
 // Plain C++ that also compiles under hipcc; no device and no context, so a sanitizer build of one *_host.cpp needs nothing else.
 //

@@ -1,5 +1,5 @@
 // rg_pcm_seam.h -- internal, HIP only: what the test seams that take tracks in a host arena on three routes (rg_pcm_stats_arena,
-// rg_spectrum_arena, rg_dr_arena, rg_ancestry_arena, rg_rip_checksums_arena) have in common.  Route 0 and route 2 are the
+// rg_spectrum_arena, rg_dr_arena, rg_stereo_arena, rg_ancestry_arena, rg_rip_checksums_arena) have in common.  Route 0 and route 2 are the
 // scan's host routes and need no context; route 1 copies the arena to the device and runs the kernels there.
 #pragma once
 

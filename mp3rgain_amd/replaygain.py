@@ -439,6 +439,116 @@ def album_dr(records) -> Optional[int]:
     return int(round(sum(vals) / len(vals))) if vals else None
 
 
+def _stereo_opts(radius, block_frames, phase_permille, delay_permille, mono_db, balance_db_limit):
+    """rg_stereo_opts, or NULL (the header's defaults) when all are None; a None field is its default."""
+    if all(v is None for v in (radius, block_frames, phase_permille, delay_permille, mono_db, balance_db_limit)):
+        return None
+    pick = lambda v, d: d if v is None else int(v)  # noqa: E731
+    return C.byref(_capi.StereoOpts(pick(block_frames, 0), pick(radius, _capi.ST_DEFAULT_RADIUS), pick(phase_permille, _capi.ST_DEFAULT_PHASE_PERMILLE),
+                                    pick(delay_permille, _capi.ST_DEFAULT_DELAY_PERMILLE), pick(mono_db, _capi.ST_DEFAULT_MONO_DB),
+                                    pick(balance_db_limit, _capi.ST_DEFAULT_BALANCE_DB)))
+
+
+def _stereo_rows(n, radius, wanted):
+    """The caller's lag sums: (an int64 array of n rows of 2 * radius + 1, its pointer), or (None, NULL) when not wanted."""
+    if not wanted:
+        return None, None
+    r = _capi.ST_DEFAULT_RADIUS if radius is None else int(radius)
+    rows = np.zeros((max(1, n), 2 * max(0, r) + 1), dtype=np.int64)
+    return rows, rows.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def stereo_arena(ctx, route: int, descs, arena, radius=None, block_frames=None, phase_permille=None, delay_permille=None, mono_db=None,
+                 balance_db_limit=None, lag_sums=False):
+    """rg_stereo_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> [StereoRecord], or with
+    `lag_sums` ([StereoRecord], int64 array of one row of 2 * radius + 1 sums per track).  Options None = the header's defaults."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    out = (_capi.StereoRecord * max(1, n))()
+    rows, rows_p = _stereo_rows(n, radius, lag_sums)
+    rc = L.rg_stereo_arena(ctx, int(route), n, d, _stereo_opts(radius, block_frames, phase_permille, delay_permille, mono_db, balance_db_limit),
+                           arena.ctypes.data if arena.size else None, arena.size, out, rows_p)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return (list(out[:n]), rows[:n]) if lag_sums else list(out[:n])
+
+
+def stereo_kernel_shape(fmt: int):
+    """rg_stereo_kernel_shape of one rg_sample_format -> (piece_samples, tile_frames, strip_frames, lag_group, lds_bytes)."""
+    v = [C.c_uint32() for _ in range(5)]
+    rc = _capi.load().rg_stereo_kernel_shape(int(fmt), *[C.byref(x) for x in v])
+    if rc != 0:
+        raise ReplayGainError(rc, f"rg_stereo_kernel_shape: format {fmt}")
+    return tuple(x.value for x in v)
+
+
+_STEREO_FIELDS = ("frames", "sample_rate", "channels", "format", "dropped_frames", "block_frames", "radius", "flags", "blocks", "active_blocks",
+                  "neg_blocks", "mono_blocks", "lag", "anti_lag", "equal_frames", "opposite_frames", "zero_frames", "nonfinite", "ell", "err", "elr",
+                  "lag_sum", "anti_sum", "correlation", "lag_correlation", "anti_correlation", "balance_db", "side_db")
+
+
+@dataclass
+class StereoImage:
+    """One file of Analyzer.stereo (rg_stereo_result): how channels 0 and 1 relate.  The definitions are a convention of
+    include/mp3rgain_amd_stereo.h, tried on synthetic material only and held to no other tool."""
+    frames: int
+    sample_rate: int
+    channels: int
+    format: int              # rg_sample_format of the planes that were scanned
+    dropped_frames: int
+    block_frames: int
+    radius: int
+    flags: int
+    blocks: int
+    active_blocks: int
+    neg_blocks: int
+    mono_blocks: int
+    lag: int                 # the lag with the largest sum; positive = the right channel is late
+    anti_lag: int            # the lag with the smallest sum
+    equal_frames: int
+    opposite_frames: int
+    zero_frames: int
+    nonfinite: int
+    ell: int
+    err: int
+    elr: int
+    lag_sum: int
+    anti_sum: int
+    correlation: float
+    lag_correlation: float
+    anti_correlation: float
+    balance_db: float        # +inf: all left, -inf: all right
+    side_db: float           # -inf: no side signal, +inf: the mono sum cancels
+    error: Optional["ReplayGainError"] = None  # why there are no numbers; every other field is then zero
+
+    def _has(self, bit) -> bool:
+        return bool(self.flags & bit)
+
+    @property
+    def complete(self) -> bool:
+        return self._has(_capi.ST_COMPLETE)
+
+    @property
+    def verdicts(self) -> list:
+        """The flags as words, in a fixed order; ["stereo"] when there is nothing to report."""
+        names = (("mono file", _capi.ST_MONO), ("silent", _capi.ST_SILENT), ("dual mono", _capi.ST_DUAL_MONO),
+                 ("inverted copy", _capi.ST_INVERTED_COPY), ("out of phase", _capi.ST_OUT_OF_PHASE), ("near mono", _capi.ST_NEAR_MONO),
+                 ("one-sided", _capi.ST_ONE_SIDED), ("delayed", _capi.ST_DELAYED), ("nonfinite", _capi.ST_NONFINITE),
+                 ("more channels", _capi.ST_MORE_CHANNELS))
+        words = [n for n, bit in names if self._has(bit)]
+        if self.error is None and not self.complete:
+            words.append("incomplete")
+        return words or ["stereo"]
+
+
+def stereo_from_record(r, error=None) -> StereoImage:
+    """A StereoImage from an rg_stereo_result."""
+    return StereoImage(*[(float if f in ("correlation", "lag_correlation", "anti_correlation", "balance_db", "side_db") else int)(getattr(r, f))
+                         for f in _STEREO_FIELDS], error)
+
+
 def _fingerprint_opts(block, probes, radius, max_ber_permille):
     """rg_fingerprint_opts, or NULL (the header's defaults) when all are None; a None field is its default."""
     if block is None and probes is None and radius is None and max_ber_permille is None:
@@ -2046,6 +2156,41 @@ class Analyzer:
     @staticmethod
     def dr_kernel_shape(fmt: int):
         return dr_kernel_shape(fmt)
+
+    def _stereo_call(self, files, radius, block_frames, phase_permille, delay_permille, mono_db, balance_db_limit, lag_sums):
+        paths, out = self._file_args(files, _capi.StereoRecord)
+        rows, rows_p = _stereo_rows(len(files), radius, lag_sums)
+        opts = _stereo_opts(radius, block_frames, phase_permille, delay_permille, mono_db, balance_db_limit)
+        self._check(self._lib.rg_stereo(self._ctx, paths, len(files), opts, out, rows_p))
+        return out, rows
+
+    def stereo(self, files, radius=None, block_frames=None, phase_permille=None, delay_permille=None, mono_db=None, balance_db_limit=None,
+               lag_sums=False):
+        """rg_stereo: `files` (WAV, FLAC or MPEG Layer III) decoded by the route the analysis uses and, from the PCM where it
+        lies on this GPU, the moments of channels 0 and 1 per block, the raw comparisons and the cross-correlation at every lag
+        within `radius` -> [StereoImage], or with `lag_sums` ([StereoImage], int64 array of one row of 2 * radius + 1 sums per
+        file).  A file that takes no part carries its ReplayGainError in `.error`."""
+        out, rows = self._stereo_call(files, radius, block_frames, phase_permille, delay_permille, mono_db, balance_db_limit, lag_sums)
+        recs = [stereo_from_record(r, err) for r, err in self._file_records(out, len(files))]
+        return (recs, rows[:len(files)]) if lag_sums else recs
+
+    def stereo_raw(self, files, radius=None, block_frames=None, lag_sums=False):
+        """stereo's rg_stereo_result array as the C call left it, and with `lag_sums` the rows' bytes behind it (tests compare
+        routes byte for byte)."""
+        out, rows = self._stereo_call(files, radius, block_frames, None, None, None, None, lag_sums)
+        raw = bytes(out)[:len(files) * C.sizeof(_capi.StereoRecord)]
+        return (raw, rows[:len(files)].tobytes()) if lag_sums else raw
+
+    def stereo_arena(self, route: int, descs, arena, radius=None, block_frames=None, phase_permille=None, delay_permille=None, mono_db=None,
+                     balance_db_limit=None, lag_sums=False):
+        """rg_stereo_arena, the seam of the stereo kernels: the tracks `descs` describe in the host arena `arena` ->
+        [StereoRecord] (with `lag_sums`: and the rows); route 0 = the serial host twin, route 1 = the arena copied to this GPU and
+        the kernels, route 2 = the kernels' cutting and fold arithmetic on the host."""
+        return stereo_arena(self._ctx, route, descs, arena, radius, block_frames, phase_permille, delay_permille, mono_db, balance_db_limit, lag_sums)
+
+    @staticmethod
+    def stereo_kernel_shape(fmt: int):
+        return stereo_kernel_shape(fmt)
 
     def _same_recording_call(self, files, block, probes, radius, max_ber_permille, codes_cap):
         paths, out = self._file_args(files, _capi.FingerprintRecord)
