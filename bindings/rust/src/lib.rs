@@ -549,6 +549,73 @@ pub mod replaygain {
     }
 }
 
+/// The FLAC encoder of `include/mp3rgain_amd_flacenc.h`: WAV files with integer samples and FLAC files are decoded by the route the
+/// analysis uses and encoded where their PCM lies on the GPU -- an LPC search at every even order, every candidate's Rice coding
+/// sized exactly, mid/side for two channels -- and each stream is decoded again by the device decoder and its MD5 held to the
+/// source's before its file is written.  An output that exists is never replaced.  A module of its own, as [`stereo`] is.
+/// `tests/test_rust_flacenc_layout.py` compares these declarations with the header.
+pub mod flacenc {
+    use super::ffi::RgCtx;
+    use std::os::raw::{c_char, c_int};
+
+    pub const FLAC_ENC_DEFAULT_BLOCK: u32 = 4096;
+    pub const FLAC_ENC_DEFAULT_LPC: u32 = 8;
+    pub const FLAC_ENC_MAX_LPC: u32 = 12;
+    pub const FLAC_ENC_VERIFY: u32 = 1;
+    pub const FLAC_ENC_COMPLETE: u32 = 1;
+    pub const FLAC_ENC_VERIFIED: u32 = 2;
+    pub const FLAC_ENC_WRITTEN: u32 = 4;
+    pub const FLAC_ENC_VERIFY_FAILED: u32 = 8;
+
+    #[derive(Clone, Copy, Debug)]
+    #[repr(C)]
+    /// `rg_flac_encode_options`: `block_size` 0 = the default; a null pointer means block 4096, order 8, verified
+    pub struct RgFlacEncodeOptions {
+        pub struct_size: u32,
+        pub block_size: u32,
+        pub max_lpc_order: u32,
+        pub flags: u32,
+    }
+
+    impl Default for RgFlacEncodeOptions {
+        fn default() -> Self {
+            RgFlacEncodeOptions {
+                struct_size: std::mem::size_of::<RgFlacEncodeOptions>() as u32,
+                block_size: FLAC_ENC_DEFAULT_BLOCK,
+                max_lpc_order: FLAC_ENC_DEFAULT_LPC,
+                flags: FLAC_ENC_VERIFY,
+            }
+        }
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_flac_encode_result`: `md5_pcm` is what STREAMINFO carries, `md5_decoded` what the verified write's decode gave
+    pub struct RgFlacEncodeResult {
+        pub status: i32,
+        pub flags: u32,
+        pub pcm_frames: u64,
+        pub flac_frames: u32,
+        pub dropped_frames: u32,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub bits_per_sample: u32,
+        pub block_size: u32,
+        pub min_frame_bytes: u32,
+        pub max_frame_bytes: u32,
+        pub pcm_bytes: u64,
+        pub stream_bytes: u64,
+        pub metadata_bytes: u64,
+        pub md5_pcm: [u8; 16],
+        pub md5_decoded: [u8; 16],
+    }
+
+    extern "C" {
+        pub fn rg_flac_encode_files(ctx: *mut RgCtx, in_paths: *const *const c_char, out_paths: *const *const c_char, n: usize,
+                                    options: *const RgFlacEncodeOptions, results: *mut RgFlacEncodeResult) -> c_int;
+    }
+}
+
 /// The stereo image scan of `include/mp3rgain_amd_stereo.h`: how do channels 0 and 1 of each of these WAV, FLAC or MP3 files relate?
 /// The exact moments of the two channels per block, how many frames are equal, opposite or zero, and the cross-correlation of the
 /// channels at every lag within a radius, all on the GPU and all integer in front of the finish: dual mono, an inverted copy, a

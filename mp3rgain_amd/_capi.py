@@ -476,6 +476,43 @@ STEREO_SYMBOLS = [
     ("rg_stereo_rate", _int, [_vp, _sz, _u64, _u32, _u32, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz), _P(_u64), _P(_u64)]),
 ]
 
+# include/mp3rgain_amd_flacenc.h (FLAC encoder: LPC search, exact Rice sizing)
+FLAC_ENC_DEFAULT_BLOCK, FLAC_ENC_DEFAULT_LPC, FLAC_ENC_MAX_LPC, FLAC_ENC_VERIFY = 4096, 8, 12, 1
+FLAC_ENC_COMPLETE, FLAC_ENC_VERIFIED, FLAC_ENC_WRITTEN, FLAC_ENC_VERIFY_FAILED = 1, 2, 4, 8
+
+
+class FlacEncodeOptions(C.Structure):  # rg_flac_encode_options
+    _fields_ = [("struct_size", C.c_uint32), ("block_size", C.c_uint32), ("max_lpc_order", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class FlacEncodeRecord(C.Structure):  # rg_flac_encode_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("pcm_frames", C.c_uint64),
+        ("flac_frames", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("bits_per_sample", C.c_uint32),
+        ("block_size", C.c_uint32),
+        ("min_frame_bytes", C.c_uint32),
+        ("max_frame_bytes", C.c_uint32),
+        ("pcm_bytes", C.c_uint64),
+        ("stream_bytes", C.c_uint64),
+        ("metadata_bytes", C.c_uint64),
+        ("md5_pcm", C.c_uint8 * 16),
+        ("md5_decoded", C.c_uint8 * 16),
+    ]
+
+
+FLACENC_SYMBOLS = [
+    ("rg_flac_encode_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _P(_u32), _vp, _sz, _P(FlacEncodeOptions), _vp, _sz, _P(_u64), _P(FlacEncodeRecord)]),
+    ("rg_flac_encode_files", _int, [_vp, _P(C.c_char_p), _P(C.c_char_p), _sz, _P(FlacEncodeOptions), _P(FlacEncodeRecord)]),
+    ("rg_flac_encode_source_blocks", _int, [_vp, _sz, _vp, _sz, _P(_sz)]),
+    ("rg_flac_encode_rate", _int, [_vp, _sz, _P(TrackDesc), _P(_u32), _vp, _sz, _P(FlacEncodeOptions), _u32, _P(_dbl), _P(_u64)]),
+]
+
 # include/mp3rgain_amd_ancestry.h (lossy ancestry: an MP3 granule grid in PCM)
 ANC_COMPLETE, ANC_MP3_GRID, ANC_MIDSIDE, ANC_NONFINITE, ANC_SHORT, ANC_SILENT = 1, 2, 4, 8, 16, 32
 ANC_MAX_CHANNELS, ANC_MAX_VIEWS, ANC_ALIGNMENTS, ANC_VIEW_MID, ANC_VIEW_SIDE, ANC_NO_VIEW = 8, 10, 576, 8, 9, 0xFFFFFFFF
@@ -761,7 +798,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + STEREO_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS + RESAMPLE_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + STEREO_SYMBOLS + FLACENC_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS + RESAMPLE_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

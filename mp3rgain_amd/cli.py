@@ -88,6 +88,11 @@ class Options:  # src/main.rs:65-96
     key: bool = False  # this façade only (--key): in which musical key is each file?  One of 12 major and 12 minor keys
     key_segment: Optional[int] = None  # with --key (--key-segment ROWS): the rows of a segment of the steadiness figure
     stereo: bool = False  # this façade only (--stereo): how do the two channels of each file relate?  Dual mono, inverted, delayed, ...
+    encode: bool = False  # this façade only (--encode): WAV and FLAC files to FLAC, encoded on the GPU, verified before they are written
+    encode_dir: Optional[Path] = None  # with --encode (--encode-dir DIR, required): where <stem>.flac goes
+    encode_lpc: Optional[int] = None  # with --encode (--encode-lpc N): the largest LPC order tried
+    encode_block: Optional[int] = None  # with --encode (--encode-block N): the block size
+    encode_verify: bool = True  # --no-encode-verify clears it
     stereo_radius: Optional[int] = None  # with --stereo (--stereo-radius N): the largest channel delay looked for, in samples
     files: List[Path] = field(default_factory=list)
 
@@ -205,6 +210,16 @@ def parse_args(args: List[str], out, err) -> Options:
             o.key_segment = _parse_int(need("--key-segment", "--key-segment requires an argument"), "invalid number of rows", 32, signed=False)
         elif arg == "--stereo":  # not in the reference: a command of its own, like --dr
             o.stereo = True
+        elif arg == "--encode":  # not in the reference: a command of its own
+            o.encode = True
+        elif arg == "--encode-dir":
+            o.encode_dir = Path(need("--encode-dir", "--encode-dir requires an argument"))
+        elif arg == "--encode-lpc":
+            o.encode_lpc = _parse_int(need("--encode-lpc", "--encode-lpc requires an argument"), "invalid LPC order", 32, signed=False)
+        elif arg == "--encode-block":
+            o.encode_block = _parse_int(need("--encode-block", "--encode-block requires an argument"), "invalid block size", 32, signed=False)
+        elif arg == "--no-encode-verify":
+            o.encode_verify = False
         elif arg == "--stereo-radius":
             o.stereo_radius = _parse_int(need("--stereo-radius", "--stereo-radius requires an argument"), "invalid radius", 32, signed=False)
         elif arg == "--decoder":  # not in the reference: see the module docstring
@@ -396,6 +411,25 @@ def parse_args(args: List[str], out, err) -> Options:
                                         ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
         if others:
             raise CliError(f"--stereo is a command of its own and cannot be combined with {', '.join(others)}")
+    if not o.encode:
+        given = [name for name, on in (("--encode-dir", o.encode_dir is not None), ("--encode-lpc", o.encode_lpc is not None),
+                                       ("--encode-block", o.encode_block is not None), ("--no-encode-verify", not o.encode_verify)) if on]
+        if given:
+            raise CliError(f"{given[0]} requires --encode")
+    else:
+        if o.encode_dir is None:
+            raise CliError("--encode requires --encode-dir DIR")
+        if o.encode_lpc is not None and not 0 <= o.encode_lpc <= _capi.FLAC_ENC_MAX_LPC:
+            raise CliError(f"--encode-lpc takes 0 to {_capi.FLAC_ENC_MAX_LPC}: {o.encode_lpc}")
+        if o.encode_block is not None and o.encode_block not in (256, 512, 1024, 2048, 4096):
+            raise CliError(f"--encode-block takes 256, 512, 1024, 2048 or 4096: {o.encode_block}")
+        others = [name for name, on in (("--verify", o.verify), ("--rip", o.rip), ("--stats", o.stats), ("--spectrum", o.spectrum), ("--dr", o.dr),
+                                        ("--ancestry", o.ancestry), ("--duplicates", o.duplicates), ("--tempo", o.tempo), ("--key", o.key),
+                                        ("--stereo", o.stereo), ("--r128", o.r128), ("-x", o.max_amplitude_only), ("-r", o.track_gain),
+                                        ("-a", o.album_gain), ("-u", o.undo), ("-g", o.gain_steps is not None), ("-l", o.channel_gain is not None),
+                                        ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
+        if others:
+            raise CliError(f"--encode is a command of its own and cannot be combined with {', '.join(others)}")
     return o
 
 
@@ -691,6 +725,8 @@ class Cli:
             return self.cmd_key()
         if o.stereo:
             return self.cmd_stereo()
+        if o.encode:
+            return self.cmd_encode()
         if o.max_amplitude_only:
             return self.cmd_max_amplitude()
         if o.stored_tag_mode == "delete":
@@ -1373,6 +1409,62 @@ class Cli:
             shown = next((w for w in named[1:] if w in r.verdicts), "stereo")
             notes = [w for w in r.verdicts if w not in ("stereo", "incomplete", shown)] + ([f"{r.dropped_frames} frames dropped"] if r.dropped_frames else [])
             self.p(f"{line}  {_name(file)}" + (f"  [{', '.join(notes)}]" if notes else ""))
+        return 1 if failed else 0
+
+    # ---- --encode (not in the reference): WAV and FLAC files to FLAC on the GPU ---------------------------------------------------
+    def cmd_encode(self) -> int:
+        """Every file decoded by the route the analysis uses and encoded where its PCM lies on the first GPU
+        (rg_flac_encode_files) into `<--encode-dir>/<stem>.flac`; unless --no-encode-verify every stream is decoded again on the
+        GPU and its MD5 held to the source's before the file is written.  Text: a line per file `name -> out  1234567 bytes,
+        61.3 % of the PCM, verified`, and a closing total.  Exit status 1 for any failing file.  TSV, no header: a row per file
+        `file, output, stream bytes, PCM bytes, PCM frames, FLAC frames, sample rate, channels, bits, dropped frames, verified,
+        MD5` (a failing file: `file, error text`)."""
+        o = self.o
+        outs = [o.encode_dir / (Path(f).stem + ".flac") for f in o.files]
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            recs = an.encode_flac(o.files, outs, block_size=o.encode_block, max_lpc_order=o.encode_lpc, verify=o.encode_verify)
+        failed = sum(1 for r in recs if r.error is not None)
+        good = [r for r in recs if r.error is None]
+        total_stream, total_pcm = sum(r.stream_bytes for r in good), sum(r.pcm_bytes for r in good)
+        if o.output_format == "json":
+            files = []
+            for file, dst, r in zip(o.files, outs, recs):
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                    d["verify_failed"] = r.verify_failed
+                else:
+                    d.update(output=str(dst), stream_bytes=r.stream_bytes, pcm_bytes=r.pcm_bytes, ratio=r.ratio, pcm_frames=r.pcm_frames,
+                             flac_frames=r.flac_frames, sample_rate=r.sample_rate, channels=r.channels, bits_per_sample=r.bits_per_sample,
+                             block_size=r.block_size, min_frame_bytes=r.min_frame_bytes, max_frame_bytes=r.max_frame_bytes,
+                             metadata_bytes=r.metadata_bytes, dropped_frames=r.dropped_frames, complete=r.complete, verified=r.verified,
+                             md5=r.md5_pcm.hex())
+                files.append(d)
+            _print_json(self.out, files=files, stream_bytes=total_stream, pcm_bytes=total_pcm,
+                        summary=_summary(len(o.files), len(o.files) - failed, failed, False))
+            return 1 if failed else 0
+        if o.output_format == "tsv":
+            for file, dst, r in zip(o.files, outs, recs):
+                if r.error is not None:
+                    self.p(f"{_name(file)}\t{r.error}")
+                    continue
+                self.p(f"{_name(file)}\t{dst}\t{r.stream_bytes}\t{r.pcm_bytes}\t{r.pcm_frames}\t{r.flac_frames}\t{r.sample_rate}\t{r.channels}\t"
+                       f"{r.bits_per_sample}\t{r.dropped_frames}\t{int(r.verified)}\t{r.md5_pcm.hex()}")
+            return 1 if failed else 0
+        if self.talk:
+            self.p(f"mp3rgain encoding {len(o.files)} file(s) to FLAC in {o.encode_dir}" + ("" if o.encode_verify else " (not verified)"))
+            self.p()
+        for file, dst, r in zip(o.files, outs, recs):
+            if r.error is not None:
+                self.e(f"{_name(file)} - {r.error}")
+                continue
+            notes = (["verified"] if r.verified else []) + ([f"{r.dropped_frames} frames of the source dropped"] if r.dropped_frames else [])
+            self.p(f"{_name(file)} -> {dst}  {r.stream_bytes} bytes, {100.0 * r.ratio:.1f} % of the PCM" + "".join(", " + w for w in notes))
+        if self.talk:
+            self.p()
+            self.p(f"{len(good)} of {len(o.files)} file(s) written: {total_stream} bytes, "
+                   f"{100.0 * total_stream / total_pcm if total_pcm else 0.0:.1f} % of {total_pcm} bytes of PCM")
         return 1 if failed else 0
 
     # ---- find_max_amplitude, src/lib.rs:1174-1199 ------------------------------------------------------------
@@ -2080,6 +2172,15 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "            material only and held to no other tool.  JSON carries every field of the record.  Exit status 1 only for a file",
         "            that fails or has dropped frames",
         "--stereo-radius <N>  With --stereo: the largest delay looked for, in samples (default 64; 0 to 255)",
+        "--encode    Encode the files (WAV with 8, 16 or 24-bit integer samples, FLAC) to FLAC on the GPU, into <--encode-dir>/<stem>.flac:",
+        "            LPC search at every even order, exact Rice sizing of every candidate, mid/side for two channels.  Unless",
+        "            --no-encode-verify each stream is decoded again on the GPU and its MD5 held to the source's before its file is",
+        "            written.  An output that exists is never replaced.  A FLAC source keeps its tags and pictures; no SEEKTABLE is",
+        "            written.  Float WAV and MP3 sources are refused.  Exit status 1 for any failing file",
+        "--encode-dir <DIR>  With --encode (required): where the outputs go",
+        "--encode-lpc <N>  With --encode: the largest LPC order tried (default 8; 0 to 12, 0 = FIXED predictors only)",
+        "--encode-block <N>  With --encode: the block size (default 4096; 256, 512, 1024, 2048 or 4096)",
+        "--no-encode-verify  With --encode: write without decoding the streams again",
         "-v          Show version",
         "-h          Show this help",
     ):

@@ -197,6 +197,9 @@ struct rg_ctx {
     DevBuf<unsigned char> d_spectrum;        // rg_spectrum.hip: [tables | per run plane records, tile -> plane | tile records | skipped | per-plane results]
     DevBuf<unsigned char> d_dr;              // rg_dr.hip: [plane records | piece -> plane | piece records | block records | per-plane results] of one launch
     DevBuf<unsigned char> d_stereo;          // rg_stereo.hip: [track records | piece -> track | tile -> track | piece records | lag sums | per-track results] of one launch
+    DevBuf<unsigned char> d_flacenc;         // rg_flacenc.hip: [stream records | frame records | frame offsets | per-stream layout | fail flag] of one call
+    DevBuf<unsigned char> d_flacenc_out;     // the streams it wrote
+    DevBuf<unsigned char> d_flacenc_verify;  // the verified write: the streams decoded again, in the arena's format
     DevBuf<unsigned char> d_ancestry;        // rg_ancestry.hip: [tables | view records | tile records | counts | nonfinite] of one launch
     DevBuf<unsigned char> d_fprint;          // rg_fprint.hip: [tables | track records | tile -> track | tile counts | track counts] of one launch; rg_fprint_match.hip: [pairs | records]
     DevBuf<uint32_t> d_fp_codes;             // the fingerprint codes of one rg_same_recording call, kept from group to group

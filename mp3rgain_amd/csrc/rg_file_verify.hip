@@ -3,9 +3,14 @@
 // (include/mp3rgain_amd_rip.h), and the four PCM scans, which share one group driver (pcm_scan_group): rg_pcm_stats
 // (include/mp3rgain_amd_stats.h), rg_dynamic_range (include/mp3rgain_amd_dr.h), rg_ancestry (include/mp3rgain_amd_ancestry.h),
 // rg_spectrum (include/mp3rgain_amd_spectrum.h), rg_same_recording (include/mp3rgain_amd_fingerprint.h), rg_tempo
-// (include/mp3rgain_amd_tempo.h), rg_key (include/mp3rgain_amd_key.h) and rg_stereo (include/mp3rgain_amd_stereo.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
+// (include/mp3rgain_amd_tempo.h), rg_key (include/mp3rgain_amd_key.h) and rg_stereo (include/mp3rgain_amd_stereo.h); and the one that
+// writes files, rg_flac_encode_files (include/mp3rgain_amd_flacenc.h).  They take the analysis calls' route (rg_files.h: for_each_group, FileGroup) without a decoder
 // command: what this library does not decode itself is not a stream it could vouch for.  A file's status lives in its record,
 // and the record of a file that failed holds nothing else.
+#include <stdio.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include <algorithm>
 
 #include "rg_ancestry.h"
@@ -21,6 +26,7 @@
 #include "rg_resample.h"
 #include "rg_stats.h"
 #include "rg_stereo.h"
+#include "rg_flacenc.h"
 
 using namespace rgf;
 
@@ -508,6 +514,146 @@ extern "C" int rg_stereo(rg_ctx *c, const char *const *paths, size_t n, const rg
     return pcm_scan_call(
         c, paths, n, opts, out, rg_st_options, [&](size_t first, size_t cnt, const rg_stereo_opts &o) { return stereo_group(c, paths, first, cnt, o, out, lag_sums); },
         lag_sums, rows);
+}
+
+// ---- rg_flac_encode_files: the kernels of rg_flacenc.hip; the metadata and the files are host work ---------------------------
+static bool same_file(const char *a, const char *b) {
+    struct stat sa, sb;
+    return stat(a, &sa) == 0 && stat(b, &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
+}
+
+// `bytes` into "<path>.part", then linked to `path`: a file that exists is never replaced, and no partial file is left
+static bool write_new_file(const char *path, const uint8_t *bytes, size_t len, std::string *why) {
+    const std::string part = std::string(path) + ".part";
+    FILE *f = fopen(part.c_str(), "wb");
+    if (!f) {
+        *why = std::string("cannot create ") + part;
+        return false;
+    }
+    const bool wrote = fwrite(bytes, 1, len, f) == len;
+    const bool closed = fclose(f) == 0;
+    bool ok = wrote && closed;
+    if (!ok) *why = std::string("cannot write ") + part;
+    if (ok && link(part.c_str(), path) != 0) {
+        ok = false;
+        *why = std::string("cannot name the output (it exists?): ") + path;
+    }
+    (void)unlink(part.c_str());
+    return ok;
+}
+
+static int flac_encode_group(rg_ctx *c, const char *const *paths, const char *const *out_paths, size_t first, size_t n, uint32_t block, uint32_t max_lpc,
+                             uint32_t flags, rg_flac_encode_result *out) {
+    FileGroup g(c, paths, first, n);
+    out += first;
+    out_paths += first;
+    const int lrc = g.load(LoadOpts{-1, false});
+    if (lrc != RG_OK) return lrc;
+    const auto mark = mark_record(g, out);
+    const auto screen = [&](size_t i, std::string *text) -> int {
+        const LoadedAudio &la = g.in[i];
+        if (la.kind != LoadedAudio::Wav && la.kind != LoadedAudio::Flac) {
+            *text = pcm_refused(g, "FLAC encode", i, "an MPEG source: a lossless container round lossy audio");
+            return RG_ERR_FORMAT;
+        }
+        const int rc = pcm_screen(g, i, 8, "FLAC encode", text);
+        if (rc != RG_OK) return rc;
+        if (la.kind == LoadedAudio::Wav) {
+            rg_wav_info w;
+            (void)rg_wav_parse(la.wav.data(), la.wav.size(), &w);  // (pcm_screen has parsed this stream)
+            if (w.sample_format == 3 || w.bits_per_sample > 24) {
+                *text = pcm_refused(g, "FLAC encode", i, w.sample_format == 3 ? "float samples" : "32-bit samples, more than 24");
+                return RG_ERR_FORMAT;
+            }
+        }
+        struct stat sb;
+        if (!out_paths[i] || !*out_paths[i]) {
+            *text = std::string("No output path for: ") + g.paths[i];
+            return RG_ERR_IO;
+        }
+        if (same_file(g.paths[i], out_paths[i])) {
+            *text = std::string("The output is the input: ") + out_paths[i];
+            return RG_ERR_IO;
+        }
+        if (lstat(out_paths[i], &sb) == 0) {
+            *text = std::string("The output exists: ") + out_paths[i];
+            return RG_ERR_IO;
+        }
+        return RG_OK;
+    };
+    const auto work = [&]() -> int {
+        std::vector<RgFeStream> st;
+        std::vector<std::vector<uint8_t>> blocks;
+        std::vector<size_t> ks;  // stream -> position in the batch
+        for (size_t k = 0; k < g.slot.size(); ++k) {
+            const size_t i = g.slot[k];
+            const LoadedAudio &la = g.in[k];
+            uint32_t bps = la.flac_bps;
+            if (la.kind == LoadedAudio::Wav) {
+                rg_wav_info w;
+                (void)rg_wav_parse(la.wav.data(), la.wav.size(), &w);
+                bps = w.bits_per_sample;
+            }
+            char err[kPcmErrLen] = "";
+            RgFeStream s;
+            const int rc = rg_fe_stream(i, g.descs[k], bps, c->d_arena.p, g.arena_bytes, block, max_lpc, &s, err, sizeof err);
+            if (rc == RG_ERR_FORMAT) {
+                mark(i, rc, pcm_refused(g, "FLAC encode", i, err));
+                continue;
+            }
+            if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
+            std::vector<uint8_t> b;
+            if (la.kind == LoadedAudio::Flac && rg_fe_source_blocks(la.file_bytes.data(), la.file_bytes.size(), &b)) s.meta_bytes = (uint32_t)(42 + b.size());
+            else b.clear();  // the vendor block
+            st.push_back(s);
+            blocks.push_back(std::move(b));
+            ks.push_back(k);
+        }
+        if (st.empty()) return RG_OK;
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> offsets(st.size() + 1);
+        std::vector<rg_flac_encode_result> res(st.size());
+        int rc = rg_fe_device(c, st, &blocks, nullptr, 0, &bytes, offsets.data(), res.data(), c->file_stream(), nullptr);
+        if (rc != RG_OK) return rc;
+        std::vector<uint8_t> ok(st.size(), 1);
+        if (flags & RG_FLAC_ENC_VERIFY) {
+            rc = rg_fe_verify_device(c, st, bytes.data(), offsets.data(), res.data(), &ok, c->file_stream());
+            if (rc != RG_OK) return rc;
+        }
+        for (size_t j = 0; j < st.size(); ++j) {
+            const size_t k = ks[j], i = g.slot[k];
+            rg_flac_encode_result r = res[j];
+            r.dropped_frames = dropped_frames(g, k);
+            if (r.dropped_frames) r.flags &= ~RG_FLAC_ENC_COMPLETE;
+            if (!ok[j]) {
+                mark(i, RG_ERR_STATE, std::string("The encoded stream does not decode to its source (nothing was written): ") + g.paths[i]);
+                out[i].flags = RG_FLAC_ENC_VERIFY_FAILED;
+                continue;
+            }
+            if (flags & RG_FLAC_ENC_VERIFY) r.flags |= RG_FLAC_ENC_VERIFIED;
+            std::string why;
+            if (!write_new_file(out_paths[i], bytes.data() + offsets[j], (size_t)(offsets[j + 1] - offsets[j]), &why)) {
+                mark(i, RG_ERR_IO, why);
+                continue;
+            }
+            r.flags |= RG_FLAC_ENC_WRITTEN;
+            out[i] = r;
+        }
+        return RG_OK;
+    };
+    g.want_counts = true;
+    return g.run(screen, mark, work);
+}
+
+extern "C" int rg_flac_encode_files(rg_ctx *c, const char *const *in_paths, const char *const *out_paths, size_t n, const rg_flac_encode_options *options,
+                                    rg_flac_encode_result *results) {
+    if (!c || (n && (!in_paths || !out_paths || !results))) return RG_ERR_INVALID_ARG;
+    uint32_t block, max_lpc, flags;
+    char err[256] = "";
+    const int orc = rg_fe_options(options, &block, &max_lpc, &flags, err, sizeof err);
+    if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
+    if (n) memset(results, 0, n * sizeof *results);
+    return for_each_group(c, in_paths, n, [&](size_t first, size_t cnt) { return flac_encode_group(c, in_paths, out_paths, first, cnt, block, max_lpc, flags, results); });
 }
 
 // ---- rg_ancestry: the kernels of rg_ancestry.hip; the verdict is host arithmetic on the counts that come back (rg_anc_fill) --

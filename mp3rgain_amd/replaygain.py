@@ -475,6 +475,82 @@ def stereo_arena(ctx, route: int, descs, arena, radius=None, block_frames=None, 
     return (list(out[:n]), rows[:n]) if lag_sums else list(out[:n])
 
 
+def _flac_encode_opts(block_size, max_lpc_order, verify=True):
+    """rg_flac_encode_options, or NULL (the header's defaults) when nothing departs from them."""
+    if block_size is None and max_lpc_order is None and verify:
+        return None
+    return C.byref(_capi.FlacEncodeOptions(C.sizeof(_capi.FlacEncodeOptions), 0 if block_size is None else int(block_size),
+                                           _capi.FLAC_ENC_DEFAULT_LPC if max_lpc_order is None else int(max_lpc_order),
+                                           _capi.FLAC_ENC_VERIFY if verify else 0))
+
+
+@dataclass
+class FlacEncoded:
+    """One file of Analyzer.encode_flac (rg_flac_encode_result)."""
+    pcm_frames: int
+    flac_frames: int
+    dropped_frames: int      # FLAC frames of the source that did not decode
+    sample_rate: int
+    channels: int
+    bits_per_sample: int
+    block_size: int
+    min_frame_bytes: int
+    max_frame_bytes: int
+    pcm_bytes: int
+    stream_bytes: int
+    metadata_bytes: int
+    md5_pcm: bytes
+    md5_decoded: bytes
+    flags: int
+    error: Optional[Exception] = None
+
+    @property
+    def complete(self) -> bool:
+        return bool(self.flags & _capi.FLAC_ENC_COMPLETE)
+
+    @property
+    def verified(self) -> bool:
+        return bool(self.flags & _capi.FLAC_ENC_VERIFIED)
+
+    @property
+    def written(self) -> bool:
+        return bool(self.flags & _capi.FLAC_ENC_WRITTEN)
+
+    @property
+    def verify_failed(self) -> bool:
+        return bool(self.flags & _capi.FLAC_ENC_VERIFY_FAILED)
+
+    @property
+    def ratio(self) -> float:
+        """Stream bytes over PCM bytes (0 for a file without audio)."""
+        return self.stream_bytes / self.pcm_bytes if self.pcm_bytes else 0.0
+
+
+def flac_encode_arena(ctx, route: int, descs, bps, arena, block_size=None, max_lpc_order=None):
+    """rg_flac_encode_arena without an Analyzer: route 0 is the serial host twin and takes ctx = None.  The tracks `descs`
+    describe in the host arena `arena` (left-justified integer planes of `bps` [int] bits) -> ([the FLAC stream of each track
+    as bytes], [FlacEncodeRecord], the offsets as the call set them)."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    b = (C.c_uint32 * max(1, n))(*[int(v) for v in bps])
+    res = (_capi.FlacEncodeRecord * max(1, n))()
+    offsets = (C.c_uint64 * (n + 1))()
+    opts = _flac_encode_opts(block_size, max_lpc_order)
+    out = np.zeros(0, dtype=np.uint8)
+    for _ in range(2):  # the first call, into nothing, says how much the streams take
+        rc = L.rg_flac_encode_arena(ctx, int(route), n, d, b, arena.ctypes.data if arena.size else None, arena.size, opts,
+                                    out.ctypes.data if out.size else None, out.size, offsets, res)
+        if rc == 0 or int(offsets[n]) <= out.size:
+            break
+        out = np.zeros(int(offsets[n]), dtype=np.uint8)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    offs = [int(v) for v in offsets]
+    return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)], list(res[:n]), offs
+
+
 def stereo_kernel_shape(fmt: int):
     """rg_stereo_kernel_shape of one rg_sample_format -> (piece_samples, tile_frames, strip_frames, lag_group, lds_bytes)."""
     v = [C.c_uint32() for _ in range(5)]
@@ -2191,6 +2267,27 @@ class Analyzer:
     @staticmethod
     def stereo_kernel_shape(fmt: int):
         return stereo_kernel_shape(fmt)
+
+    def encode_flac(self, files, out_files, block_size=None, max_lpc_order=None, verify=True) -> list:
+        """rg_flac_encode_files: `files` (WAV with integer samples, FLAC) decoded by the route the analysis uses and encoded
+        where their PCM lies on this GPU, files[i] into out_files[i] -> [FlacEncoded].  With `verify` every stream is decoded
+        again by the device decoder and its MD5 held to the source's before the file is written.  A file that fails carries its
+        ReplayGainError in `.error` and leaves no output."""
+        if len(files) != len(out_files):
+            raise ValueError("encode_flac: as many outputs as inputs")
+        n = len(files)
+        paths, out = self._file_args(files, _capi.FlacEncodeRecord)
+        outs = (C.c_char_p * max(1, n))(*[os.fsencode(os.fspath(f)) for f in out_files])
+        self._check(self._lib.rg_flac_encode_files(self._ctx, paths, outs, n, _flac_encode_opts(block_size, max_lpc_order, verify), out))
+        return [FlacEncoded(int(r.pcm_frames), int(r.flac_frames), int(r.dropped_frames), int(r.sample_rate), int(r.channels), int(r.bits_per_sample),
+                            int(r.block_size), int(r.min_frame_bytes), int(r.max_frame_bytes), int(r.pcm_bytes), int(r.stream_bytes),
+                            int(r.metadata_bytes), bytes(r.md5_pcm), bytes(r.md5_decoded), int(r.flags), err) for r, err in self._file_records(out, n)]
+
+    def flac_encode_arena(self, route: int, descs, bps, arena, block_size=None, max_lpc_order=None):
+        """rg_flac_encode_arena, the seam of the FLAC encoder: the tracks `descs` describe in the host arena `arena` ->
+        ([stream bytes], [FlacEncodeRecord], offsets); route 0 = the serial host twin, route 1 = the arena copied to this GPU
+        and the analyse, layout and write kernels."""
+        return flac_encode_arena(self._ctx, route, descs, bps, arena, block_size, max_lpc_order)
 
     def _same_recording_call(self, files, block, probes, radius, max_ber_permille, codes_cap):
         paths, out = self._file_args(files, _capi.FingerprintRecord)
