@@ -549,6 +549,120 @@ pub mod replaygain {
     }
 }
 
+/// The click scan of `include/mp3rgain_amd_clicks.h`: are there clicks or glitches in each of these WAV, FLAC or MP3 files?  Every
+/// channel is predicted block by block by the FLAC encoder's linear model on the GPU; a sample whose residual stands far above the
+/// median residual around it is flagged, flagged samples close together make an event, a narrow event is a click and a wide one a
+/// burst.  The definitions are a convention of that header, tried on synthetic material only and held to no other tool; the
+/// default `ratio_permille` is measured on synthetic material (`tests/golden/clicks_measured.json`).  A module of its own, as
+/// [`stereo`] is.  `tests/test_rust_clicks_layout.py` compares these declarations with the header.
+pub mod clicks {
+    use super::ffi::RgCtx;
+    use std::os::raw::{c_char, c_int};
+
+    pub const CK_COMPLETE: u32 = 1;
+    pub const CK_SILENT: u32 = 2;
+    pub const CK_NONFINITE: u32 = 4;
+    pub const CK_CLICKS: u32 = 8;
+    pub const CK_BURSTS: u32 = 16;
+    pub const CK_TRUNCATED: u32 = 32;
+    pub const CK_KIND_CLICK: u32 = 1;
+    pub const CK_KIND_BURST: u32 = 2;
+    pub const CK_MAX_CHANNELS: usize = 8;
+    pub const CK_MAX_ORDER: u32 = 12;
+    pub const CK_MAX_EVENTS: u32 = 256;
+    pub const CK_DEFAULT_BLOCK: u32 = 1024;
+    pub const CK_DEFAULT_ORDER: u32 = 8;
+    pub const CK_DEFAULT_RATIO_PERMILLE: u32 = 8371;
+    pub const CK_DEFAULT_FLOOR: u32 = 4;
+    pub const CK_DEFAULT_GAP: u32 = 16;
+    pub const CK_DEFAULT_MAX_WIDTH: u32 = 32;
+    pub const CK_DEFAULT_MAX_EVENTS: u32 = 16;
+
+    #[derive(Clone, Copy, Debug)]
+    #[repr(C)]
+    /// `rg_clicks_opts`: every field is taken as it stands; a null pointer means the defaults
+    pub struct RgClicksOpts {
+        pub block_samples: u32,
+        pub order: u32,
+        pub ratio_permille: u32,
+        pub floor: u32,
+        pub gap: u32,
+        pub max_width: u32,
+        pub max_events: u32,
+    }
+
+    impl Default for RgClicksOpts {
+        fn default() -> Self {
+            RgClicksOpts {
+                block_samples: CK_DEFAULT_BLOCK,
+                order: CK_DEFAULT_ORDER,
+                ratio_permille: CK_DEFAULT_RATIO_PERMILLE,
+                floor: CK_DEFAULT_FLOOR,
+                gap: CK_DEFAULT_GAP,
+                max_width: CK_DEFAULT_MAX_WIDTH,
+                max_events: CK_DEFAULT_MAX_EVENTS,
+            }
+        }
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_clicks_channel`: `first_click` and `strongest_at` equal the record's `frames` when the channel has no click
+    pub struct RgClicksChannel {
+        pub flagged: u32,
+        pub clicks: u32,
+        pub bursts: u32,
+        pub widest: u32,
+        pub first_click: u32,
+        pub strongest_at: u32,
+        pub strongest_permille: u32,
+        pub fallback_blocks: u32,
+        pub median_max: u32,
+        pub reserved: u32,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_clicks_event`: `kind` is `CK_KIND_CLICK` or `CK_KIND_BURST`, 0 in an unused record
+    pub struct RgClicksEvent {
+        pub start: u32,
+        pub width: u32,
+        pub peak_at: u32,
+        pub strength_permille: u32,
+        pub channel: u16,
+        pub kind: u16,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_clicks_result`: `ch[c]` is channel c; `listed` of `events` are in the file's row of the event list
+    pub struct RgClicksResult {
+        pub status: i32,
+        pub flags: u32,
+        pub frames: u64,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub format: u32,
+        pub dropped_frames: u32,
+        pub block_samples: u32,
+        pub order: u32,
+        pub ratio_permille: u32,
+        pub floor: u32,
+        pub gap: u32,
+        pub max_width: u32,
+        pub max_events: u32,
+        pub listed: u32,
+        pub nonfinite: u64,
+        pub events: u64,
+        pub ch: [RgClicksChannel; CK_MAX_CHANNELS],
+    }
+
+    extern "C" {
+        pub fn rg_clicks(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, opts: *const RgClicksOpts, out: *mut RgClicksResult,
+                         events: *mut RgClicksEvent) -> c_int;
+    }
+}
+
 /// The FLAC encoder of `include/mp3rgain_amd_flacenc.h`: WAV files with integer samples and FLAC files are decoded by the route the
 /// analysis uses and encoded where their PCM lies on the GPU -- an LPC search at every even order, every candidate's Rice coding
 /// sized exactly, mid/side for two channels -- and each stream is decoded again by the device decoder and its MD5 held to the

@@ -53,7 +53,8 @@
  *
  * Not here: RMS or loudness (the R 128 path has LUFS, loudness range and true peak; the per-block RMS, the peaks and the DR value
  * are rg_dynamic_range, mp3rgain_amd_dr.h), the node and multi-GPU calls.  Spectral detection of lossy transcodes
- * and upsampled files is rg_spectrum (mp3rgain_amd_spectrum.h).
+ * and upsampled files is rg_spectrum (mp3rgain_amd_spectrum.h).  Clicks and glitches -- neither full-scale nor zero -- are
+ * rg_clicks (mp3rgain_amd_clicks.h).
  * Nothing is written to files.
  */
 #ifndef MP3RGAIN_AMD_STATS_H

@@ -513,6 +513,60 @@ FLACENC_SYMBOLS = [
     ("rg_flac_encode_rate", _int, [_vp, _sz, _P(TrackDesc), _P(_u32), _vp, _sz, _P(FlacEncodeOptions), _u32, _P(_dbl), _P(_u64)]),
 ]
 
+# include/mp3rgain_amd_clicks.h (clicks and glitches: the encoder's linear model per block, residual against the local median, events)
+CK_COMPLETE, CK_SILENT, CK_NONFINITE, CK_CLICKS, CK_BURSTS, CK_TRUNCATED = (1 << k for k in range(6))
+CK_KIND_CLICK, CK_KIND_BURST = 1, 2
+CK_MAX_CHANNELS, CK_MAX_ORDER, CK_MAX_EVENTS = 8, 12, 256
+(CK_DEFAULT_BLOCK, CK_DEFAULT_ORDER, CK_DEFAULT_RATIO_PERMILLE, CK_DEFAULT_FLOOR, CK_DEFAULT_GAP, CK_DEFAULT_MAX_WIDTH,
+ CK_DEFAULT_MAX_EVENTS) = 1024, 8, 8371, 4, 16, 32, 16
+
+
+class ClicksOpts(C.Structure):  # rg_clicks_opts
+    _fields_ = [("block_samples", C.c_uint32), ("order", C.c_uint32), ("ratio_permille", C.c_uint32), ("floor", C.c_uint32), ("gap", C.c_uint32),
+                ("max_width", C.c_uint32), ("max_events", C.c_uint32)]
+
+
+class ClicksChannel(C.Structure):  # rg_clicks_channel
+    _fields_ = [("flagged", C.c_uint32), ("clicks", C.c_uint32), ("bursts", C.c_uint32), ("widest", C.c_uint32), ("first_click", C.c_uint32),
+                ("strongest_at", C.c_uint32), ("strongest_permille", C.c_uint32), ("fallback_blocks", C.c_uint32), ("median_max", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class ClicksEvent(C.Structure):  # rg_clicks_event
+    _fields_ = [("start", C.c_uint32), ("width", C.c_uint32), ("peak_at", C.c_uint32), ("strength_permille", C.c_uint32), ("channel", C.c_uint16),
+                ("kind", C.c_uint16)]
+
+
+class ClicksRecord(C.Structure):  # rg_clicks_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("dropped_frames", C.c_uint32),
+        ("block_samples", C.c_uint32),
+        ("order", C.c_uint32),
+        ("ratio_permille", C.c_uint32),
+        ("floor", C.c_uint32),
+        ("gap", C.c_uint32),
+        ("max_width", C.c_uint32),
+        ("max_events", C.c_uint32),
+        ("listed", C.c_uint32),
+        ("nonfinite", C.c_uint64),
+        ("events", C.c_uint64),
+        ("ch", ClicksChannel * CK_MAX_CHANNELS),
+    ]
+
+
+CLICKS_SYMBOLS = [
+    ("rg_clicks", _int, [_vp, _P(C.c_char_p), _sz, _P(ClicksOpts), _P(ClicksRecord), _P(ClicksEvent)]),
+    ("rg_clicks_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _P(ClicksOpts), _vp, _sz, _P(ClicksRecord), _P(ClicksEvent)]),
+    ("rg_clicks_kernel_shape", _int, [_u32, _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_clicks_rate", _int, [_vp, _sz, _u64, _u32, _P(ClicksOpts), _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz), _P(_u64), _P(_u64)]),
+]
+
 # include/mp3rgain_amd_ancestry.h (lossy ancestry: an MP3 granule grid in PCM)
 ANC_COMPLETE, ANC_MP3_GRID, ANC_MIDSIDE, ANC_NONFINITE, ANC_SHORT, ANC_SILENT = 1, 2, 4, 8, 16, 32
 ANC_MAX_CHANNELS, ANC_MAX_VIEWS, ANC_ALIGNMENTS, ANC_VIEW_MID, ANC_VIEW_SIDE, ANC_NO_VIEW = 8, 10, 576, 8, 9, 0xFFFFFFFF
@@ -798,7 +852,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + STEREO_SYMBOLS + FLACENC_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS + RESAMPLE_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + STEREO_SYMBOLS + CLICKS_SYMBOLS + FLACENC_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS + RESAMPLE_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

@@ -197,6 +197,7 @@ struct rg_ctx {
     DevBuf<unsigned char> d_spectrum;        // rg_spectrum.hip: [tables | per run plane records, tile -> plane | tile records | skipped | per-plane results]
     DevBuf<unsigned char> d_dr;              // rg_dr.hip: [plane records | piece -> plane | piece records | block records | per-plane results] of one launch
     DevBuf<unsigned char> d_stereo;          // rg_stereo.hip: [track records | piece -> track | tile -> track | piece records | lag sums | per-track results] of one launch
+    DevBuf<unsigned char> d_clicks;          // rg_clicks.hip: [plane records | tile -> plane | tile records | events before a tile | listed tiles | count | per-plane results | event slots] of one launch
     DevBuf<unsigned char> d_flacenc;         // rg_flacenc.hip: [stream records | frame records | frame offsets | per-stream layout | fail flag] of one call
     DevBuf<unsigned char> d_flacenc_out;     // the streams it wrote
     DevBuf<unsigned char> d_flacenc_verify;  // the verified write: the streams decoded again, in the arena's format

@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "rg_ancestry.h"
+#include "rg_clicks.h"
 #include "rg_dr.h"
 #include "rg_files.h"
 #include "rg_flac_md5.h"
@@ -654,6 +655,44 @@ extern "C" int rg_flac_encode_files(rg_ctx *c, const char *const *in_paths, cons
     if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
     if (n) memset(results, 0, n * sizeof *results);
     return for_each_group(c, in_paths, n, [&](size_t first, size_t cnt) { return flac_encode_group(c, in_paths, out_paths, first, cnt, block, max_lpc, flags, results); });
+}
+
+// ---- rg_clicks: the kernels of rg_clicks.hip; the channel records and the merge of the planes' event lists are host code (rg_ck_fill)
+// The caller's event list is rows by file, so a group fills the rows of its own files.
+static int clicks_group(rg_ctx *c, const char *const *paths, size_t first, size_t n, const rg_clicks_opts &o, rg_clicks_result *out, rg_clicks_event *events) {
+    FileGroup g(c, paths, first, n);
+    out += first;
+    const uint32_t K = o.max_events;
+    std::vector<PcmRec> recs;
+    std::vector<RgCkPlane> planes(n * RG_CK_MAX_CHANNELS + 1);
+    size_t n_planes = 0;
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        const int rc = rg_ck_track_planes(i, g.descs[k], o, g.arena_bytes, &planes[n_planes], err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        recs.push_back(PcmRec{k, n_planes});
+        n_planes += g.descs[k].channels;
+        return RG_OK;
+    };
+    const auto finish = [&]() -> int {
+        if (recs.empty()) return RG_OK;
+        std::vector<RgCkTile> po(n_planes);
+        std::vector<RgCkEv> ev(n_planes * K + 1);
+        const int rc = rg_ck_device(c, c->d_arena.p, planes.data(), n_planes, o, po.data(), ev.data(), c->file_stream());
+        if (rc != RG_OK) return rc;
+        for (const PcmRec &r : recs)
+            rg_ck_fill(g.descs[r.k], o, dropped_frames(g, r.k), &po[r.plane], &ev[r.plane * K], &out[g.slot[r.k]], events ? events + (first + g.slot[r.k]) * K : nullptr);
+        return RG_OK;
+    };
+    return pcm_scan_group(g, "click scan", RG_CK_MAX_CHANNELS, out, add, finish);
+}
+
+extern "C" int rg_clicks(rg_ctx *c, const char *const *paths, size_t n, const rg_clicks_opts *opts, rg_clicks_result *out, rg_clicks_event *events) {
+    rg_clicks_opts probe;
+    char err[8];
+    const size_t rows = rg_ck_options(opts, &probe, err, sizeof err) == RG_OK ? n * probe.max_events * sizeof(rg_clicks_event) : 0;  // (pcm_scan_call reports a bad option)
+    return pcm_scan_call(
+        c, paths, n, opts, out, rg_ck_options, [&](size_t first, size_t cnt, const rg_clicks_opts &o) { return clicks_group(c, paths, first, cnt, o, out, events); },
+        events, rows);
 }
 
 // ---- rg_ancestry: the kernels of rg_ancestry.hip; the verdict is host arithmetic on the counts that come back (rg_anc_fill) --

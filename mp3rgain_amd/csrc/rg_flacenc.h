@@ -305,19 +305,25 @@ RG_FE_HD void rg_fe_try(X &x, RgFeWork &w, uint32_t n, const int32_t *c, bool ri
     rg_fe_rice(x, w, n, order, rice2);
 }
 
+// One step of the Levinson-Durbin recursion: order i -> i + 1 over lp[0 .. i] (tmp: scratch of i values); `err` is the
+// prediction error before the step, the return value the one after it.  The click scan (rg_clicks.h) runs these very steps.
+RG_FE_HD double rg_fe_levinson_step(const int64_t *acf, double *lp, double *tmp, uint32_t i, double err) {
+    double acc = (double)acf[i + 1];
+    for (uint32_t j = 0; j < i; ++j) acc = acc - lp[j] * (double)acf[i - j];
+    const double k = acc / err;
+    for (uint32_t j = 0; j < i; ++j) tmp[j] = lp[j] - k * lp[i - 1 - j];
+    for (uint32_t j = 0; j < i; ++j) lp[j] = tmp[j];
+    lp[i] = k;
+    return err * (1.0 - k * k);
+}
+
 // Levinson-Durbin on one lane: w.acf[0 .. maxo] -> w.lpc[o / 2 - 1][0 .. o) for the even orders o, w.lpc_orders of them
 RG_FE_HD void rg_fe_levinson(RgFeWork &w, uint32_t maxo) {
     w.lpc_orders = 0;
     if (w.acf[0] <= 0) return;
     double err = (double)w.acf[0];
     for (uint32_t i = 0; i < maxo; ++i) {
-        double acc = (double)w.acf[i + 1];
-        for (uint32_t j = 0; j < i; ++j) acc = acc - w.lp[j] * (double)w.acf[i - j];
-        const double k = acc / err;
-        for (uint32_t j = 0; j < i; ++j) w.tmp[j] = w.lp[j] - k * w.lp[i - 1 - j];
-        for (uint32_t j = 0; j < i; ++j) w.lp[j] = w.tmp[j];
-        w.lp[i] = k;
-        err = err * (1.0 - k * k);
+        err = rg_fe_levinson_step(w.acf, w.lp, w.tmp, i, err);
         if ((i & 1u) == 1u) {
             for (uint32_t j = 0; j <= i; ++j) w.lpc[i / 2][j] = w.lp[j];
             w.lpc_orders = i / 2 + 1;
@@ -326,37 +332,40 @@ RG_FE_HD void rg_fe_levinson(RgFeWork &w, uint32_t maxo) {
     }
 }
 
-// quantise w.lpc[oi] to `precision` bits: the shift from the largest coefficient's exponent bits, rounding with error feedback
-RG_FE_HD void rg_fe_quantise(RgFeWork &w, uint32_t oi, uint32_t precision) {
-    const uint32_t order = 2 * oi + 2;
-    w.qok[oi] = 0;
+// quantise lpc[0 .. order) to `precision` bits: the shift from the largest coefficient's exponent bits, rounding with error
+// feedback -> qc[0 .. order) and *qshift; false when there is no such quantisation
+RG_FE_HD bool rg_fe_quantise_to(const double *lpc, uint32_t order, uint32_t precision, int32_t *qc, int32_t *qshift) {
     uint64_t top = 0;  // the largest magnitude's bit pattern: for finite doubles the patterns order as the values do
     for (uint32_t j = 0; j < order; ++j) {
         uint64_t b;
-        const double c = w.lpc[oi][j];
+        const double c = lpc[j];
         memcpy(&b, &c, 8);
         b &= 0x7FFFFFFFFFFFFFFFull;
-        if ((b >> 52) == 0x7FFu) return;
+        if ((b >> 52) == 0x7FFu) return false;
         if (b > top) top = b;
     }
     const int e = (int)(top >> 52) - 1022;  // |c| = m 2^e, 0.5 <= m < 1
-    if ((top >> 52) == 0) return;
+    if ((top >> 52) == 0) return false;
     int shift = (int)precision - 1 - e;
     if (shift > 15) shift = 15;
-    if (shift < 0) return;
+    if (shift < 0) return false;
     const double scale = (double)(1u << shift);
     const int64_t hi = ((int64_t)1 << (precision - 1)) - 1, lo = -hi - 1;
     double err = 0.0;
     for (uint32_t j = 0; j < order; ++j) {
-        err = err + w.lpc[oi][j] * scale;
+        err = err + lpc[j] * scale;
         int64_t q = err >= 0.0 ? (int64_t)(err + 0.5) : -(int64_t)(0.5 - err);
         if (q > hi) q = hi;
         if (q < lo) q = lo;
         err = err - (double)q;
-        w.qc[oi][j] = (int32_t)q;
+        qc[j] = (int32_t)q;
     }
-    w.qshift[oi] = shift;
-    w.qok[oi] = 1;
+    *qshift = shift;
+    return true;
+}
+// ... w.lpc[oi] -> w.qc[oi], w.qshift[oi], w.qok[oi]
+RG_FE_HD void rg_fe_quantise(RgFeWork &w, uint32_t oi, uint32_t precision) {
+    w.qok[oi] = rg_fe_quantise_to(w.lpc[oi], 2 * oi + 2, precision, w.qc[oi], &w.qshift[oi]) ? 1u : 0u;
 }
 
 // The search over one signal: w.sig[0 .. n) holds it (sbps bits) -> w.best.  Candidates in this order, the earlier one

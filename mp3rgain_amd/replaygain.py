@@ -625,6 +625,144 @@ def stereo_from_record(r, error=None) -> StereoImage:
                          for f in _STEREO_FIELDS], error)
 
 
+def _clicks_opts(block_samples, order, ratio_permille, floor, gap, max_width, max_events):
+    """rg_clicks_opts, or NULL (the header's defaults) when all are None; a None field is its default."""
+    if all(v is None for v in (block_samples, order, ratio_permille, floor, gap, max_width, max_events)):
+        return None
+    pick = lambda v, d: d if v is None else int(v)  # noqa: E731
+    return C.byref(_capi.ClicksOpts(pick(block_samples, _capi.CK_DEFAULT_BLOCK), pick(order, _capi.CK_DEFAULT_ORDER),
+                                    pick(ratio_permille, _capi.CK_DEFAULT_RATIO_PERMILLE), pick(floor, _capi.CK_DEFAULT_FLOOR),
+                                    pick(gap, _capi.CK_DEFAULT_GAP), pick(max_width, _capi.CK_DEFAULT_MAX_WIDTH),
+                                    pick(max_events, _capi.CK_DEFAULT_MAX_EVENTS)))
+
+
+def _clicks_rows(n, max_events):
+    """The caller's event list: a ClicksEvent array of n rows of max_events (never empty)."""
+    k = _capi.CK_DEFAULT_MAX_EVENTS if max_events is None else max(0, min(int(max_events), _capi.CK_MAX_EVENTS))
+    return k, (_capi.ClicksEvent * max(1, n * k))()
+
+
+def clicks_arena(ctx, route: int, descs, arena, block_samples=None, order=None, ratio_permille=None, floor=None, gap=None, max_width=None,
+                 max_events=None):
+    """rg_clicks_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None -> ([ClicksRecord], ClicksEvent array
+    of max_events records per track, row after row).  Options None = the header's defaults."""
+    L = _capi.load()
+    n = len(descs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    out = (_capi.ClicksRecord * max(1, n))()
+    k, rows = _clicks_rows(n, max_events)
+    rc = L.rg_clicks_arena(ctx, int(route), n, d, _clicks_opts(block_samples, order, ratio_permille, floor, gap, max_width, max_events),
+                           arena.ctypes.data if arena.size else None, arena.size, out, rows)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    return list(out[:n]), rows
+
+
+def clicks_kernel_shape(block_samples: int):
+    """rg_clicks_kernel_shape of one block length -> (tile_samples, tile_blocks, fold_lanes, lds_bytes)."""
+    v = [C.c_uint32() for _ in range(4)]
+    rc = _capi.load().rg_clicks_kernel_shape(int(block_samples), *[C.byref(x) for x in v])
+    if rc != 0:
+        raise ReplayGainError(rc, f"rg_clicks_kernel_shape: block_samples {block_samples}")
+    return tuple(x.value for x in v)
+
+
+@dataclass
+class ClickEvent:
+    """One event of a file's list (rg_clicks_event)."""
+    start: int
+    width: int
+    channel: int
+    kind: str            # "click" or "burst"
+    peak_at: int
+    strength_permille: int
+
+
+@dataclass
+class ClickChannel:
+    """One channel of a Clicks record (rg_clicks_channel)."""
+    flagged: int
+    clicks: int
+    bursts: int
+    widest: int
+    first_click: int          # == frames when there is none
+    strongest_at: int         # == frames when there is none
+    strongest_permille: int
+    fallback_blocks: int
+    median_max: int
+
+
+@dataclass
+class Clicks:
+    """One file of Analyzer.clicks (rg_clicks_result and its row of the event list): clicks and bursts per channel.  The
+    definitions are a convention of include/mp3rgain_amd_clicks.h, tried on synthetic material only and held to no other tool."""
+    frames: int
+    sample_rate: int
+    channels: int
+    format: int
+    dropped_frames: int
+    flags: int
+    block_samples: int
+    order: int
+    ratio_permille: int
+    floor: int
+    gap: int
+    max_width: int
+    max_events: int
+    listed: int
+    nonfinite: int
+    events_total: int
+    ch: list = field(default_factory=list)       # [ClickChannel], one per channel
+    events: list = field(default_factory=list)   # [ClickEvent], the file's first `listed` events by (start, channel)
+    error: Optional["ReplayGainError"] = None    # why there are no numbers; every other field is then zero
+
+    def _has(self, bit) -> bool:
+        return bool(self.flags & bit)
+
+    @property
+    def complete(self) -> bool:
+        return self._has(_capi.CK_COMPLETE)
+
+    @property
+    def truncated(self) -> bool:
+        return self._has(_capi.CK_TRUNCATED)
+
+    @property
+    def clicks(self) -> int:
+        return sum(c.clicks for c in self.ch)
+
+    @property
+    def bursts(self) -> int:
+        return sum(c.bursts for c in self.ch)
+
+    @property
+    def first_click(self):
+        """(sample, channel) of the earliest click of any channel, or None."""
+        have = [(c.first_click, i) for i, c in enumerate(self.ch) if c.clicks]
+        return min(have) if have else None
+
+    @property
+    def strongest_click(self):
+        """(strength_permille, sample, channel) of the strongest click of any channel (the earliest on a tie), or None."""
+        have = [(-c.strongest_permille, c.strongest_at, i) for i, c in enumerate(self.ch) if c.clicks]
+        if not have:
+            return None
+        s, at, i = min(have)
+        return -s, at, i
+
+
+def clicks_from_record(r, events=(), error=None) -> Clicks:
+    """A Clicks from an rg_clicks_result and its row of rg_clicks_event."""
+    names = ("flagged", "clicks", "bursts", "widest", "first_click", "strongest_at", "strongest_permille", "fallback_blocks", "median_max")
+    ch = [ClickChannel(*[int(getattr(r.ch[c], f)) for f in names]) for c in range(min(int(r.channels), _capi.CK_MAX_CHANNELS))]
+    evs = [ClickEvent(int(e.start), int(e.width), int(e.channel), "click" if e.kind == _capi.CK_KIND_CLICK else "burst", int(e.peak_at),
+                      int(e.strength_permille)) for e in list(events)[:int(r.listed)]]
+    return Clicks(int(r.frames), int(r.sample_rate), int(r.channels), int(r.format), int(r.dropped_frames), int(r.flags), int(r.block_samples),
+                  int(r.order), int(r.ratio_permille), int(r.floor), int(r.gap), int(r.max_width), int(r.max_events), int(r.listed), int(r.nonfinite),
+                  int(r.events), ch, evs, error)
+
+
 def _fingerprint_opts(block, probes, radius, max_ber_permille):
     """rg_fingerprint_opts, or NULL (the header's defaults) when all are None; a None field is its default."""
     if block is None and probes is None and radius is None and max_ber_permille is None:
@@ -2288,6 +2426,39 @@ class Analyzer:
         ([stream bytes], [FlacEncodeRecord], offsets); route 0 = the serial host twin, route 1 = the arena copied to this GPU
         and the analyse, layout and write kernels."""
         return flac_encode_arena(self._ctx, route, descs, bps, arena, block_size, max_lpc_order)
+
+    def _clicks_call(self, files, block_samples, order, ratio_permille, floor, gap, max_width, max_events):
+        paths, out = self._file_args(files, _capi.ClicksRecord)
+        k, rows = _clicks_rows(len(files), max_events)
+        opts = _clicks_opts(block_samples, order, ratio_permille, floor, gap, max_width, max_events)
+        self._check(self._lib.rg_clicks(self._ctx, paths, len(files), opts, out, rows))
+        return out, rows, k
+
+    def clicks(self, files, block_samples=None, order=None, ratio_permille=None, floor=None, gap=None, max_width=None, max_events=None):
+        """rg_clicks: `files` (WAV, FLAC or MPEG Layer III) decoded by the route the analysis uses and, from the PCM where it lies
+        on this GPU, every channel predicted block by block by the FLAC encoder's linear model; samples whose residual stands
+        `ratio_permille` / 1000 times above the median residual around them make events, narrow events are clicks -> [Clicks],
+        each with its channels and the file's first `max_events` events.  A file that takes no part carries its ReplayGainError in
+        `.error`."""
+        out, rows, k = self._clicks_call(files, block_samples, order, ratio_permille, floor, gap, max_width, max_events)
+        return [clicks_from_record(r, rows[i * k:(i + 1) * k], err) for i, (r, err) in enumerate(self._file_records(out, len(files)))]
+
+    def clicks_raw(self, files, block_samples=None, order=None, ratio_permille=None, max_events=None):
+        """clicks' rg_clicks_result array as the C call left it, and the event rows' bytes behind it (tests compare routes byte for
+        byte)."""
+        out, rows, k = self._clicks_call(files, block_samples, order, ratio_permille, None, None, None, max_events)
+        return bytes(out)[:len(files) * C.sizeof(_capi.ClicksRecord)], bytes(rows)[:len(files) * k * C.sizeof(_capi.ClicksEvent)]
+
+    def clicks_arena(self, route: int, descs, arena, block_samples=None, order=None, ratio_permille=None, floor=None, gap=None, max_width=None,
+                     max_events=None):
+        """rg_clicks_arena, the seam of the click kernels: the tracks `descs` describe in the host arena `arena` -> ([ClicksRecord],
+        the event rows); route 0 = the serial host twin, route 1 = the arena copied to this GPU and the kernels, route 2 = the
+        kernels' tile and fold code on one host lane."""
+        return clicks_arena(self._ctx, route, descs, arena, block_samples, order, ratio_permille, floor, gap, max_width, max_events)
+
+    @staticmethod
+    def clicks_kernel_shape(block_samples: int):
+        return clicks_kernel_shape(block_samples)
 
     def _same_recording_call(self, files, block, probes, radius, max_ber_permille, codes_cap):
         paths, out = self._file_args(files, _capi.FingerprintRecord)
