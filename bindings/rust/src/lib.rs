@@ -549,6 +549,160 @@ pub mod replaygain {
     }
 }
 
+/// The null test of `include/mp3rgain_amd_compare.h`: how does copy b of a recording relate to the reference copy a?  The copies are
+/// lined up to the sample on the GPU (a cross-correlation at every lag within a radius of a coarse hint, which comes from the
+/// [`fingerprint`] match or from the caller), one gain is fitted, and what is left is sized per block: identical samples some
+/// frames apart, the same master after a gain change and a re-dither, a lossy copy, another recording.  The unit of work is a pair
+/// of files.  The definitions are a convention of that header, held to no other null-test tool; `lock_permille` and
+/// `requant_millilsb2` are measured on synthetic material (`tests/golden/compare_measured.json`).  A module of its own, as
+/// [`stereo`] is.  `tests/test_rust_compare_layout.py` compares these declarations with the header.
+pub mod compare {
+    use super::ffi::RgCtx;
+    use std::os::raw::{c_char, c_int};
+
+    pub const CMP_COMPLETE: u32 = 1;
+    pub const CMP_IDENTICAL: u32 = 2;
+    pub const CMP_SHIFTED: u32 = 4;
+    pub const CMP_LENGTHS: u32 = 8;
+    pub const CMP_INVERTED: u32 = 16;
+    pub const CMP_NONFINITE: u32 = 32;
+    pub const CMP_LOCKED: u32 = 64;
+    pub const CMP_AT_EDGE: u32 = 128;
+    pub const CMP_DRIFT: u32 = 256;
+    pub const CMP_SAME_MASTER: u32 = 512;
+    pub const CMP_DIFFERS: u32 = 1024;
+    pub const CMP_UNRELATED: u32 = 2048;
+    pub const CMP_RATE: u32 = 4096;
+    pub const CMP_NO_OVERLAP: u32 = 8192;
+    pub const CMP_NO_COARSE: u32 = 16384;
+    pub const CMP_CHANNELS_DIFFER: u32 = 32768;
+    pub const CMP_RAW: u32 = 65536;
+    pub const CMP_ALIGN_FINGERPRINT: u32 = 0;
+    pub const CMP_ALIGN_HINT: u32 = 1;
+    pub const CMP_MAX_CHANNELS: usize = 8;
+    pub const CMP_MAX_RADIUS: u32 = 2047;
+    pub const CMP_MAX_COARSE_RADIUS: u32 = 2047;
+    pub const CMP_MAX_SEGMENTS: u32 = 16;
+    pub const CMP_MAX_BLOCK_FRAMES: u32 = 384000;
+    pub const CMP_DEFAULT_COARSE_RADIUS: u32 = 512;
+    pub const CMP_DEFAULT_RADIUS: u32 = 1024;
+    pub const CMP_DEFAULT_SEGMENTS: u32 = 4;
+    pub const CMP_DEFAULT_SEGMENT_FRAMES: u32 = 262144;
+    pub const CMP_DEFAULT_DRIFT_FRAMES: u32 = 1;
+    pub const CMP_DEFAULT_LOCK_PERMILLE: u32 = 606;
+    pub const CMP_DEFAULT_REQUANT_MILLILSB2: u32 = 18156;
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_compare_pair`: `a` is the reference copy; `hint` in frames, b[n + hint] is expected beside a[n]
+    pub struct RgComparePair {
+        pub a: u32,
+        pub b: u32,
+        pub hint: i64,
+    }
+
+    #[derive(Clone, Copy, Debug)]
+    #[repr(C)]
+    /// `rg_compare_opts`: `block_frames` 0 = the sample rate, `segment_frames` 0 = the whole overlap; a null pointer means the defaults
+    pub struct RgCompareOpts {
+        pub align: u32,
+        pub coarse_radius: u32,
+        pub radius: u32,
+        pub segments: u32,
+        pub segment_frames: u32,
+        pub block_frames: u32,
+        pub drift_frames: u32,
+        pub lock_permille: u32,
+        pub requant_millilsb2: u32,
+    }
+
+    impl Default for RgCompareOpts {
+        fn default() -> Self {
+            RgCompareOpts {
+                align: CMP_ALIGN_FINGERPRINT,
+                coarse_radius: CMP_DEFAULT_COARSE_RADIUS,
+                radius: CMP_DEFAULT_RADIUS,
+                segments: CMP_DEFAULT_SEGMENTS,
+                segment_frames: CMP_DEFAULT_SEGMENT_FRAMES,
+                block_frames: 0,
+                drift_frames: CMP_DEFAULT_DRIFT_FRAMES,
+                lock_permille: CMP_DEFAULT_LOCK_PERMILLE,
+                requant_millilsb2: CMP_DEFAULT_REQUANT_MILLILSB2,
+            }
+        }
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_compare_block`: one block of the overlap, summed over the channels; `first_diff` all ones = no sample differs
+    pub struct RgCompareBlock {
+        pub aa: i64,
+        pub bb: i64,
+        pub ab: i64,
+        pub first_diff: u64,
+        pub equal: u32,
+        pub max_diff: u32,
+        pub frames: u32,
+        pub reserved: u32,
+    }
+
+    #[derive(Clone, Copy, Debug, Default)]
+    #[repr(C)]
+    /// `rg_compare_result`: b[n + lag] lies beside a[n]; `null_db`, `null_unity_db` and `worst_block_db` may be infinite
+    pub struct RgCompareResult {
+        pub status: i32,
+        pub flags: u32,
+        pub a: u32,
+        pub b: u32,
+        pub frames_a: u64,
+        pub frames_b: u64,
+        pub sample_rate: u32,
+        pub channels: u32,
+        pub format_a: u32,
+        pub format_b: u32,
+        pub dropped_a: u32,
+        pub dropped_b: u32,
+        pub block_frames: u32,
+        pub radius: u32,
+        pub segments: u32,
+        pub locked_segments: u32,
+        pub polarity: i32,
+        pub max_diff: u32,
+        pub hint: i64,
+        pub lag: i64,
+        pub seg_lag_min: i64,
+        pub seg_lag_max: i64,
+        pub overlap: u64,
+        pub a_head: u64,
+        pub a_tail: u64,
+        pub b_head: u64,
+        pub b_tail: u64,
+        pub blocks: u32,
+        pub differing_blocks: u32,
+        pub worst_block: u32,
+        pub reserved: u32,
+        pub equal: u64,
+        pub first_diff: u64,
+        pub nonfinite: u64,
+        pub aa: i64,
+        pub bb: i64,
+        pub ab: i64,
+        pub lock: f64,
+        pub gain_db: f64,
+        pub null_unity_db: f64,
+        pub null_db: f64,
+        pub residual_lsb2: f64,
+        pub worst_block_db: f64,
+        pub gain_min_db: f64,
+        pub gain_max_db: f64,
+    }
+
+    extern "C" {
+        pub fn rg_compare(ctx: *mut RgCtx, paths: *const *const c_char, n: usize, pairs: *const RgComparePair, n_pairs: usize, opts: *const RgCompareOpts,
+                          out: *mut RgCompareResult, blocks_out: *mut RgCompareBlock, blocks_per_pair: usize, lag_sums: *mut i64) -> c_int;
+    }
+}
+
 /// The click scan of `include/mp3rgain_amd_clicks.h`: are there clicks or glitches in each of these WAV, FLAC or MP3 files?  Every
 /// channel is predicted block by block by the FLAC encoder's linear model on the GPU; a sample whose residual stands far above the
 /// median residual around it is flagged, flagged samples close together make an event, a narrow event is a click and a wide one a

@@ -476,6 +476,89 @@ STEREO_SYMBOLS = [
     ("rg_stereo_rate", _int, [_vp, _sz, _u64, _u32, _u32, _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz), _P(_u64), _P(_u64)]),
 ]
 
+# include/mp3rgain_amd_compare.h (null test of two tracks: lag rows around a hint, the pick, aligned moments per block)
+(CMP_COMPLETE, CMP_IDENTICAL, CMP_SHIFTED, CMP_LENGTHS, CMP_INVERTED, CMP_NONFINITE, CMP_LOCKED, CMP_AT_EDGE, CMP_DRIFT, CMP_SAME_MASTER,
+ CMP_DIFFERS, CMP_UNRELATED, CMP_RATE, CMP_NO_OVERLAP, CMP_NO_COARSE, CMP_CHANNELS_DIFFER, CMP_RAW) = (1 << k for k in range(17))
+CMP_ALIGN_FINGERPRINT, CMP_ALIGN_HINT = 0, 1
+CMP_MAX_CHANNELS, CMP_MAX_RADIUS, CMP_MAX_COARSE_RADIUS, CMP_MAX_SEGMENTS, CMP_MAX_BLOCK_FRAMES, CMP_MAX_HINT = 8, 2047, 2047, 16, 384000, 1 << 32
+(CMP_DEFAULT_COARSE_RADIUS, CMP_DEFAULT_RADIUS, CMP_DEFAULT_SEGMENTS, CMP_DEFAULT_SEGMENT_FRAMES, CMP_DEFAULT_DRIFT_FRAMES,
+ CMP_DEFAULT_LOCK_PERMILLE, CMP_DEFAULT_REQUANT_MILLILSB2) = 512, 1024, 4, 262144, 1, 606, 18156
+CMP_NONE = (1 << 64) - 1  # first_diff: no sample differs
+
+
+class ComparePair(C.Structure):  # rg_compare_pair
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("hint", C.c_int64)]
+
+
+class CompareOpts(C.Structure):  # rg_compare_opts
+    _fields_ = [("align", C.c_uint32), ("coarse_radius", C.c_uint32), ("radius", C.c_uint32), ("segments", C.c_uint32), ("segment_frames", C.c_uint32),
+                ("block_frames", C.c_uint32), ("drift_frames", C.c_uint32), ("lock_permille", C.c_uint32), ("requant_millilsb2", C.c_uint32)]
+
+
+class CompareBlock(C.Structure):  # rg_compare_block
+    _fields_ = [("aa", C.c_int64), ("bb", C.c_int64), ("ab", C.c_int64), ("first_diff", C.c_uint64), ("equal", C.c_uint32), ("max_diff", C.c_uint32),
+                ("frames", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CompareRecord(C.Structure):  # rg_compare_result
+    _fields_ = [
+        ("status", C.c_int32),
+        ("flags", C.c_uint32),
+        ("a", C.c_uint32),
+        ("b", C.c_uint32),
+        ("frames_a", C.c_uint64),
+        ("frames_b", C.c_uint64),
+        ("sample_rate", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("format_a", C.c_uint32),
+        ("format_b", C.c_uint32),
+        ("dropped_a", C.c_uint32),
+        ("dropped_b", C.c_uint32),
+        ("block_frames", C.c_uint32),
+        ("radius", C.c_uint32),
+        ("segments", C.c_uint32),
+        ("locked_segments", C.c_uint32),
+        ("polarity", C.c_int32),
+        ("max_diff", C.c_uint32),
+        ("hint", C.c_int64),
+        ("lag", C.c_int64),
+        ("seg_lag_min", C.c_int64),
+        ("seg_lag_max", C.c_int64),
+        ("overlap", C.c_uint64),
+        ("a_head", C.c_uint64),
+        ("a_tail", C.c_uint64),
+        ("b_head", C.c_uint64),
+        ("b_tail", C.c_uint64),
+        ("blocks", C.c_uint32),
+        ("differing_blocks", C.c_uint32),
+        ("worst_block", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("equal", C.c_uint64),
+        ("first_diff", C.c_uint64),
+        ("nonfinite", C.c_uint64),
+        ("aa", C.c_int64),
+        ("bb", C.c_int64),
+        ("ab", C.c_int64),
+        ("lock", C.c_double),
+        ("gain_db", C.c_double),
+        ("null_unity_db", C.c_double),
+        ("null_db", C.c_double),
+        ("residual_lsb2", C.c_double),
+        ("worst_block_db", C.c_double),
+        ("gain_min_db", C.c_double),
+        ("gain_max_db", C.c_double),
+    ]
+
+
+COMPARE_SYMBOLS = [
+    ("rg_compare_error", C.c_char_p, [_vp, _sz]),
+    ("rg_compare", _int, [_vp, _P(C.c_char_p), _sz, _P(ComparePair), _sz, _P(CompareOpts), _P(CompareRecord), _P(CompareBlock), _sz, _P(C.c_int64)]),
+    ("rg_compare_arena", _int, [_vp, _int, _sz, _P(TrackDesc), _sz, _P(ComparePair), _P(CompareOpts), _vp, _sz, _P(CompareRecord), _P(CompareBlock), _sz,
+                                _P(C.c_int64)]),
+    ("rg_compare_kernel_shape", _int, [_u32, _u32, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("rg_compare_rate", _int, [_vp, _sz, _sz, _u64, _u32, _P(CompareOpts), _sz, _u32, _u32, _dbl, _P(_dbl), _P(_dbl), _P(_dbl), _P(_sz), _P(_u64), _P(_u64)]),
+]
+
 # include/mp3rgain_amd_flacenc.h (FLAC encoder: LPC search, exact Rice sizing)
 FLAC_ENC_DEFAULT_BLOCK, FLAC_ENC_DEFAULT_LPC, FLAC_ENC_MAX_LPC, FLAC_ENC_VERIFY = 4096, 8, 12, 1
 FLAC_ENC_COMPLETE, FLAC_ENC_VERIFIED, FLAC_ENC_WRITTEN, FLAC_ENC_VERIFY_FAILED = 1, 2, 4, 8
@@ -852,7 +935,7 @@ def load():
         if not standalone and "torch" not in sys.modules and importlib.util.find_spec("torch") is not None:
             import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + STEREO_SYMBOLS + CLICKS_SYMBOLS + FLACENC_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS + RESAMPLE_SYMBOLS:
+        for name, res, args in SYMBOLS + R128_SYMBOLS + RIP_SYMBOLS + STATS_SYMBOLS + SPECTRUM_SYMBOLS + DR_SYMBOLS + STEREO_SYMBOLS + COMPARE_SYMBOLS + CLICKS_SYMBOLS + FLACENC_SYMBOLS + ANCESTRY_SYMBOLS + FINGERPRINT_SYMBOLS + TEMPO_SYMBOLS + KEY_SYMBOLS + RESAMPLE_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

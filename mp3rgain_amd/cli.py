@@ -93,6 +93,9 @@ class Options:  # src/main.rs:65-96
     encode_lpc: Optional[int] = None  # with --encode (--encode-lpc N): the largest LPC order tried
     encode_block: Optional[int] = None  # with --encode (--encode-block N): the block size
     encode_verify: bool = True  # --no-encode-verify clears it
+    compare: bool = False  # this façade only (--compare REF FILE...): a null test of every file against the first
+    compare_radius: Optional[int] = None  # with --compare (--compare-radius N): how far from the hint the fine lag is looked for, in samples
+    compare_hint: Optional[int] = None  # with --compare (--compare-hint FRAMES): the expected lag of every file, instead of the fingerprint match
     stereo_radius: Optional[int] = None  # with --stereo (--stereo-radius N): the largest channel delay looked for, in samples
     clicks: bool = False  # this façade only (--clicks): are there clicks or glitches in each file?  Residual of a linear predictor against its local median
     click_ratio: Optional[float] = None  # with --clicks (--click-ratio X): a sample is flagged when its residual is more than X times the scale
@@ -235,6 +238,12 @@ def parse_args(args: List[str], out, err) -> Options:
             o.click_block = _parse_int(need("--click-block", "--click-block requires an argument"), "invalid block length", 32, signed=False)
         elif arg == "--click-list":
             o.click_list = _parse_int(need("--click-list", "--click-list requires an argument"), "invalid number of events", 32, signed=False)
+        elif arg == "--compare":  # not in the reference: a command of its own, like --stereo
+            o.compare = True
+        elif arg == "--compare-radius":
+            o.compare_radius = _parse_int(need("--compare-radius", "--compare-radius requires an argument"), "invalid radius", 32, signed=False)
+        elif arg == "--compare-hint":
+            o.compare_hint = _parse_int(need("--compare-hint", "--compare-hint requires an argument"), "invalid hint", 64, signed=True)
         elif arg == "--stereo-radius":
             o.stereo_radius = _parse_int(need("--stereo-radius", "--stereo-radius requires an argument"), "invalid radius", 32, signed=False)
         elif arg == "--decoder":  # not in the reference: see the module docstring
@@ -426,6 +435,24 @@ def parse_args(args: List[str], out, err) -> Options:
                                         ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
         if others:
             raise CliError(f"--stereo is a command of its own and cannot be combined with {', '.join(others)}")
+    for name, v in (("--compare-radius", o.compare_radius), ("--compare-hint", o.compare_hint)):
+        if v is not None and not o.compare:
+            raise CliError(f"{name} requires --compare")
+    if o.compare_radius is not None and not 0 <= o.compare_radius <= _capi.CMP_MAX_RADIUS:
+        raise CliError(f"--compare-radius takes 0 to {_capi.CMP_MAX_RADIUS} samples: {o.compare_radius}")
+    if o.compare_hint is not None and abs(o.compare_hint) > _capi.CMP_MAX_HINT:
+        raise CliError(f"--compare-hint takes at most 2^32 frames either way: {o.compare_hint}")
+    if o.compare:
+        others = [name for name, on in (("--verify", o.verify), ("--rip", o.rip), ("--stats", o.stats), ("--spectrum", o.spectrum), ("--dr", o.dr),
+                                        ("--ancestry", o.ancestry), ("--duplicates", o.duplicates), ("--tempo", o.tempo), ("--key", o.key),
+                                        ("--stereo", o.stereo), ("--clicks", o.clicks), ("--encode", o.encode), ("--r128", o.r128),
+                                        ("-x", o.max_amplitude_only), ("-r", o.track_gain), ("-a", o.album_gain), ("-u", o.undo),
+                                        ("-g", o.gain_steps is not None), ("-l", o.channel_gain is not None),
+                                        ("-s", o.stored_tag_mode in ("check", "delete"))) if on]
+        if others:
+            raise CliError(f"--compare is a command of its own and cannot be combined with {', '.join(others)}")
+        if len(o.files) < 2:
+            raise CliError("--compare takes the reference copy and at least one file to hold against it")
     given = [name for name, on in (("--click-ratio", o.click_ratio is not None), ("--click-order", o.click_order is not None),
                                    ("--click-block", o.click_block is not None), ("--click-list", o.click_list is not None)) if on]
     if given and not o.clicks:
@@ -789,6 +816,8 @@ class Cli:
             return self.cmd_key()
         if o.stereo:
             return self.cmd_stereo()
+        if o.compare:
+            return self.cmd_compare()
         if o.clicks:
             return self.cmd_clicks()
         if o.encode:
@@ -1475,6 +1504,71 @@ class Cli:
             shown = next((w for w in named[1:] if w in r.verdicts), "stereo")
             notes = [w for w in r.verdicts if w not in ("stereo", "incomplete", shown)] + ([f"{r.dropped_frames} frames dropped"] if r.dropped_frames else [])
             self.p(f"{line}  {_name(file)}" + (f"  [{', '.join(notes)}]" if notes else ""))
+        return 1 if failed else 0
+
+    # ---- --compare (not in the reference): a null test of every file against the first.  On the GPU ------------------------------
+    def cmd_compare(self) -> int:
+        """Every file decoded by the route the analysis uses; every file but the first lined up with the first to the sample
+        (the coarse lag from the fingerprint match, or --compare-hint for all of them), one gain fitted and what is left sized, on
+        the first GPU (rg_compare).  Text: a line per file but the first, `identical  name`, `identical samples, starts 588 samples
+        later, 1176 shorter at the end  name`, `same master  (gain -3.01 dB, residual 0.31 LSB^2)  name`, `same recording, differs
+        (null -23.4 dB after +0.2 dB, worst 1:02-1:03 at -9.1 dB, first difference at 0:00.013)  name`, `same recording, drifts
+        (...)  name`, `inverted copy, ...  name`, `not the same recording  (best correlation 0.03)  name`, `different sample rate:
+        not compared  name`, with the other verdicts in brackets.  The definitions are a convention of this project, held to no
+        other tool.  A report: exit status 1 only when a file fails or has dropped frames.  JSON carries every field of the
+        record.  TSV, no header: a row per file `file, verdicts, lag, polarity, lock, gain dB, null dB, residual LSB^2, overlap,
+        a head, a tail, b head, b tail, differing blocks, first difference, max difference, sample rate, channels, dropped a,
+        dropped b` (a failing file: `file, error text`)."""
+        o = self.o
+        devs = os.environ.get("MP3RGAIN_AMD_DEVICES")
+        with rgmod.Analyzer(int(devs.split(",")[0]) if devs else 0) as an:
+            recs = an.compare(o.files, hints=o.compare_hint, radius=o.compare_radius)
+        return self.print_compare(o.files[1:], recs)
+
+    def print_compare(self, files, recs) -> int:
+        """The report of cmd_compare: `recs[k]` is files[k] against the reference copy."""
+        o = self.o
+        failed = sum(1 for r in recs if r.error is not None or not r.complete)
+        num = lambda x: x if math.isfinite(x) else None  # noqa: E731  (JSON has no infinity)
+        if o.output_format == "json":
+            out = []
+            for file, r in zip(files, recs):
+                d = {"file": str(file), "status": "error" if r.error is not None else "success"}
+                if r.error is not None:
+                    d["error"] = str(r.error)
+                else:
+                    d.update(verdicts=r.verdicts, reading=r.reading, complete=r.complete)
+                    for f in rgmod._COMPARE_FIELDS:
+                        v = getattr(r, f)
+                        d[f] = num(v) if isinstance(v, float) else v
+                    d["first_diff"] = None if r.first_diff == _capi.CMP_NONE else r.first_diff
+                out.append(d)
+            _print_json(self.out, reference=str(o.files[0]), files=out, summary=_summary(len(files), len(files) - failed, failed, False))
+            return 1 if failed else 0
+        if o.output_format == "tsv":
+            for file, r in zip(files, recs):
+                if r.error is not None:
+                    self.p(f"{_name(file)}\t{r.error}")
+                    continue
+                first = "" if r.first_diff == _capi.CMP_NONE else str(r.first_diff)
+                self.p(f"{_name(file)}\t{','.join(r.verdicts)}\t{r.lag}\t{r.polarity}\t{r.lock:.4f}\t{r.gain_db:.3f}\t{r.null_db:.2f}\t{r.residual_lsb2:.4f}\t"
+                       f"{r.overlap}\t{r.a_head}\t{r.a_tail}\t{r.b_head}\t{r.b_tail}\t{r.differing_blocks}\t{first}\t{r.max_diff}\t{r.sample_rate}\t"
+                       f"{r.channels}\t{r.dropped_a}\t{r.dropped_b}")
+            return 1 if failed else 0
+        if self.talk:
+            self.p(f"mp3rgain null test of {len(files)} file(s) against {_name(o.files[0])}: lag, gain and what is left"
+                   " (a convention of this project, held to no other tool)")
+            self.p()
+        shown = ("different sample rate", "no overlap", "identical", "same master", "differs", "unrelated", "inverted", "drifts", "shifted", "lengths differ",
+                 "incomplete")
+        for file, r in zip(files, recs):
+            if r.error is not None:
+                self.e(f"{_name(file)} - {r.error}")
+                continue
+            notes = [w for w in r.verdicts if w not in shown]
+            dropped = r.dropped_a + r.dropped_b
+            notes += [f"{dropped} frames dropped"] if dropped else []
+            self.p(f"{r.reading}  {_name(file)}" + (f"  [{', '.join(notes)}]" if notes else ""))
         return 1 if failed else 0
 
     # ---- --encode (not in the reference): WAV and FLAC files to FLAC on the GPU ---------------------------------------------------
@@ -2305,6 +2399,13 @@ def print_usage(out):  # src/main.rs:2261-2346, shortened to the option table
         "            `channels out of phase`, `one-sided`, `near mono`, `mono file`.  A convention of this project, tried on synthetic",
         "            material only and held to no other tool.  JSON carries every field of the record.  Exit status 1 only for a file",
         "            that fails or has dropped frames",
+        "--compare   A null test: every FILE held against the first (the reference copy).  On the GPU (WAV, FLAC, MP3): the copies lined up",
+        "            to the sample, one gain fitted, what is left sized per second.  A line per file: `identical  name`, `identical samples,",
+        "            starts 588 samples later  name`, `same master  (gain -3.01 dB, residual 0.31 LSB^2)  name`, `same recording, differs",
+        "            (null -23.4 dB after +0.2 dB, worst 1:02-1:03 at -9.1 dB, first difference at 0:00.013)  name`, `not the same recording`.",
+        "            A convention of this project, held to no other tool; exit status 1 only for a failing file or dropped frames",
+        "--compare-radius <N>  With --compare: how far from the coarse lag the fine lag is looked for, in samples (default 1024; 0 to 2047)",
+        "--compare-hint <FRAMES>  With --compare: the expected lag of every file, instead of the fingerprint match",
         "--stereo-radius <N>  With --stereo: the largest delay looked for, in samples (default 64; 0 to 255)",
         "--encode    Encode the files (WAV with 8, 16 or 24-bit integer samples, FLAC) to FLAC on the GPU, into <--encode-dir>/<stem>.flac:",
         "            LPC search at every even order, exact Rice sizing of every candidate, mid/side for two channels.  Unless",

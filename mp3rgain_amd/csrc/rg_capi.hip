@@ -325,6 +325,7 @@ extern "C" void rg_destroy(rg_ctx *c) {
     c->d_spectrum.release();
     c->d_dr.release();
     c->d_stereo.release();
+    c->d_compare.release();
     c->d_clicks.release();
     c->d_flacenc.release();
     c->d_flacenc_out.release();

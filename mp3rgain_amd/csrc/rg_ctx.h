@@ -181,6 +181,7 @@ struct rg_ctx {
     // were the source of H2D copies cost more than decoding them (munmap of such pages: 0.4 ms per MB)
     void *file_pool = nullptr;
     std::vector<std::string> file_errors;    // rg_analyze_tracks: message per file of the last call
+    std::vector<std::string> pair_errors;    // rg_compare: message per pair of the last call, for a pair whose files both loaded (rg_compare_error)
     void (*file_pool_free)(void *) = nullptr;
     int gpu_mp3_decode = 3;                  // tuning key 6: 0 = host decoder, 1 = stages B-E of MP3 decoding run on the device,
                                              // 2 = scalefactors + Huffman too, 3 (default) = side-information parsing too: the host
@@ -197,6 +198,7 @@ struct rg_ctx {
     DevBuf<unsigned char> d_spectrum;        // rg_spectrum.hip: [tables | per run plane records, tile -> plane | tile records | skipped | per-plane results]
     DevBuf<unsigned char> d_dr;              // rg_dr.hip: [plane records | piece -> plane | piece records | block records | per-plane results] of one launch
     DevBuf<unsigned char> d_stereo;          // rg_stereo.hip: [track records | piece -> track | tile -> track | piece records | lag sums | per-track results] of one launch
+    DevBuf<unsigned char> d_compare;         // rg_compare.hip: [pair records | tile -> pair | lag rows] of the lag launch, then [pair records | piece -> pair | piece records | block rows | per-pair totals] of the moments launch
     DevBuf<unsigned char> d_clicks;          // rg_clicks.hip: [plane records | tile -> plane | tile records | events before a tile | listed tiles | count | per-plane results | event slots] of one launch
     DevBuf<unsigned char> d_flacenc;         // rg_flacenc.hip: [stream records | frame records | frame offsets | per-stream layout | fail flag] of one call
     DevBuf<unsigned char> d_flacenc_out;     // the streams it wrote

@@ -27,6 +27,7 @@
 #include "rg_resample.h"
 #include "rg_stats.h"
 #include "rg_stereo.h"
+#include "rg_compare.h"
 #include "rg_flacenc.h"
 
 using namespace rgf;
@@ -888,6 +889,179 @@ extern "C" int rg_same_recording(rg_ctx *c, const char *const *paths, size_t n, 
         return RG_OK;
     });
 }
+
+// ---- rg_compare: the fingerprint kernels and the match kernel for the coarse hints of the requested pairs, then the kernels of
+// rg_compare.hip; the pick and the finish are host arithmetic on what comes back (rg_cmp_pick, rg_cmp_fill) ----------------------
+// The unit of work is a pair, and both files of a pair must lie in the arena together: the whole list is one group.
+namespace {
+struct CmpFile {  // what mark_record takes: a file that fails, fails its pairs
+    int32_t status;
+};
+}  // namespace
+
+// the coarse hints of the pairs whose files both loaded: hints[p] <- 512 * lag, brought to "b behind a"; coarse[p] <- 0 when the
+// match skipped the pair
+static int compare_coarse(rg_ctx *c, const FileGroup &g, const std::vector<rg_track_desc> &fdesc, const std::vector<char> &loaded, const rg_compare_pair *pairs,
+                          size_t n_pairs, const rg_compare_opts &o, std::vector<int64_t> *hints, std::vector<char> *coarse) {
+    const size_t n = fdesc.size();
+    std::vector<RgFpTrack> tracks(n + 1);
+    std::vector<size_t> track_of(n, SIZE_MAX);
+    size_t m = 0;
+    char err[kPcmErrLen] = "";
+    for (size_t i = 0; i < n; ++i) {
+        if (!loaded[i]) continue;
+        const int rc = rg_fp_track(i, fdesc[i], g.arena_bytes, &tracks[m], err, sizeof err);
+        if (rc == RG_ERR_FORMAT) continue;  // no fingerprint of this file: its pairs get no coarse hint
+        if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
+        track_of[i] = m++;
+    }
+    if (!m) return RG_OK;
+    uint64_t fmt_tile[4], codes = 0;
+    (void)rg_fp_plan(tracks.data(), m, fmt_tile, 0, 0);
+    for (size_t t = 0; t < m; ++t) codes += tracks[t].frames ? tracks[t].frames - 1u : 0u;
+    int rc = fp_codes_grow(c, 0, (size_t)codes + 4, c->file_stream());
+    if (rc != RG_OK) return rc;
+    std::vector<uint32_t> nonfinite(m);
+    rc = rg_fprint_device(c, c->d_arena.p, tracks.data(), m, c->d_fp_codes.p, nullptr, nonfinite.data(), c->file_stream());
+    if (rc != RG_OK) return rc;
+    rg_fingerprint_opts fo;
+    (void)rg_fp_options(nullptr, &fo, err, sizeof err);
+    fo.radius = o.coarse_radius;
+    std::vector<RgFpPair> compared;
+    std::vector<rg_fingerprint_pair_record> records(n_pairs + 1, rg_fingerprint_pair_record{0u, 0u, 0, RG_FP_PAIR_SKIPPED});
+    std::vector<char> probe_b(n_pairs, 0);
+    for (size_t p = 0; p < n_pairs; ++p) {
+        const size_t ta = track_of[pairs[p].a], tb = track_of[pairs[p].b];
+        if (ta == SIZE_MAX || tb == SIZE_MAX || fdesc[pairs[p].a].sample_rate != fdesc[pairs[p].b].sample_rate) continue;
+        const RgFpTrack &A = tracks[ta], &B = tracks[tb];
+        const uint32_t ka = A.frames ? A.frames - 1u : 0u, kb = B.frames ? B.frames - 1u : 0u;
+        if (!A.rate_ok || !B.rate_ok || ka < fo.block || kb < fo.block) continue;
+        probe_b[p] = kb < ka;  // the probe side is the one with fewer codes, on a tie the reference copy
+        compared.push_back(probe_b[p] ? RgFpPair{B.codes_at, A.codes_at, kb, ka, (uint32_t)p, RG_FP_PAIR_COMPARED | RG_FP_PAIR_PROBE_J}
+                                      : RgFpPair{A.codes_at, B.codes_at, ka, kb, (uint32_t)p, RG_FP_PAIR_COMPARED});
+    }
+    if (!compared.empty()) {
+        rc = rg_fprint_match_device(c, c->d_fp_codes.p, compared, fo, records.data(), c->file_stream());
+        if (rc != RG_OK) return rc;
+    }
+    for (size_t p = 0; p < n_pairs; ++p) {
+        if ((records[p].flags & RG_FP_PAIR_SKIPPED) || !records[p].bits) continue;
+        (*coarse)[p] = 1;
+        (*hints)[p] = (int64_t)RG_FP_HOP * records[p].lag * (probe_b[p] ? -1 : 1);
+    }
+    return RG_OK;
+}
+
+static int compare_group(rg_ctx *c, const char *const *paths, size_t n, const rg_compare_pair *pairs, size_t n_pairs, const rg_compare_opts &o,
+                         rg_compare_result *out, rg_compare_block *blocks_out, size_t blocks_per_pair, int64_t *lag_sums) {
+    FileGroup g(c, paths, 0, n);
+    std::vector<CmpFile> files(n + 1);
+    std::vector<rg_track_desc> fdesc(n);
+    std::vector<char> loaded(n, 0);
+    std::vector<uint32_t> dropped(n, 0);
+    const auto add = [&](size_t k, size_t i, char *err) -> int {
+        const int rc = rg_pcm_check_format(i, g.descs[k], RG_CMP_MAX_CHANNELS, "the null test takes", err, kPcmErrLen);
+        if (rc != RG_OK) return rc;
+        fdesc[i] = g.descs[k];
+        loaded[i] = 1;
+        dropped[i] = dropped_frames(g, k);
+        return RG_OK;
+    };
+    const auto finish = [&]() -> int {
+        std::vector<int64_t> hints(n_pairs, 0);
+        std::vector<char> coarse(n_pairs, 0);
+        if (o.align == RG_CMP_ALIGN_HINT) {
+            for (size_t p = 0; p < n_pairs; ++p) hints[p] = pairs[p].hint;
+        } else {
+            const int rc = compare_coarse(c, g, fdesc, loaded, pairs, n_pairs, o, &hints, &coarse);
+            if (rc != RG_OK) return rc;
+        }
+        std::vector<RgCmpPair> plan;
+        std::vector<size_t> pair_of;
+        std::vector<rg_compare_pair> hinted(n_pairs);
+        char err[kPcmErrLen] = "";
+        for (size_t p = 0; p < n_pairs; ++p) {
+            hinted[p] = rg_compare_pair{pairs[p].a, pairs[p].b, hints[p]};
+            if (!loaded[pairs[p].a] || !loaded[pairs[p].b]) continue;  // (the record has the failing file's status)
+            RgCmpPair rec;
+            const int rc = rg_cmp_plan_pair(p, fdesc.data(), n, hinted[p], o, true, g.arena_bytes, &rec, err, sizeof err);
+            if (rc == RG_ERR_FORMAT) {
+                out[p].status = RG_ERR_FORMAT;
+                c->pair_errors[p] = std::string("No comparison (") + err + "): " + g.paths[pairs[p].a] + " against " + g.paths[pairs[p].b];
+                continue;
+            }
+            if (rc != RG_OK) return rg_set_err(c, rc, "%s", err);
+            plan.push_back(rec);
+            pair_of.push_back(p);
+        }
+        const size_t m = plan.size();
+        std::vector<RgCmpPicked> picked(m + 1);
+        std::vector<RgCmpTotals> tot(m + 1);
+        std::vector<int64_t> rows;
+        std::vector<rg_compare_block> blocks;
+        const int rc = rg_cmp_device(c, c->d_arena.p, plan.data(), m, o, &rows, picked.data(), tot.data(), &blocks, c->file_stream());
+        if (rc != RG_OK) return rc;
+        const size_t slab = (size_t)o.segments * RG_CMP_MAX_CHANNELS * rg_cmp_row_len(o.radius);
+        for (size_t j = 0; j < m; ++j) {
+            const size_t p = pair_of[j];
+            const RgCmpPair &r = plan[j];
+            const uint32_t da = dropped[pairs[p].a], db = dropped[pairs[p].b];
+            const uint32_t more = (o.align != RG_CMP_ALIGN_HINT && !coarse[p]) ? RG_CMP_NO_COARSE : 0u;
+            if (!r.cc) {
+                rg_cmp_fill_skipped(fdesc.data(), hinted[p], o, r, da, db, &out[p]);
+                if (!(r.flags & RG_CMP_RATE)) out[p].flags |= more;  // (another rate: nothing was looked for)
+                continue;
+            }
+            const rg_compare_block *mine = blocks.data() + r.first_block;
+            rg_cmp_fill(fdesc.data(), hinted[p], o, r, picked[j], tot[j], mine, da, db, more, &out[p]);
+            if (lag_sums) rg_cmp_rows_out(r, o, rows.data() + r.first_row * rg_cmp_row_len(o.radius), lag_sums + p * slab);
+            if (blocks_out) rg_cmp_blocks_out(r, mine, blocks_out + p * blocks_per_pair, blocks_per_pair);
+        }
+        return RG_OK;
+    };
+    const int rc = pcm_scan_group(g, "comparison", RG_CMP_MAX_CHANNELS, files.data(), add, finish);
+    if (rc != RG_OK) return rc;
+    for (size_t p = 0; p < n_pairs; ++p)  // a failing file fails its own pairs only: the record zero apart from `status`
+        for (const uint32_t i : {pairs[p].a, pairs[p].b})
+            if (files[i].status != RG_OK && out[p].status == RG_OK) {
+                memset(&out[p], 0, sizeof out[p]);
+                out[p].status = files[i].status;
+            }
+    return RG_OK;
+}
+
+extern "C" int rg_compare(rg_ctx *c, const char *const *paths, size_t n, const rg_compare_pair *pairs, size_t n_pairs, const rg_compare_opts *opts,
+                          rg_compare_result *out, rg_compare_block *blocks_out, size_t blocks_per_pair, int64_t *lag_sums) {
+    if (!c || (n && !paths) || (n_pairs && (!pairs || !out))) return RG_ERR_INVALID_ARG;
+    rg_compare_opts o;
+    char err[256] = "";
+    const int orc = rg_cmp_options(opts, &o, err, sizeof err);
+    if (orc != RG_OK) return rg_set_err(c, orc, "%s", err);
+    for (size_t p = 0; p < n_pairs; ++p) {
+        if (pairs[p].a >= n || pairs[p].b >= n) return rg_set_err(c, RG_ERR_INVALID_ARG, "pair %zu: (%u, %u) is not a pair of the %zu files", p, pairs[p].a, pairs[p].b, n);
+        if (pairs[p].a == pairs[p].b) return rg_set_err(c, RG_ERR_INVALID_ARG, "pair %zu: file %u against itself", p, pairs[p].a);
+        if (pairs[p].hint > RG_CMP_MAX_HINT || pairs[p].hint < -RG_CMP_MAX_HINT)
+            return rg_set_err(c, RG_ERR_INVALID_ARG, "pair %zu: a hint of %lld frames is beyond 2^32", p, (long long)pairs[p].hint);
+    }
+    if (n_pairs) memset(out, 0, n_pairs * sizeof *out);
+    const size_t slab = (size_t)o.segments * RG_CMP_MAX_CHANNELS * rg_cmp_row_len(o.radius);
+    if (lag_sums && n_pairs) memset(lag_sums, 0, n_pairs * slab * sizeof(int64_t));
+    if (blocks_out && n_pairs && blocks_per_pair) memset(blocks_out, 0, n_pairs * blocks_per_pair * sizeof *blocks_out);
+    return no_throw(c, [&]() -> int {
+        c->file_errors.assign(n, std::string());
+        c->pair_errors.assign(n_pairs, std::string());
+        int rc = rg_bind_device(c);
+        if (rc != RG_OK || !n || !n_pairs) return rc;
+        std::vector<std::pair<size_t, size_t>> groups;
+        file_groups(c, paths, n, &groups);
+        if (groups.size() != 1)
+            return rg_set_err(c, RG_ERR_REFUSED, "No comparison: the %zu files would be decoded in %zu groups, and the copies of a pair must lie on the device together", n,
+                              groups.size());
+        return compare_group(c, paths, n, pairs, n_pairs, o, out, blocks_out, blocks_per_pair, lag_sums);
+    });
+}
+
+extern "C" const char *rg_compare_error(const rg_ctx *c, size_t pair) { return c && pair < c->pair_errors.size() ? c->pair_errors[pair].c_str() : ""; }
 
 // ---- rg_same_recording_xrate: per group the resampler (rg_resample.hip) and the fingerprint kernels on its output, the match once
 // (include/mp3rgain_amd_resample.h).  The codes are kept as rg_same_recording keeps them; a group's resampled signals lie in

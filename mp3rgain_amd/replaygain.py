@@ -625,6 +625,185 @@ def stereo_from_record(r, error=None) -> StereoImage:
                          for f in _STEREO_FIELDS], error)
 
 
+_COMPARE_OPTS = ("align", "coarse_radius", "radius", "segments", "segment_frames", "block_frames", "drift_frames", "lock_permille", "requant_millilsb2")
+
+
+def _compare_opts(**given):
+    """(rg_compare_opts with a None field at its default, the pointer to pass: NULL when all are None)."""
+    defaults = dict(align=_capi.CMP_ALIGN_FINGERPRINT, coarse_radius=_capi.CMP_DEFAULT_COARSE_RADIUS, radius=_capi.CMP_DEFAULT_RADIUS,
+                    segments=_capi.CMP_DEFAULT_SEGMENTS, segment_frames=_capi.CMP_DEFAULT_SEGMENT_FRAMES, block_frames=0,
+                    drift_frames=_capi.CMP_DEFAULT_DRIFT_FRAMES, lock_permille=_capi.CMP_DEFAULT_LOCK_PERMILLE,
+                    requant_millilsb2=_capi.CMP_DEFAULT_REQUANT_MILLILSB2)
+    unknown = set(given) - set(_COMPARE_OPTS)
+    if unknown:
+        raise TypeError(f"unknown compare option(s): {sorted(unknown)}")
+    o = _capi.CompareOpts(*[int(defaults[f] if given.get(f) is None else given[f]) for f in _COMPARE_OPTS])
+    return o, (None if all(given.get(f) is None for f in _COMPARE_OPTS) else C.byref(o))
+
+
+def compare_arena(ctx, route: int, descs, pairs, arena, blocks_per_pair=0, lag_sums=False, **opts):
+    """rg_compare_arena without an Analyzer: routes 0 and 2 are host code and take ctx = None.  `pairs`: (a, b, hint) tuples of
+    indices into `descs`.  -> [CompareRecord]; with `blocks_per_pair` > 0 also a list, per pair, of its first CompareBlock rows;
+    with `lag_sums` also an int64 array [pair][segment][channel (8)][2 * radius + 3].  Options (radius, segments, segment_frames,
+    block_frames, drift_frames, lock_permille, requant_millilsb2, ...) None = the header's defaults."""
+    L = _capi.load()
+    n, n_pairs = len(descs), len(pairs)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    d = (_capi.TrackDesc * max(1, n))(*descs)
+    pr = (_capi.ComparePair * max(1, n_pairs))(*[_capi.ComparePair(int(a), int(b), int(h)) for a, b, h in pairs])
+    out = (_capi.CompareRecord * max(1, n_pairs))()
+    o, o_p = _compare_opts(**opts)
+    per = max(0, int(blocks_per_pair))
+    blocks = (_capi.CompareBlock * max(1, n_pairs * per))() if per else None
+    rows = np.zeros((max(1, n_pairs), max(1, min(o.segments, _capi.CMP_MAX_SEGMENTS)), _capi.CMP_MAX_CHANNELS,
+                     2 * min(o.radius, _capi.CMP_MAX_RADIUS) + 3), dtype=np.int64) if lag_sums else None
+    rc = L.rg_compare_arena(ctx, int(route), n, d, n_pairs, pr, o_p, arena.ctypes.data if arena.size else None, arena.size, out, blocks, per,
+                            rows.ctypes.data_as(C.POINTER(C.c_int64)) if lag_sums else None)
+    if rc != 0:
+        raise ReplayGainError(rc, L.rg_last_error(ctx).decode("utf-8", "replace"))
+    res = [list(out[:n_pairs])]
+    if per:
+        res.append([[blocks[p * per + k] for k in range(min(per, out[p].blocks))] for p in range(n_pairs)])
+    if lag_sums:
+        res.append(rows[:n_pairs])
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def compare_kernel_shape(fmt_a: int, fmt_b: int = None):
+    """rg_compare_kernel_shape of a pair's two rg_sample_formats -> (piece_frames, tile_frames, strip_frames, lag_group, lds_bytes)."""
+    v = [C.c_uint32() for _ in range(5)]
+    rc = _capi.load().rg_compare_kernel_shape(int(fmt_a), int(fmt_a if fmt_b is None else fmt_b), *[C.byref(x) for x in v])
+    if rc != 0:
+        raise ReplayGainError(rc, f"rg_compare_kernel_shape: formats {fmt_a}, {fmt_b}")
+    return tuple(x.value for x in v)
+
+
+_COMPARE_FLOATS = ("lock", "gain_db", "null_unity_db", "null_db", "residual_lsb2", "worst_block_db", "gain_min_db", "gain_max_db")
+_COMPARE_FIELDS = tuple(f for f, _ in _capi.CompareRecord._fields_ if f not in ("status", "reserved"))
+
+
+def _clock(frames, rate, millis=False):
+    """m:ss (or m:ss.mmm) of a frame index."""
+    if rate <= 0:
+        return f"frame {frames}"
+    s = frames / rate
+    return f"{int(s // 60)}:{s % 60:06.3f}" if millis else f"{int(s // 60)}:{int(s % 60):02d}"
+
+
+@dataclass
+class Comparison:
+    """One pair of a null test (rg_compare_result): how copy b relates to the reference copy a.  The definitions are a convention
+    of include/mp3rgain_amd_compare.h, held to no other tool."""
+    flags: int
+    a: int
+    b: int
+    frames_a: int
+    frames_b: int
+    sample_rate: int
+    channels: int
+    format_a: int
+    format_b: int
+    dropped_a: int
+    dropped_b: int
+    block_frames: int
+    radius: int
+    segments: int
+    locked_segments: int
+    polarity: int
+    max_diff: int
+    hint: int
+    lag: int                 # b[n + lag] lies beside a[n]
+    seg_lag_min: int
+    seg_lag_max: int
+    overlap: int
+    a_head: int
+    a_tail: int
+    b_head: int
+    b_tail: int
+    blocks: int
+    differing_blocks: int
+    worst_block: int
+    equal: int
+    first_diff: int          # frame index in a; _capi.CMP_NONE when no sample differs
+    nonfinite: int
+    aa: int
+    bb: int
+    ab: int
+    lock: float
+    gain_db: float
+    null_unity_db: float
+    null_db: float
+    residual_lsb2: float
+    worst_block_db: float
+    gain_min_db: float
+    gain_max_db: float
+    error: Optional["ReplayGainError"] = None  # why there are no numbers; every other field is then zero
+
+    def _has(self, bit) -> bool:
+        return bool(self.flags & bit)
+
+    @property
+    def complete(self) -> bool:
+        return self._has(_capi.CMP_COMPLETE)
+
+    @property
+    def verdicts(self) -> list:
+        """The flags as words, in a fixed order."""
+        names = (("different sample rate", _capi.CMP_RATE), ("no overlap", _capi.CMP_NO_OVERLAP), ("identical", _capi.CMP_IDENTICAL),
+                 ("same master", _capi.CMP_SAME_MASTER), ("differs", _capi.CMP_DIFFERS), ("unrelated", _capi.CMP_UNRELATED),
+                 ("inverted", _capi.CMP_INVERTED), ("shifted", _capi.CMP_SHIFTED), ("lengths differ", _capi.CMP_LENGTHS), ("drifts", _capi.CMP_DRIFT),
+                 ("at edge", _capi.CMP_AT_EDGE), ("no coarse match", _capi.CMP_NO_COARSE), ("channels differ", _capi.CMP_CHANNELS_DIFFER),
+                 ("nonfinite", _capi.CMP_NONFINITE))
+        words = [n for n, bit in names if self._has(bit)]
+        if self.error is None and not self.complete:
+            words.append("incomplete")
+        return words
+
+    def _placement(self) -> list:
+        """Where copy b's samples lie against the reference's, as phrases."""
+        out = []
+        if self.b_head:
+            out.append(f"starts {self.b_head} samples later")
+        if self.a_head:
+            out.append(f"starts {self.a_head} samples earlier")
+        if self.a_tail:
+            out.append(f"{self.a_tail} shorter at the end")
+        if self.b_tail:
+            out.append(f"{self.b_tail} longer at the end")
+        return out
+
+    @property
+    def reading(self) -> str:
+        """One line for a person, without the file's name."""
+        if self.error is not None:
+            return "failed"
+        if self._has(_capi.CMP_RATE):
+            return "different sample rate: not compared"
+        if self._has(_capi.CMP_NO_OVERLAP):
+            return "no overlap at the hint: not compared"
+        head = "inverted copy, " if self._has(_capi.CMP_INVERTED) else ""
+        if self._has(_capi.CMP_DRIFT):  # (segments that lock at different lags dilute the lock of the whole: asked first)
+            return f"{head}same recording, drifts  (lag {self.seg_lag_min} .. {self.seg_lag_max} samples over the file)"
+        if self._has(_capi.CMP_UNRELATED):
+            return f"not the same recording  (best correlation {self.lock:.2f})"
+        place = self._placement()
+        if self._has(_capi.CMP_IDENTICAL):
+            return ", ".join(["identical samples"] + place) if place else "identical"
+        tail = "".join(", " + p for p in place)
+        if self._has(_capi.CMP_SAME_MASTER):
+            return f"{head}same master  (gain {self.gain_db:+.2f} dB, residual {self.residual_lsb2:.2f} LSB^2{tail})"
+        B, rate = self.block_frames, self.sample_rate
+        t0 = self.a_head + self.worst_block * B
+        first = f", first difference at {_clock(self.first_diff, rate, True)}" if self.first_diff != _capi.CMP_NONE else ""
+        return (f"{head}same recording, differs  (null {self.null_db:.1f} dB after {self.gain_db:+.1f} dB, worst {_clock(t0, rate)}-{_clock(t0 + B, rate)} "
+                f"at {self.worst_block_db:.1f} dB{first}{tail})")
+
+
+def compare_from_record(r, error=None) -> Comparison:
+    """A Comparison from an rg_compare_result."""
+    return Comparison(*[(float if f in _COMPARE_FLOATS else int)(getattr(r, f)) for f in _COMPARE_FIELDS], error)
+
+
 def _clicks_opts(block_samples, order, ratio_permille, floor, gap, max_width, max_events):
     """rg_clicks_opts, or NULL (the header's defaults) when all are None; a None field is its default."""
     if all(v is None for v in (block_samples, order, ratio_permille, floor, gap, max_width, max_events)):
@@ -2426,6 +2605,67 @@ class Analyzer:
         ([stream bytes], [FlacEncodeRecord], offsets); route 0 = the serial host twin, route 1 = the arena copied to this GPU
         and the analyse, layout and write kernels."""
         return flac_encode_arena(self._ctx, route, descs, bps, arena, block_size, max_lpc_order)
+
+    def _compare_call(self, files, pairs, hints, blocks_per_pair, lag_sums, opts):
+        n = len(files)
+        if pairs is None:
+            pairs = [(0, j) for j in range(1, n)]  # every file against the first
+        if hints is not None:
+            hints = [int(hints)] * len(pairs) if np.isscalar(hints) else [int(h) for h in hints]
+            if len(hints) != len(pairs):
+                raise ValueError("compare: as many hints as pairs")
+            opts = dict(opts, align=_capi.CMP_ALIGN_HINT)
+        n_pairs = len(pairs)
+        paths, _ = self._file_args(files, _capi.CompareRecord)
+        pr = (_capi.ComparePair * max(1, n_pairs))(*[_capi.ComparePair(int(p[0]), int(p[1]), hints[k] if hints is not None else 0) for k, p in enumerate(pairs)])
+        out = (_capi.CompareRecord * max(1, n_pairs))()
+        o, o_p = _compare_opts(**opts)
+        per = max(0, int(blocks_per_pair))
+        blocks = (_capi.CompareBlock * max(1, n_pairs * per))() if per else None
+        rows = np.zeros((max(1, n_pairs), max(1, min(o.segments, _capi.CMP_MAX_SEGMENTS)), _capi.CMP_MAX_CHANNELS,
+                         2 * min(o.radius, _capi.CMP_MAX_RADIUS) + 3), dtype=np.int64) if lag_sums else None
+        self._check(self._lib.rg_compare(self._ctx, paths, n, pr, n_pairs, o_p, out, blocks, per, rows.ctypes.data_as(C.POINTER(C.c_int64)) if lag_sums else None))
+        return pairs, out, blocks, rows
+
+    def compare(self, files, pairs=None, hints=None, radius=None, blocks_per_pair=0, lag_sums=False, **opts) -> list:
+        """rg_compare, a null test: `files` (WAV, FLAC or MPEG Layer III) decoded by the route the analysis uses and, where the PCM
+        lies on this GPU, copy b of every pair lined up with the reference copy a to the sample, one gain fitted, and what is left
+        sized -> [Comparison], one per pair.  `pairs`: (a, b) indices into `files`, None = every file against the first.  `hints`:
+        None = the coarse lag comes from the fingerprint match; a number or one per pair = the expected lag in frames
+        (b[n + hint] beside a[n]).  With `blocks_per_pair` > 0 also, per pair, its first CompareBlock rows; with `lag_sums` also
+        the lag rows, an int64 array [pair][segment][channel (8)][2 * radius + 3].  A pair one of whose files fails carries that
+        file's ReplayGainError in `.error`."""
+        pairs, out, blocks, rows = self._compare_call(files, pairs, hints, blocks_per_pair, lag_sums, dict(opts, radius=radius))
+        recs = []
+        for k, p in enumerate(pairs):
+            err = None
+            if out[k].status != 0:
+                texts = [self._lib.rg_compare_error(self._ctx, k).decode("utf-8", "replace")]  # the pair's own text, then its files'
+                texts += [self._lib.rg_tracks_error(self._ctx, int(i)).decode("utf-8", "replace") for i in p[:2]]
+                err = ReplayGainError(int(out[k].status), next((t for t in texts if t), "not compared"))
+            recs.append(compare_from_record(out[k], err))
+        res = [recs]
+        if blocks_per_pair:
+            res.append([[blocks[k * blocks_per_pair + j] for j in range(min(blocks_per_pair, out[k].blocks))] for k in range(len(pairs))])
+        if lag_sums:
+            res.append(rows[:len(pairs)])
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def compare_raw(self, files, pairs=None, hints=None, blocks_per_pair=0, **opts):
+        """compare's rg_compare_result array as the C call left it, then the block rows' and the lag rows' bytes (tests compare
+        routes byte for byte)."""
+        pairs, out, blocks, rows = self._compare_call(files, pairs, hints, blocks_per_pair, True, opts)
+        return bytes(out)[:len(pairs) * C.sizeof(_capi.CompareRecord)], bytes(blocks) if blocks is not None else b"", rows[:len(pairs)].tobytes()
+
+    def compare_arena(self, route: int, descs, pairs, arena, blocks_per_pair=0, lag_sums=False, **opts):
+        """rg_compare_arena, the seam of the null-test kernels: the pairs (a, b, hint) of the tracks `descs` describe in the host
+        arena `arena` -> [CompareRecord] (with `blocks_per_pair` / `lag_sums`: and the block rows / the lag rows); route 0 = the
+        serial host twin, route 1 = the arena copied to this GPU and the kernels, route 2 = the kernels' cutting on the host."""
+        return compare_arena(self._ctx, route, descs, pairs, arena, blocks_per_pair, lag_sums, **opts)
+
+    @staticmethod
+    def compare_kernel_shape(fmt_a: int, fmt_b: int = None):
+        return compare_kernel_shape(fmt_a, fmt_b)
 
     def _clicks_call(self, files, block_samples, order, ratio_permille, floor, gap, max_width, max_events):
         paths, out = self._file_args(files, _capi.ClicksRecord)
